@@ -11,9 +11,12 @@ buffers so the 256 MiB Infinity Cache cannot hold the working set).  Frames are 
 ranks shard by frame with no data-path collective (weak scaling); `value` = pixels all ranks
 processed / max-over-ranks time.
 
-Extra, rank 0 at N=1 only, outside the timed region: the same kernel at 8K (the north-star
-roofline target), the HLG/PQ outputs, the encode-side kernels, and the CPU baseline (the real
-reference from oracle/_ref when it loads, else the C port) on a bounded sample.
+A plain run does only what the headline needs: set-up, clock ramp, W warm-up steps, the K timed
+steps, the outputs (--dump-outputs DIR) and the line.  With --full, after the timed region: the
+per-family kernel times of the step, the roofline kernel at 8K (the north-star target), the
+striped encode (config 4; every rank), and at N=1 on rank 0 the HLG/PQ outputs, the encode-side
+kernels and the CPU baseline (the real reference from oracle/_ref when it loads, else the C port)
+on a bounded sample.
 """
 import argparse
 import ctypes as C
@@ -48,7 +51,15 @@ def parse():
     ap.add_argument("--no-config4", action="store_true", help="skip the row-striped two-pass encode leg (the RCCL collective)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure everything beyond the headline (per-family kernel times, the 8K roofline "
+                         "kernel, config 4 / 5, encode chains, extras, API level, CPU baselines); --no-extra / --no-config4 / --no-cpu trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (scans, metadata, a fixed sample of the decoded frame) to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 MAP_DESC = {"A": "Y400 gain map (scale 4)", "B": "RGB888 gain map (scale 1)", "C": "RGBA8888 gain map (scale 1)"}
@@ -226,6 +237,48 @@ def make_roundtrip(ctx, u, device, w, h, seed=1234):
     return enc, dec, box
 
 
+DUMP_SEED = 20251016
+DUMP_PIXELS = 1 << 20  # decoded pixels kept: x 4 channels x 4 bytes = 16 MiB
+DUMP_SCAN_BYTES = 4 << 20  # bytes kept per scan: x 4 bytes = 16 MiB; all three arrays + the pixel index stay under 64 MB
+
+
+def seeded_sample(n, k, seed):
+    """Sorted positions of a fixed, seeded sample of k of n elements; all of them when n <= k."""
+    import numpy as np
+
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(out_dir, box, w, h):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files under out_dir.  Inputs are
+    synthesised from fixed seeds, so two builds given the same arguments can be compared file for file:
+      base_scan, map_scan  the two entropy-coded scans, one byte per element (beyond DUMP_SCAN_BYTES: a fixed seeded sample)
+      scan_bytes           the lengths of the two scans
+      metadata             the gain-map metadata: max / min content boost, gamma, offset sdr / hdr (3 each), hdr capacity
+                           min / max, use_base_cg
+      decoded_rgba         the decoded RGBA_F16 frame as float32, (DUMP_PIXELS, 4) at a fixed seeded sample of pixels ...
+      decoded_index        ... whose positions (row * width + column) are these"""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    out_b, out_m = box["keep"][2], box["keep"][3]
+    nb, nm = int(box["nb"]), int(box["nm"])
+    for name, t, n, seed in (("base_scan", out_b, nb, DUMP_SEED), ("map_scan", out_m, nm, DUMP_SEED + 1)):
+        v = t[:n].cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), v[seeded_sample(n, DUMP_SCAN_BYTES, seed)].astype(np.float32))
+    np.save(os.path.join(out_dir, "scan_bytes.npy"), np.array([nb, nm], dtype=np.float64))
+    md = box["md"]
+    fields = [list(md.max_content_boost), list(md.min_content_boost), list(md.gamma), list(md.offset_sdr), list(md.offset_hdr),
+              [md.hdr_capacity_min, md.hdr_capacity_max, md.use_base_cg]]
+    np.save(os.path.join(out_dir, "metadata.npy"), np.array([x for f in fields for x in f], dtype=np.float64))
+    px = np.ascontiguousarray(box["dst"].to_host().valid(0)).view(np.float16).reshape(w * h, 4)
+    idx = seeded_sample(w * h, DUMP_PIXELS, DUMP_SEED + 2)
+    np.save(os.path.join(out_dir, "decoded_rgba.npy"), px[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "decoded_index.npy"), idx.astype(np.float64))
+
+
 def main():
     args = parse()
     import torch
@@ -291,21 +344,24 @@ def main():
         step()
     barrier()
     t1 = time.perf_counter()
-    # ... and, OUTSIDE it, the same steps once more with the library's per-family HIP-event pairs on (two hipEventCreate + two hipEventRecord per
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, box, w, h)
+    # ... and, OUTSIDE it (--full), the same steps once more with the library's per-family HIP-event pairs on (two hipEventCreate + two hipEventRecord per
     # family scope, ~16 scopes per round trip: through round 6's first lines this rode along INSIDE the timed region and cost it ~70 us per step)
     fam_steps = max(1, min(args.steps, 10))
-    ctx.profile(True)
-    ctx.profile_read(None, reset=True)
-    for _ in range(fam_steps):
-        step()
-    barrier()
     fam_us = {}
-    for f in fams:
-        n_f, ms_f = ctx.profile_read(f, reset=True)
-        if n_f:
-            fam_us[f] = {"us": round(ms_f / fam_steps * 1e3, 2), "launches": n_f // fam_steps}
-    ctx.profile_read(None, reset=True)
-    ctx.profile(False)
+    if args.full:
+        ctx.profile(True)
+        ctx.profile_read(None, reset=True)
+        for _ in range(fam_steps):
+            step()
+        barrier()
+        for f in fams:
+            n_f, ms_f = ctx.profile_read(f, reset=True)
+            if n_f:
+                fam_us[f] = {"us": round(ms_f / fam_steps * 1e3, 2), "launches": n_f // fam_steps}
+        ctx.profile_read(None, reset=True)
+        ctx.profile(False)
     st1 = A.Stats()
     ctx.lib.uhdr_hip_get_stats(ctx.handle, C.byref(st1))
     ctx.stream_safe = True
@@ -336,19 +392,21 @@ def main():
             "clock_ramp": f"{ramp_steps} untimed steps ({ramp_seconds:.1f} s) before the {args.warmup} warm-up steps (profiles/r03_clock_ramp.txt)",
             "sharding": f"frames x{world} ranks, no data-path collective",
         },
-        "step": {"kernel_families_us_per_step": fam_us, "kernel_families_note": f"{fam_steps} more steps after the timed region, the library's per-family event pairs on",
-                 "scan_bytes_base": box["nb"], "scan_bytes_map": box["nm"],
+        "step": {"scan_bytes_base": box["nb"], "scan_bytes_map": box["nm"],
                  "decode_route": {"parallel": int(st1.entropy_decode_parallel - st0.entropy_decode_parallel),
                                   "single_lane": int(st1.entropy_decode_single_lane - st0.entropy_decode_single_lane),
                                   "declined": int(st1.entropy_decode_declined - st0.entropy_decode_declined)}},
         "roofline": {"bound": "hbm", "kernel": None, "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None},
     }
+    if args.full:
+        full["step"]["kernel_families_us_per_step"] = fam_us
+        full["step"]["kernel_families_note"] = f"{fam_steps} more steps after the timed region, the library's per-family event pairs on"
     del enc, dec, box, step
     torch.cuda.empty_cache()
 
     # ---- roofline: the dominant HBM kernel of the path -- applyGainMap -> RGBA_F16 -- at the north-star size (ONE 7680x4320
     # frame per launch, RGBA8888 map at scale 1), HIP events around every launch on the library's stream, live in this run (rank 0)
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             full["roofline"] = roofline_section(ctx, device, w, h, light=headline_only)
         except Exception as e:  # noqa: BLE001
@@ -356,7 +414,7 @@ def main():
 
     # BASELINE configs[3]: the row-striped API-1 two-pass encode, the one place where the path has a collective.  Every
     # rank runs it (also at N = 1: a one-rank communicator), after the headline's timed region.
-    if not args.no_config4 and not headline_only:
+    if args.full and not args.no_config4 and not headline_only:
         # The headline is measured; nothing after it may cost the line.  An exception is caught below, but a collective that
         # never returns (a communicator that cannot form on some node) cannot be: a watchdog prints the line and leaves.
         dog = arm_watchdog(180.0 if world > 1 else 600.0, full, rank, "config4")
@@ -370,7 +428,7 @@ def main():
 
     # the stage measurements and the CPU baseline run AFTER the timed region; a failure there (e.g. an
     # out-of-memory on a smaller device) must not cost the headline line
-    if rank == 0 and world == 1 and not args.no_extra and not headline_only:
+    if rank == 0 and world == 1 and args.full and not args.no_extra and not headline_only:
         for key, fn in (("api1_roundtrip", lambda: api1_roundtrip_section(ctx, u, device)),
                         ("api1_concurrent", lambda: concurrent_section(device, dev_index)),
                         ("headline_16x4k", lambda: batch16_section(ctx, u, device, args)),
@@ -380,7 +438,7 @@ def main():
                 full[key] = fn()
             except Exception as e:  # noqa: BLE001  (a failure in one section must not cost the headline line)
                 full[key] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         try:
             full["cpu_baseline"] = cpu_baseline(w, h, args.cpu_seconds, stages=not args.no_extra)
         except Exception as e:  # noqa: BLE001

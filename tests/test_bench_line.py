@@ -75,3 +75,48 @@ def test_emit_prints_the_compact_line_last(tmp_path, monkeypatch, capsys):
 def test_bench_never_switches_the_stderr_trace_on():
     src = open(os.path.join(os.path.dirname(os.path.abspath(bench.__file__)), "bench.py")).read()
     assert "UHDR_HIP_SEAM_TRACE" not in src
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_are_float_arrays_of_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs on a host stand-in for the round trip's buffers: float32 / float64 files only, the sampled pixels are the
+    frame's own at the recorded positions, and the sample is the same from run to run."""
+    import numpy as np
+    import torch
+
+    from libultrahdr_amd import capi as A
+    from libultrahdr_amd.images import Image
+
+    monkeypatch.setattr(bench, "DUMP_PIXELS", 500)
+    monkeypatch.setattr(bench, "DUMP_SCAN_BYTES", 300)
+    w, h = 64, 24
+    rng = np.random.default_rng(3)
+    dst = Image(A.UHDR_IMG_FMT_64bppRGBAHalfFloat, w, h, align=64)
+    dst.valid(0)[:] = rng.random((h, w * 4), dtype=np.float32).astype(np.float16).view(np.uint64).reshape(h, w)
+    md = A.GainmapMetadata()
+    md.max_content_boost[2], md.hdr_capacity_max, md.use_base_cg = 4.5, 2.25, 1
+    scan_b = torch.from_numpy(rng.integers(0, 256, 1000, dtype=np.uint8))
+    box = {"keep": (None, None, scan_b, torch.arange(200, dtype=torch.uint8)), "nb": 900, "nm": 150, "md": md, "dst": dst}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), box, w, h)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["base_scan.npy", "decoded_index.npy", "decoded_rgba.npy", "map_scan.npy", "metadata.npy", "scan_bytes.npy"]
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    d = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert d["scan_bytes"].tolist() == [900, 150] and d["map_scan"].tolist() == list(range(150))
+    assert d["base_scan"].shape == (300,) and set(d["base_scan"].tolist()) <= set(scan_b[:900].numpy().tolist())
+    assert d["metadata"].shape == (18,) and d["metadata"][2] == 4.5 and d["metadata"][16:].tolist() == [2.25, 1.0]
+    idx = d["decoded_index"].astype(np.int64)
+    assert d["decoded_rgba"].shape == (500, 4) and len(set(idx.tolist())) == 500 and idx.max() < w * h
+    px = dst.valid(0).view(np.float16).reshape(w * h, 4).astype(np.float32)
+    assert np.array_equal(d["decoded_rgba"], px[idx])

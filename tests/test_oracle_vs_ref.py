@@ -1,8 +1,13 @@
 """Pins the C restatement (oracle "port") against the REAL reference compiled into oracle/_ref:
 bit-for-bit on seeded images for every stage of the hot path, and the DCT/quantize restatement
 against libjpeg itself (jpeg_read_coefficients on the JPEG the reference's helper produces).
-Skipped where oracle/_ref is not built (it needs /root/reference)."""
+The libjpeg tests are skipped where oracle/_ref is not built (it needs the reference's sources).  The stage tests
+(applyGainMap, generateGainMap, toneMap, convertYuv, convert_raw_input_to_ycbcr) run everywhere: what the reference
+returns -- a SHA-256 per image plane, the metadata's bytes, or the error code -- is recorded per test in
+tests/golden/oracle_ref_outputs.json (tests/ref_record.py: live where oracle/_ref is built, replayed elsewhere)."""
 import ctypes as C
+import hashlib
+import types
 
 import numpy as np
 import pytest
@@ -12,20 +17,55 @@ from libultrahdr_amd import synth
 from libultrahdr_amd.images import Image
 from oracle import loader as L
 
-pytestmark = pytest.mark.usefixtures("ref")
+import ref_record
+
+
+class RecordedImage:
+    """What the record keeps of an image the reference returned: its descriptor and a digest per valid plane."""
+
+    def __init__(self, d):
+        self.fmt, self.w, self.h, cg, ct, rng = d["image"]
+        self.raw = types.SimpleNamespace(fmt=self.fmt, w=self.w, h=self.h, cg=cg, ct=ct, range=rng)
+        self.digests = d["planes"]
+
+
+def _digests(img):
+    if isinstance(img, RecordedImage):
+        return img.digests
+    return [hashlib.sha256(repr((p.dtype.str, p.shape)).encode() + np.ascontiguousarray(p).tobytes()).hexdigest() for p in img.planes_valid()]
+
+
+def _fingerprint(out):
+    if isinstance(out, tuple):  # generate_gainmap: (metadata, map)
+        return {"md": bytes(out[0]).hex(), "gm": _fingerprint(out[1])}
+    return {"image": [out.fmt, out.w, out.h, out.raw.cg, out.raw.ct, out.raw.range], "planes": _digests(out)}
+
+
+def _replay(item):
+    if "md" in item:
+        return A.GainmapMetadata.from_buffer_copy(bytes.fromhex(item["md"])), RecordedImage(item["gm"])
+    return RecordedImage(item)
+
+
+@pytest.fixture
+def ref_outputs(request, monkeypatch):
+    """L.<stage>("ref", ...) answers as the reference does."""
+    yield from ref_record.answers(
+        request, monkeypatch, "oracle_ref_outputs.json", L,
+        ("apply_gainmap", "generate_gainmap", "tone_map", "convert_yuv", "convert_raw_input_to_ycbcr"),
+        fingerprint=lambda name, a, out: _fingerprint(out), replay=lambda name, item: _replay(item),
+        is_ref=lambda lib_kind, *a, **kw: lib_kind == "ref")
 
 
 def same(a: Image, b: Image):
-    for pa, pb in zip(a.planes_valid(), b.planes_valid()):
-        if not np.array_equal(pa, pb):
-            return False
-    return True
+    return _digests(a) == _digests(b)
 
 
 def md_equal(a, b):
     return bytes(a) == bytes(b)
 
 
+@pytest.mark.usefixtures("ref_outputs")
 @pytest.mark.parametrize("ch,alpha,scale", [(1, False, 4), (1, False, 2), (1, False, 1), (3, False, 1), (3, True, 1),
                                             (3, False, 2), (3, True, 4), (1, False, 8)])
 @pytest.mark.parametrize("out_ct", [A.UHDR_CT_LINEAR, A.UHDR_CT_HLG, A.UHDR_CT_PQ])
@@ -38,6 +78,7 @@ def test_apply_gainmap_420(ch, alpha, scale, out_ct):
         assert same(L.apply_gainmap("port", sdr, gm, md, out_ct), L.apply_gainmap("ref", sdr, gm, md, out_ct))
 
 
+@pytest.mark.usefixtures("ref_outputs")
 def test_apply_gainmap_variants():
     w, h = 130, 66  # not multiples of 4 / 8
     rng = np.random.default_rng(7)
@@ -97,6 +138,7 @@ def _make_pair(w, h, hdr_kw, sdr_kind):
     return sdr, hdr
 
 
+@pytest.mark.usefixtures("ref_outputs")
 @pytest.mark.parametrize("hdr_kw,sdr_kind,cfg_kw", GEN_CASES)
 def test_generate_gainmap(hdr_kw, sdr_kind, cfg_kw):
     sdr, hdr = _make_pair(96, 48, hdr_kw, sdr_kind)
@@ -108,6 +150,7 @@ def test_generate_gainmap(hdr_kw, sdr_kind, cfg_kw):
     assert md_equal(md_p, md_r), (md_p.as_dict(), md_r.as_dict())
 
 
+@pytest.mark.usefixtures("ref_outputs")
 def test_generate_gainmap_other_formats():
     w, h = 64, 32
     rng = np.random.default_rng(3)
@@ -129,6 +172,7 @@ def test_generate_gainmap_other_formats():
             assert same(gm_p, gm_r) and md_equal(md_p, md_r)
 
 
+@pytest.mark.usefixtures("ref_outputs")
 @pytest.mark.parametrize("kind,ct,cg", [("p010", A.UHDR_CT_HLG, A.UHDR_CG_BT_2100), ("p010", A.UHDR_CT_PQ, A.UHDR_CG_DISPLAY_P3),
                                         ("1010102", A.UHDR_CT_PQ, A.UHDR_CG_BT_2100), ("1010102", A.UHDR_CT_HLG, A.UHDR_CG_BT_709),
                                         ("p010", A.UHDR_CT_LINEAR, A.UHDR_CG_BT_2100)])
@@ -140,6 +184,7 @@ def test_tone_map(kind, ct, cg):
     assert (a.raw.cg, a.raw.ct, a.raw.range) == (b.raw.cg, b.raw.ct, b.raw.range) == (A.UHDR_CG_DISPLAY_P3, A.UHDR_CT_SRGB, A.UHDR_CR_FULL_RANGE)
 
 
+@pytest.mark.usefixtures("ref_outputs")
 def test_tone_map_444_and_f16():
     w, h = 48, 24
     rng = np.random.default_rng(5)
@@ -152,6 +197,7 @@ def test_tone_map_444_and_f16():
     assert same(L.tone_map("port", f16), L.tone_map("ref", f16))
 
 
+@pytest.mark.usefixtures("ref_outputs")
 @pytest.mark.parametrize("src,dst", [(0, 1), (0, 2), (1, 0), (1, 2), (2, 0), (2, 1), (1, 1)])
 def test_convert_yuv(src, dst):
     rng = np.random.default_rng(11)
@@ -161,6 +207,7 @@ def test_convert_yuv(src, dst):
         assert same(L.convert_yuv("port", img, src, dst), L.convert_yuv("ref", img, src, dst))
 
 
+@pytest.mark.usefixtures("ref_outputs")
 @pytest.mark.parametrize("fmt", [A.UHDR_IMG_FMT_32bppRGBA1010102, A.UHDR_IMG_FMT_32bppRGBA8888, A.UHDR_IMG_FMT_24bppRGB888])
 @pytest.mark.parametrize("chroma", [False, True])
 def test_convert_raw_input_to_ycbcr(fmt, chroma):

@@ -21,7 +21,7 @@ limited() {  # run "$@" in its own session; SIGKILL the whole group after $LIMIT
 }
 cd /tmp && export TMPDIR=/tmp
 export UHDR_BENCH_HEADLINE_ONLY=1  # no 8K north-star launches (same kernel name, other grid): the statistics below are the headline launch's
-CMD="python $R/bench.py --steps 10 --warmup 2 --no-extra --no-cpu --no-config4"
+CMD="python $R/bench.py --steps 10 --warmup 2 --full --no-extra --no-cpu --no-config4"  # --full: the roofline kernel's 8K launches
 limited rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- $CMD > $OUT/trace.log 2>&1 || echo "trace pass failed / timed out" >> $OUT/errors.log
 i=0
 export UHDR_BENCH_CLOCK_RAMP_S=0.05  # the byte counters do not depend on the clock; 2000 ramp launches would only bloat the databases

@@ -32,7 +32,7 @@ sha = bench.library_sha256()
 rd, wr = int(round(2 * fetch * 1024)), int(round(write * 1024))
 out = {"apply_quad_kernel<F16,RGBA8888,scale1>|1x7680x4320": {
     "traffic_bytes_per_launch": rd + wr, "read_bytes": rd, "write_bytes": wr, "library_sha256": sha,
-    "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, tools/profile_bench.sh) of `python bench.py --steps 10 --warmup 2 --no-extra --no-cpu "
+    "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, tools/profile_bench.sh) of `python bench.py --steps 10 --warmup 2 --full --no-extra --no-cpu "
               f"--no-config4` (UHDR_BENCH_HEADLINE_ONLY: the round-trip steps + the roofline kernel's 8K launches), {nf} / {nw} dispatches; FETCH_SIZE / WRITE_SIZE are in KiB, read bytes = 2 x FETCH_SIZE on gfx950 "
               f"(MI355X_MICROARCH.md); {committed_as}"}}
 if len(sys.argv) > 4:
