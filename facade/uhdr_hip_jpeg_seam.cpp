@@ -242,7 +242,8 @@ namespace {
 
 // true: the device decoded the whole scan (*st = result).  false: not a file for the device path; nothing consumed.
 bool device_scan_decode(jpeg_decompress_struct* cinfo, bool want_rgb, unsigned char* dest, const unsigned int hstride[3],
-                        const unsigned int vstride[3], uhdr_img_fmt_t planar_fmt, uhdr_img_fmt_t* out_fmt, uhdr_error_info_t* st) {
+                        const unsigned int vstride[3], uhdr_img_fmt_t planar_fmt, uhdr_img_fmt_t* out_fmt, uhdr_error_info_t* st,
+                        bool* reached = nullptr) {
   const int nc = cinfo->num_components;
   if (cinfo->progressive_mode || cinfo->arith_code || cinfo->data_precision != 8) return false;
   if (cinfo->comps_in_scan != nc || cinfo->Ss != 0 || cinfo->Se != 63 || cinfo->Ah != 0 || cinfo->Al != 0) return false;
@@ -286,13 +287,21 @@ bool device_scan_decode(jpeg_decompress_struct* cinfo, bool want_rgb, unsigned c
     variant = JPEG_LIB_VERSION >= 90 ? 1 : 0;  // IJG 9 refined the green-term constants (jdcolor.c)
 #endif
   }
+  uhdr_error_info_t r;
+  if (want_rgb && planar_fmt == UHDR_IMG_FMT_12bppYCbCr420) {
+    // 4:2:0 -> RGB: the libjpeg family's chroma reconstruction on the device (turbo's fancy upsampling / IJG 9's 16x16 chroma IDCT)
+    if (reached) *reached = true;  // decode_rgb tallies its own outcome from here on
+    if (!decode_rgb(&hdr, cinfo->src->next_input_byte, cinfo->src->bytes_in_buffer, channels, variant, dest, hstride[0], &r)) return false;
+    *st = r;
+    if (r.error_code == UHDR_CODEC_OK) *out_fmt = channels == 4 ? UHDR_IMG_FMT_32bppRGBA8888 : UHDR_IMG_FMT_24bppRGB888;
+    return true;
+  }
   unsigned char* planes[3] = {nullptr, nullptr, nullptr};
   size_t off = 0;
   for (int c = 0; c < (want_rgb ? 1 : nc); c++) {
     planes[c] = dest + off;
     off += (size_t)hstride[c] * vstride[c];
   }
-  uhdr_error_info_t r;
   if (!decode_scan(&hdr, cinfo->src->next_input_byte, cinfo->src->bytes_in_buffer, channels, variant, planes, hstride, vstride, &r)) return false;
   *st = r;
   if (r.error_code == UHDR_CODEC_OK)
@@ -326,7 +335,17 @@ bool jpeg_decompress_on_device(jpeg_decompress_struct* cinfo, bool want_rgb, uns
       else if (mh == 2 && mv == 1) fmt = UHDR_IMG_FMT_16bppYCbCr422;
       else if (mh == 2 && mv == 2) fmt = UHDR_IMG_FMT_12bppYCbCr420;
       else return false;
-      if (want_rgb && fmt != UHDR_IMG_FMT_24bppYCbCr444) return false;  // libjpeg's fancy upsampling stays libjpeg's
+      if (want_rgb && fmt == UHDR_IMG_FMT_16bppYCbCr422) return false;  // libjpeg's h2v1 upsampling stays libjpeg's
+    }
+    if (want_rgb && fmt == UHDR_IMG_FMT_12bppYCbCr420) {
+      // 4:2:0 -> RGB exists on the device only as the whole-file decode: the coefficient route below (jpeg_read_coefficients) has
+      // no way back to libjpeg's upsampler, so every reason to keep libjpeg is settled here, before that call
+      if (getenv("UHDR_HIP_SEAM_CPU_UPSAMPLE")) { decline("jpeg_decode_rgb", "UHDR_HIP_SEAM_CPU_UPSAMPLE"); return false; }
+      if (getenv("UHDR_HIP_SEAM_CPU_ENTROPY")) { decline("jpeg_decode_rgb", "UHDR_HIP_SEAM_CPU_ENTROPY"); return false; }
+      bool reached = false;
+      if (device_scan_decode(cinfo, want_rgb, dest, hstride, vstride, fmt, out_fmt, st, &reached)) return true;
+      if (!reached) decline("jpeg_decode_rgb", "not a baseline single-scan file the device decodes");
+      return false;
     }
 
     // Whole decode on the device when the file is what libjpeg writes by default (baseline, one interleaved scan, 8 bit):

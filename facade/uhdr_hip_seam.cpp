@@ -613,6 +613,29 @@ bool decode_scan(const void* hdr, const unsigned char* data, size_t bytes, int o
   return on_device_;
 }
 
+bool decode_rgb(const void* hdr, const unsigned char* data, size_t bytes, int channels, int libjpeg_variant, unsigned char* rgb,
+                unsigned int stride_px, uhdr_error_info_t* st) {
+  // every exit that leaves the work to the reference's CPU code drops the device-resident copies
+  const bool on_device_ = [&]() -> bool {
+    if (!cur()) return false;
+    enter();
+    *st = uhdr_hip_jpeg_decode_rgb(cur(), static_cast<const uhdr_hip_jpeg_header_t*>(hdr), data, bytes, channels, libjpeg_variant, rgb, stride_px);
+    // corrupt entropy-coded data: libjpeg decodes such files with warnings and padding; that behaviour stays libjpeg's
+    if (st->error_code == UHDR_CODEC_INVALID_PARAM) {
+      note("jpeg_decode_rgb", false, st->has_detail ? st->detail : "");
+      return false;
+    }
+    return handled(*st, "jpeg_decode_rgb");
+  }();
+  if (!on_device_) drop_resident();
+  return on_device_;
+}
+
+void decline(const char* stage, const char* why) {
+  if (cur()) note(stage, false, why);
+  drop_resident();
+}
+
 bool encode_scan(const void* scan, const void* qtables, const unsigned char* const planes[3], const unsigned int strides[3],
                  int rgb_channels, unsigned char* out, size_t cap, size_t* bytes, uhdr_error_info_t* st) {
   // every exit that leaves the work to the reference's CPU code drops the device-resident copies: that code may write the

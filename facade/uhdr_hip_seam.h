@@ -151,6 +151,15 @@ bool decode_scan(const void* hdr, const unsigned char* data, size_t bytes, int o
                  unsigned char* const planes[3], const unsigned int hstride[3], const unsigned int vstride[3],
                  uhdr_error_info_t* st);
 
+// A whole baseline 4:2:0 file to packed RGB888 / RGBA8888 on the device (uhdr_hip_jpeg_decode_rgb: entropy decode, IDCT, the
+// libjpeg family's chroma reconstruction, ycc_rgb_convert): rgb = the helper's result buffer, stride_px its row pitch in pixels.
+// Same contract as decode_scan: false = the device path does not take this file, nothing was consumed.
+bool decode_rgb(const void* hdr, const unsigned char* data, size_t bytes, int channels, int libjpeg_variant, unsigned char* rgb,
+                unsigned int stride_px, uhdr_error_info_t* st);
+// a stage the seam leaves to the reference's CPU code before calling into the library (a route option, a layout it does not
+// take): tallied as that stage's reference route, and the device-resident copies are dropped
+void decline(const char* stage, const char* why);
+
 // The mirror for the encoder (uhdr_hip_jpeg_encode_scan): samples -> entropy-coded data with restart markers, on the device.
 // scan is a uhdr_hip_jpeg_scan_t, qtables a uint16_t[3][64].
 bool encode_scan(const void* scan, const void* qtables, const unsigned char* const planes[3], const unsigned int strides[3],

@@ -569,6 +569,31 @@ uhdr_error_info_t uhdr_hip_jpeg_decode_scan(uhdr_hip_ctx_t* ctx, const uhdr_hip_
                                             int libjpeg_variant, uint8_t* const planes[3],
                                             const unsigned int hstride[3], const unsigned int vstride[3]);
 
+/* 4:2:0 JPEG -> packed RGB888 / RGBA8888 (alpha 255), libjpeg-exact.  What uhdr_decode does for UHDR_CT_SRGB /
+ * UHDR_IMG_FMT_32bppRGBA8888 output (jpegr.cpp:1479-1525): JpegDecoderHelper::decompressImage(DECODE_TO_RGB_CS)
+ * (jpegdecoderhelper.cpp:349-375, decodeToCSRGB :456-478), i.e. libjpeg's jpeg_read_scanlines of the base image.
+ * libjpeg_variant selects the libjpeg family, which rebuilds the chroma differently: 0 = libjpeg-turbo (8x8 islow IDCT,
+ * h2v2_fancy_upsample; plain 2x2 replication when ceil(w/2) <= 2), 1 = IJG libjpeg 9 (each chroma block rebuilt as 16x16
+ * samples by jpeg_idct_16x16); each with its own ycc_rgb_convert constants (uhdr_hip_jpeg_ycc_to_rgb).
+ *
+ * _dev: coef_y / coef_cb / coef_cr = DEVICE JBLOCK arrays (16-byte aligned) on libjpeg's width_in_blocks grids:
+ * ceil(w/8) x ceil(h/8) luma blocks, ceil(w/16) x ceil(h/16) blocks per chroma component (the layout
+ * uhdr_hip_idct_dequant_dev reads); qt_*: natural order, Cb and Cr may differ.  rgb: DEVICE image of w x h,
+ * UHDR_IMG_FMT_24bppRGB888 or UHDR_IMG_FMT_32bppRGBA8888, stride in pixels.  Stream-ordered, no host synchronisation.
+ *
+ * uhdr_hip_jpeg_decode_rgb: the whole file, as uhdr_hip_jpeg_decode_scan takes it (hdr, HOST scan_data / scan_bytes): the
+ * compressed bytes go up, the pixels come down into the HOST buffer rgb (row pitch stride_px PIXELS).  out_channels 3 / 4.
+ * 4:2:0 and 4:4:4 files; 4:4:4 takes uhdr_hip_jpeg_decode_scan's fused path (one chroma quantization table).  Any other
+ * sampling: UHDR_CODEC_UNSUPPORTED_FEATURE.  The device copies the resident handoff keeps of rgb are dropped (4:2:0) or
+ * registered as by uhdr_hip_jpeg_decode_scan (4:4:4).  Synchronous. */
+uhdr_error_info_t uhdr_hip_idct_upsample_rgb_dev(uhdr_hip_ctx_t* ctx, const int16_t* coef_y, const int16_t* coef_cb,
+                                                 const int16_t* coef_cr, unsigned int w, unsigned int h,
+                                                 const uint16_t qt_y[64], const uint16_t qt_cb[64], const uint16_t qt_cr[64],
+                                                 int libjpeg_variant, uhdr_raw_image_t* rgb);
+uhdr_error_info_t uhdr_hip_jpeg_decode_rgb(uhdr_hip_ctx_t* ctx, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data,
+                                           size_t scan_bytes, int out_channels, int libjpeg_variant, uint8_t* rgb,
+                                           unsigned int stride_px);
+
 /* The encode-side mirror: JpegEncoderHelper::compressImage's sample -> entropy-coded-data part
  * (jpegencoderhelper.cpp:131-309) on the device.  FDCT + quantization (uhdr_hip_fdct_quant_dev; for a packed RGB gain map
  * uhdr_hip_fdct_quant_rgb_dev, i.e. rgb_ycc_convert included) feed uhdr_hip_huffman_encode_dev without the coefficient
@@ -754,6 +779,7 @@ typedef struct uhdr_hip_stats {
    * C / C++ caller such as the facade pays, without the overhead of whatever binding drives the library */
   unsigned long long last_jpeg_decode_scan_ns;
   unsigned long long last_encode_api1_scans_ns;
+  unsigned long long last_jpeg_decode_rgb_ns;     /* uhdr_hip_jpeg_decode_rgb, the same way */
 } uhdr_hip_stats_t;
 void uhdr_hip_get_stats(uhdr_hip_ctx_t* ctx, uhdr_hip_stats_t* out);
 

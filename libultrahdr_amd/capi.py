@@ -166,7 +166,8 @@ class Stats(C.Structure):
     _fields_ = [(n, C.c_ulonglong) for n in ("entropy_decode_parallel", "entropy_decode_intervals", "entropy_decode_single_lane",
                                               "entropy_decode_declined", "entropy_encode_stream", "entropy_encode_intervals", "resident_hits",
                                               "generate_channels_tabled", "generate_channels_per_sample", "lazy_downloads_skipped",
-                                              "lazy_downloads_done", "last_jpeg_decode_scan_ns", "last_encode_api1_scans_ns")]
+                                              "lazy_downloads_done", "last_jpeg_decode_scan_ns", "last_encode_api1_scans_ns",
+                                              "last_jpeg_decode_rgb_ns")]
 
 
 class SeamStage(C.Structure):  # uhdr_hip_seam_stage_t
@@ -241,6 +242,9 @@ _SIGS = {
     "uhdr_hip_huffman_decode_dev": (ErrorInfo, [C.c_void_p, _P(JpegScan), _P(HuffTables), C.c_void_p, C.c_size_t]),
     "uhdr_hip_jpeg_parse": (C.c_int, [C.c_void_p, C.c_size_t, _P(JpegHeader)]),
     "uhdr_hip_jpeg_decode_scan": (ErrorInfo, [C.c_void_p, _P(JpegHeader), C.c_void_p, C.c_size_t, C.c_int, C.c_int, _P(C.c_void_p), _P(C.c_uint), _P(C.c_uint)]),
+    "uhdr_hip_idct_upsample_rgb_dev": (ErrorInfo, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, _P(C.c_uint16), _P(C.c_uint16),
+                                                   _P(C.c_uint16), C.c_int, _P(RawImage)]),
+    "uhdr_hip_jpeg_decode_rgb": (ErrorInfo, [C.c_void_p, _P(JpegHeader), C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_uint]),
     "uhdr_hip_jpeg_encode_scan": (ErrorInfo, [C.c_void_p, _P(JpegScan), C.c_void_p, _P(C.c_void_p), _P(C.c_uint), C.c_int, C.c_void_p, C.c_size_t,
                                               _P(C.c_size_t)]),
     "uhdr_hip_jpeg_encode_image": (ErrorInfo, [C.c_void_p, _P(JpegScan), C.c_void_p, _P(C.c_void_p), _P(C.c_uint), C.c_int, C.c_void_p, C.c_size_t,

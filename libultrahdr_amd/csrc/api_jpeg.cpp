@@ -934,38 +934,12 @@ uhdr_error_info_t uhdr_hip_jpeg_encode_image(uhdr_hip_ctx_t* c, const uhdr_hip_j
   return jpeg_encode_impl(c, scan, qtable, planes, strides, rgb_channels, out, out_capacity, out_bytes, true);
 }
 
-// JpegDecoderHelper::decompressImage (jpegdecoderhelper.cpp:169-535) for a baseline file whose headers are parsed: entropy
-// decode, dequantization, JDCT_ISLOW IDCT and (for RGB / RGBA output of a 4:4:4 file) ycc_rgb_convert on the device; only
-// the compressed bytes go up and only the decoded samples come down.
-static uhdr_error_info_t jpeg_decode_scan_impl(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data, size_t scan_bytes,
-                                               int out_channels, int variant, uint8_t* const planes[3], const unsigned int hstride[3],
-                                               const unsigned int vstride[3]);
-uhdr_error_info_t uhdr_hip_jpeg_decode_scan(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data, size_t scan_bytes,
-                                            int out_channels, int variant, uint8_t* const planes[3], const unsigned int hstride[3],
-                                            const unsigned int vstride[3]) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const uhdr_error_info_t r = jpeg_decode_scan_impl(c, hdr, scan_data, scan_bytes, out_channels, variant, planes, hstride, vstride);
-  if (c) c->stats.last_jpeg_decode_scan_ns = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-  return r;
-}
-static uhdr_error_info_t jpeg_decode_scan_impl(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data, size_t scan_bytes,
-                                               int out_channels, int variant, uint8_t* const planes[3], const unsigned int hstride[3],
-                                               const unsigned int vstride[3]) {
-  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
-  if (!hdr || !scan_data || !planes || !hstride || !vstride) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument for jpeg_decode_scan");
-  const DbgClock dbg;
-  if (out_channels != 0 && out_channels != 3 && out_channels != 4) return err_status(UHDR_CODEC_INVALID_PARAM, "out_channels is 0 (planes), 3 (RGB888) or 4 (RGBA8888), received %d", out_channels);
-  uhdr_hip_jpeg_scan_t sc = hdr->scan;
+// The compressed bytes of a parsed baseline file up to the device and through the entropy decoder (uhdr_hip_huffman_decode_dev):
+// sc's coefficient arrays (c->jpg[1..3]) hold the quantized blocks on return.  Shared by uhdr_hip_jpeg_decode_scan and
+// uhdr_hip_jpeg_decode_rgb.
+static uhdr_error_info_t jpeg_scan_to_coefficients(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data, size_t scan_bytes,
+                                                   const DbgClock& dbg, uhdr_hip_jpeg_scan_t& sc) {
   const int nc = sc.num_components;
-  int mpr = 0, mrows = 0, bpm = 0;
-  UHDR_TRY(check_scan(&sc, false, &mpr, &mrows, &bpm));
-  if (out_channels != 0) {
-    if (nc != 3 || sc.h_samp[0] != 1 || sc.v_samp[0] != 1 || sc.h_samp[1] != 1 || sc.v_samp[1] != 1 || sc.h_samp[2] != 1 || sc.v_samp[2] != 1)
-      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "RGB output needs a 3-component 4:4:4 file (libjpeg's upsampling is outside the HIP path)");
-    if (memcmp(hdr->qtable[1], hdr->qtable[2], sizeof hdr->qtable[1]))
-      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "RGB output with different Cb and Cr quantization tables is outside the HIP path");
-    if (!planes[0] || hstride[0] < sc.w || vstride[0] < sc.h) return err_status(UHDR_CODEC_INVALID_PARAM, "destination smaller than the %ux%u image", sc.w, sc.h);
-  }
   // the entropy-coded data ends at the first marker that is neither a stuffed zero, a fill byte nor RSTn (T.81 B.1.1.2 / B.2.1)
   auto walk = [&]() -> size_t {
     size_t e = 0;
@@ -1017,6 +991,42 @@ static uhdr_error_info_t jpeg_decode_scan_impl(uhdr_hip_ctx_t* c, const uhdr_hip
   c->huff_serial_ok = true;
   if (hs.error_code != UHDR_CODEC_OK) return hs;
   dbg.mark("jpeg_decode_scan: entropy decode returned");
+  return ok_status();
+}
+
+// JpegDecoderHelper::decompressImage (jpegdecoderhelper.cpp:169-535) for a baseline file whose headers are parsed: entropy
+// decode, dequantization, JDCT_ISLOW IDCT and (for RGB / RGBA output of a 4:4:4 file) ycc_rgb_convert on the device; only
+// the compressed bytes go up and only the decoded samples come down.
+static uhdr_error_info_t jpeg_decode_scan_impl(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data, size_t scan_bytes,
+                                               int out_channels, int variant, uint8_t* const planes[3], const unsigned int hstride[3],
+                                               const unsigned int vstride[3]);
+uhdr_error_info_t uhdr_hip_jpeg_decode_scan(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data, size_t scan_bytes,
+                                            int out_channels, int variant, uint8_t* const planes[3], const unsigned int hstride[3],
+                                            const unsigned int vstride[3]) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const uhdr_error_info_t r = jpeg_decode_scan_impl(c, hdr, scan_data, scan_bytes, out_channels, variant, planes, hstride, vstride);
+  if (c) c->stats.last_jpeg_decode_scan_ns = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+  return r;
+}
+static uhdr_error_info_t jpeg_decode_scan_impl(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data, size_t scan_bytes,
+                                               int out_channels, int variant, uint8_t* const planes[3], const unsigned int hstride[3],
+                                               const unsigned int vstride[3]) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  if (!hdr || !scan_data || !planes || !hstride || !vstride) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument for jpeg_decode_scan");
+  const DbgClock dbg;
+  if (out_channels != 0 && out_channels != 3 && out_channels != 4) return err_status(UHDR_CODEC_INVALID_PARAM, "out_channels is 0 (planes), 3 (RGB888) or 4 (RGBA8888), received %d", out_channels);
+  uhdr_hip_jpeg_scan_t sc = hdr->scan;
+  const int nc = sc.num_components;
+  int mpr = 0, mrows = 0, bpm = 0;
+  UHDR_TRY(check_scan(&sc, false, &mpr, &mrows, &bpm));
+  if (out_channels != 0) {
+    if (nc != 3 || sc.h_samp[0] != 1 || sc.v_samp[0] != 1 || sc.h_samp[1] != 1 || sc.v_samp[1] != 1 || sc.h_samp[2] != 1 || sc.v_samp[2] != 1)
+      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "RGB output needs a 3-component 4:4:4 file (libjpeg's upsampling is outside the HIP path)");
+    if (memcmp(hdr->qtable[1], hdr->qtable[2], sizeof hdr->qtable[1]))
+      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "RGB output with different Cb and Cr quantization tables is outside the HIP path");
+    if (!planes[0] || hstride[0] < sc.w || vstride[0] < sc.h) return err_status(UHDR_CODEC_INVALID_PARAM, "destination smaller than the %ux%u image", sc.w, sc.h);
+  }
+  UHDR_TRY(jpeg_scan_to_coefficients(c, hdr, scan_data, scan_bytes, dbg, sc));
   uhdr_hip_ctx::Resident* res = c->resident_on ? &c->resident[c->resident_next++ % 2] : nullptr;
   DeviceBuf* out_buf = res ? &res->buf : &c->jpg[4];
   if (res) {
@@ -1094,6 +1104,107 @@ static uhdr_error_info_t jpeg_decode_scan_impl(uhdr_hip_ctx_t* c, const uhdr_hip
   if (!lazy) HIP_TRY(hipStreamSynchronize(c->stream));
   dbg.mark("jpeg_decode_scan: done");
   return ok_status();
+}
+
+// ---- 4:2:0 -> RGB: libjpeg's chroma reconstruction on the device (jpeg_upsample.hip) ------------------------------------
+static bool is_420(const uhdr_hip_jpeg_scan_t& sc) {
+  return sc.num_components == 3 && sc.h_samp[0] == 2 && sc.v_samp[0] == 2 && sc.h_samp[1] == 1 && sc.v_samp[1] == 1 && sc.h_samp[2] == 1 &&
+         sc.v_samp[2] == 1;
+}
+
+// grids: the arrays' block grids (libjpeg's width_in_blocks, or larger up to the MCU-padded grid); rgb: device image, w x h
+static uhdr_error_info_t idct_upsample_rgb_impl(uhdr_hip_ctx_t* c, const int16_t* const coef[3], const int bw[3], const int bh[3],
+                                                const uint16_t* const qt[3], int variant, uhdr_raw_image_t* rgb) {
+  if (bw[1] != bw[2] || bh[1] != bh[2]) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "Cb and Cr block grids differ");
+  for (int k = 0; k < 3; k++)
+    for (int i = 0; i < 64; i++)
+      if (qt[k][i] == 0) return err_status(UHDR_CODEC_INVALID_PARAM, "quantization table %d entry %d is zero", k, i);
+  uint8_t* scratch = nullptr;
+  if (variant == 0) {
+    UHDR_TRY(ensure(c->jpg[5], upsample420_scratch_bytes(bw, bh)));
+    scratch = (uint8_t*)c->jpg[5].p;
+  }
+  rgb->range = UHDR_CR_FULL_RANGE;
+  ProfScope ps(c, "idct_upsample_rgb");
+  HIP_TRY(launch_idct_upsample_rgb(coef, bw, bh, qt, variant, view_mut_of(rgb), scratch, c->stream));
+  return ok_status();
+}
+
+// JpegDecoderHelper::decompressImage's DECODE_TO_RGB_CS branch (jpegdecoderhelper.cpp:349-375, decodeToCSRGB :456-478) after the
+// entropy decode, for a 4:2:0 file: dequant + islow IDCT of luma, libjpeg's chroma reconstruction, ycc_rgb_convert.
+uhdr_error_info_t uhdr_hip_idct_upsample_rgb_dev(uhdr_hip_ctx_t* c, const int16_t* coef_y, const int16_t* coef_cb, const int16_t* coef_cr,
+                                                 unsigned int w, unsigned int h, const uint16_t qt_y[64], const uint16_t qt_cb[64],
+                                                 const uint16_t qt_cr[64], int variant, uhdr_raw_image_t* rgb) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  if (!coef_y || !coef_cb || !coef_cr || !qt_y || !qt_cb || !qt_cr || !rgb || !rgb->planes[0])
+    return err_status(UHDR_CODEC_INVALID_PARAM, "received bad argument for idct_upsample_rgb");
+  if (rgb->fmt != UHDR_IMG_FMT_24bppRGB888 && rgb->fmt != UHDR_IMG_FMT_32bppRGBA8888)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "idct_upsample_rgb expects UHDR_IMG_FMT_24bppRGB888 or UHDR_IMG_FMT_32bppRGBA8888. Received %d", rgb->fmt);
+  if (variant != 0 && variant != 1) return err_status(UHDR_CODEC_INVALID_PARAM, "unknown libjpeg variant %d", variant);
+  if (w == 0 || h == 0 || w > 65535 || h > 65535) return err_status(UHDR_CODEC_INVALID_PARAM, "image dimensions %ux%u are outside JPEG's 1..65535", w, h);
+  if (rgb->w != w || rgb->h != h) return err_status(UHDR_CODEC_INVALID_PARAM, "destination is %ux%u, the image %ux%u", rgb->w, rgb->h, w, h);
+  if (rgb->stride[0] < w) return err_status(UHDR_CODEC_INVALID_PARAM, "stride (%u) cannot be less than width (%u)", rgb->stride[0], w);
+  if (((uintptr_t)coef_y | (uintptr_t)coef_cb | (uintptr_t)coef_cr) & 15)
+    return err_status(UHDR_CODEC_INVALID_PARAM, "coefficient buffers must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  const int16_t* coef[3] = {coef_y, coef_cb, coef_cr};
+  const int bw[3] = {(int)((w + 7) / 8), (int)((w + 15) / 16), (int)((w + 15) / 16)};
+  const int bh[3] = {(int)((h + 7) / 8), (int)((h + 15) / 16), (int)((h + 15) / 16)};
+  const uint16_t* qt[3] = {qt_y, qt_cb, qt_cr};
+  return idct_upsample_rgb_impl(c, coef, bw, bh, qt, variant, rgb);
+}
+
+// JpegDecoderHelper::decompressImage(DECODE_TO_RGB_CS) (jpegdecoderhelper.cpp:169-535) for a whole baseline file: what uhdr_decode
+// runs for UHDR_CT_SRGB / RGBA8888 output (jpegr.cpp:1479-1525).  4:4:4 goes through uhdr_hip_jpeg_decode_scan's fused path.
+static uhdr_error_info_t jpeg_decode_rgb_impl(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data, size_t scan_bytes,
+                                              int out_channels, int variant, uint8_t* rgb, unsigned int stride_px) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  if (!hdr || !scan_data || !rgb) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument for jpeg_decode_rgb");
+  if (out_channels != 3 && out_channels != 4) return err_status(UHDR_CODEC_INVALID_PARAM, "out_channels is 3 (RGB888) or 4 (RGBA8888), received %d", out_channels);
+  if (variant != 0 && variant != 1) return err_status(UHDR_CODEC_INVALID_PARAM, "unknown libjpeg variant %d", variant);
+  uhdr_hip_jpeg_scan_t sc = hdr->scan;
+  int mpr = 0, mrows = 0, bpm = 0;
+  UHDR_TRY(check_scan(&sc, false, &mpr, &mrows, &bpm));
+  if (stride_px < sc.w) return err_status(UHDR_CODEC_INVALID_PARAM, "stride (%u) cannot be less than width (%u)", stride_px, sc.w);
+  const bool s444 = sc.num_components == 3 && sc.h_samp[0] == 1 && sc.v_samp[0] == 1 && sc.h_samp[1] == 1 && sc.v_samp[1] == 1 &&
+                    sc.h_samp[2] == 1 && sc.v_samp[2] == 1;
+  if (s444) {
+    uint8_t* planes[3] = {rgb, nullptr, nullptr};
+    const unsigned int hs[3] = {stride_px, 0, 0}, vs[3] = {sc.h, 0, 0};
+    return jpeg_decode_scan_impl(c, hdr, scan_data, scan_bytes, out_channels, variant, planes, hs, vs);
+  }
+  if (!is_420(sc))
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "RGB output on the device takes 4:2:0 or 4:4:4 files; received %d components at %dx%d / %dx%d / %dx%d",
+                      sc.num_components, sc.h_samp[0], sc.v_samp[0], sc.h_samp[1], sc.v_samp[1], sc.h_samp[2], sc.v_samp[2]);
+  if (sc.blocks_w[1] != sc.blocks_w[2] || sc.blocks_h[1] != sc.blocks_h[2]) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "Cb and Cr block grids differ");
+  const DbgClock dbg;
+  UHDR_TRY(jpeg_scan_to_coefficients(c, hdr, scan_data, scan_bytes, dbg, sc));
+  // the image is written to the caller's buffer, so any device copy the resident handoff keeps of that buffer is stale
+  resident_drop(c, rgb);
+  uhdr_raw_image_t img;
+  memset(&img, 0, sizeof img);
+  img.fmt = out_channels == 3 ? UHDR_IMG_FMT_24bppRGB888 : UHDR_IMG_FMT_32bppRGBA8888;
+  img.w = sc.w;
+  img.h = sc.h;
+  const size_t pitch_px = ((size_t)sc.w + 63) & ~(size_t)63;
+  UHDR_TRY(ensure(c->jpg[4], pitch_px * (size_t)out_channels * sc.h));
+  img.planes[0] = c->jpg[4].p;
+  img.stride[0] = (unsigned int)pitch_px;
+  const uint16_t* qt[3] = {hdr->qtable[0], hdr->qtable[1], hdr->qtable[2]};
+  UHDR_TRY(idct_upsample_rgb_impl(c, sc.coef, sc.blocks_w, sc.blocks_h, qt, variant, &img));
+  HIP_TRY(hipMemcpy2DAsync(rgb, (size_t)stride_px * out_channels, c->jpg[4].p, pitch_px * out_channels, (size_t)sc.w * out_channels, sc.h,
+                           hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  dbg.mark("jpeg_decode_rgb: done");
+  return ok_status();
+}
+
+uhdr_error_info_t uhdr_hip_jpeg_decode_rgb(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data, size_t scan_bytes,
+                                           int out_channels, int variant, uint8_t* rgb, unsigned int stride_px) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const uhdr_error_info_t r = jpeg_decode_rgb_impl(c, hdr, scan_data, scan_bytes, out_channels, variant, rgb, stride_px);
+  if (c) c->stats.last_jpeg_decode_rgb_ns = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+  return r;
 }
 
 // JpegR::decodeJPEGR behind its container parsing (jpegr.cpp:1469-1531) on DEVICE-resident data in ONE entry point (round 6): the two

@@ -1,0 +1,215 @@
+"""The 4:2:0 -> RGB decode on the device (uhdr_hip_idct_upsample_rgb_dev, jpeg_upsample.hip) at 4K and 8K, next to the 4:4:4
+idct_dequant_rgb_kernel, the whole-file entry (uhdr_hip_jpeg_decode_rgb), and uhdr_decode to SRGB / RGBA8888 through the
+drop-in libuhdr.so with and without GPU acceleration.
+
+    python tools/srgb_decode_time.py [--iters 50] [--json out.json]        per-call times (see below) + the facade decode
+    python tools/srgb_decode_time.py --kernel-trace DIR                     kernel times: one rocprofv3 --kernel-trace child
+                                                                            process per size, durations read from its database
+
+Per-call times are torch events around a loop of Python calls of the entry (ctypes tables, the stream handshake and, for
+variant 0, the two chroma IDCT launches included): a bound on what a caller pays, not a kernel time.  Kernel times come from
+the trace; the fraction of 8 TB/s is taken on algorithmic bytes: 3 B/px of int16 coefficients in (1.5 samples per pixel) +
+4 (3) B/px out for 4:2:0, 6 B/px in for 4:4:4.  Variant 0's kernel time is the upsampling kernel plus its two chroma
+idct_dequant_kernel launches (1 B/px more through HBM, not counted as algorithmic).
+"""
+import argparse
+import io
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PEAK = 8.0e12
+
+
+def _time(fn, iters):
+    import torch
+
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e-3
+
+
+SIZES = {"4K": (3840, 2160), "8K": (7680, 4320)}
+
+
+def _inputs(w, h, rng):
+    import torch
+
+    from oracle import loader as L
+
+    grids = [((h + 7) // 8, (w + 7) // 8), ((h + 15) // 16, (w + 15) // 16), ((h + 15) // 16, (w + 15) // 16)]
+    coefs = []
+    for bh, bw in grids:
+        c = rng.integers(-3, 4, (bh, bw, 64)).astype(np.int16)
+        c[..., 0] = rng.integers(-60, 61, (bh, bw))
+        coefs.append(torch.from_numpy(c).to("cuda:0"))
+    c444 = [torch.from_numpy(rng.integers(-3, 4, (grids[0][0], grids[0][1], 64)).astype(np.int16)).to("cuda:0") for _ in range(3)]
+    qts = [L.quant_table_port(90, False), L.quant_table_port(90, True), L.quant_table_port(90, True)]
+    return coefs, c444, qts
+
+
+def _per_call(u, sizes, iters, rng):
+    from libultrahdr_amd import capi as A
+    from libultrahdr_amd.images import Image
+
+    rows = []
+    for name in sizes:
+        w, h = SIZES[name]
+        coefs, c444, qts = _inputs(w, h, rng)
+        for ch, fmt in ((4, A.UHDR_IMG_FMT_32bppRGBA8888), (3, A.UHDR_IMG_FMT_24bppRGB888)):
+            dst = Image(fmt, w, h, align=64, device="cuda:0")
+            for variant in (0, 1):
+                t = _time(lambda: u.idct_upsample_rgb(coefs, qts, w, h, fmt, variant, dst=dst), iters)
+                rows.append(dict(entry=f"uhdr_hip_idct_upsample_rgb_dev v{variant}", size=name, channels=ch, per_call_us=t * 1e6))
+            t = _time(lambda: u.idct_dequant_rgb(c444, qts[0], qts[1], w, h, fmt, 0, dst=dst), iters)
+            rows.append(dict(entry="uhdr_hip_idct_dequant_rgb_dev (4:4:4)", size=name, channels=ch, per_call_us=t * 1e6))
+    return rows
+
+
+def _whole_file_and_facade(u, rng):
+    """4K: the whole-file entry against Pillow's libjpeg-turbo on the host, and uhdr_decode to SRGB / RGBA8888 through the
+    facade with and without GPU acceleration (the facade links IJG 9: its CPU route is that libjpeg)."""
+    from libultrahdr_amd import capi as A
+    from libultrahdr_amd import facade as FA
+    from libultrahdr_amd import synth
+
+    rows = []
+    w, h = SIZES["4K"]
+    try:
+        from PIL import Image as PImage
+
+        yy, xx = np.mgrid[0:h, 0:w]
+        a = np.stack([(xx * 255 // w), (yy * 255 // h), ((xx + yy) * 97 % 256)], -1).astype(np.uint8)
+        a = np.clip(a.astype(np.int32) + rng.integers(-12, 13, a.shape), 0, 255).astype(np.uint8)
+        buf = io.BytesIO()
+        PImage.fromarray(a, "RGB").save(buf, format="JPEG", quality=95, subsampling=2)
+        jpeg = buf.getvalue()
+        out = np.empty((h, w, 4), np.uint8)
+        for _ in range(3):
+            u.jpeg_decode_rgb(jpeg, 4, 0, out=out)
+        n = 20
+        t0 = time.perf_counter()
+        for _ in range(n):
+            u.jpeg_decode_rgb(jpeg, 4, 0, out=out)
+        t_gpu = (time.perf_counter() - t0) / n
+        t0 = time.perf_counter()
+        for _ in range(n):
+            cpu = np.asarray(PImage.open(io.BytesIO(jpeg)).convert("RGBA"))
+        t_cpu = (time.perf_counter() - t0) / n
+        rows.append(dict(entry="uhdr_hip_jpeg_decode_rgb (variant 0) vs Pillow's libjpeg-turbo on the host, one 4:2:0 file", size="4K",
+                         gpu_ms=t_gpu * 1e3, pillow_ms=t_cpu * 1e3, bytes=len(jpeg), identical=bool(np.array_equal(out, cpu))))
+    except ImportError:
+        pass
+    if os.path.isfile(FA.PATH):
+        sdr = synth.make_sdr_yuv420(w, h)
+        hdr = synth.make_hdr_p010(w, h, ct=A.UHDR_CT_HLG)
+        jpegr = FA.encode(hdr, sdr, gpu=True)
+        res = {}
+        for gpu in (False, True):
+            ts = []
+            for _ in range(6):
+                px = FA.decode(jpegr, A.UHDR_CT_SRGB, A.UHDR_IMG_FMT_32bppRGBA8888, gpu=gpu)
+                ts.append(FA.last_call_seconds)
+            res[gpu] = (float(np.median(ts[1:])), px)
+        st = A.seam_stats()
+        rows.append(dict(entry="facade uhdr_decode -> SRGB / RGBA8888 (API-1 JpegR, median of 5 after one warm-up)", size="4K",
+                         gpu_ms=res[True][0] * 1e3, cpu_ms=res[False][0] * 1e3, identical=bool(np.array_equal(res[True][1], res[False][1])),
+                         device_route_calls=st.get("jpeg_decode_rgb", {}).get("device", 0)))
+    return rows
+
+
+def _kernel_trace(outdir, iters):
+    """One rocprofv3 --kernel-trace child per size (this script with --launch-only); kernel durations from its database."""
+    import glob
+    import sqlite3
+    import subprocess
+
+    rows = []
+    for name in SIZES:
+        w, h = SIZES[name]
+        d = os.path.join(outdir, name)
+        cmd = ["rocprofv3", "--kernel-trace", "-d", d, "-o", "k", "--", sys.executable, os.path.abspath(__file__), "--launch-only", name,
+               "--iters", str(iters)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+        if p.returncode != 0:
+            raise SystemExit(f"rocprofv3 run for {name} ended with {p.returncode}:\n{p.stderr[-2000:]}")
+        db = glob.glob(os.path.join(d, "**", "*.db"), recursive=True)
+        con = sqlite3.connect(db[0])
+        tabs = [r[0] for r in con.execute("select name from sqlite_master where type='table'")]
+        kd = [t for t in tabs if t.startswith("rocpd_kernel_dispatch")][0]
+        ks = [t for t in tabs if t.startswith("rocpd_info_kernel_symbol")][0]
+        avg = {n: (a, c) for n, c, a in con.execute(
+            f"select s.kernel_name, count(*), avg(d.end - d.start) from {kd} d join {ks} s on d.kernel_id = s.id group by s.kernel_name")}
+        con.close()
+
+        def find(name, *targs):
+            """(avg ns, launches) of the kernel `name` with these template arguments; the symbol table may hold demangled or
+            mangled names (<4, 0> / ILi4ELi0EE)."""
+            dem = "<" + ", ".join(str(t) for t in targs) + ">" if targs else ""
+            man = "I" + "".join(f"Li{t}E" for t in targs) + "E" if targs else ""
+            hits = [(a, c) for n, (a, c) in avg.items() if name in n and (not targs or dem in n or man in n)]
+            return hits[0] if hits else (None, 0)
+
+        chroma_idct, n_chroma = find("idct_dequant_kernel")
+        for ch in (4, 3):
+            for variant in (0, 1):
+                k, calls = find("idct_upsample_rgb_kernel", ch, variant)
+                if k is None:
+                    continue
+                ns = k + (2 * chroma_idct if variant == 0 and chroma_idct else 0)
+                by = (3 + ch) * w * h
+                rows.append(dict(kernel=f"idct_upsample_rgb_kernel<{ch},{variant}>" + (" + 2 x idct_dequant_kernel" if variant == 0 else ""),
+                                 size=name, channels=ch, launches=calls, kernel_us=ns / 1e3, alg_bytes_per_px=3 + ch, frac_8tbs=by / (ns * 1e-9) / PEAK))
+            k, calls = find("idct_dequant_rgb_kernel", ch)
+            if k is not None:
+                by = (6 + ch) * w * h
+                rows.append(dict(kernel=f"idct_dequant_rgb_kernel<{ch}> (4:4:4)", size=name, channels=ch, launches=calls, kernel_us=k / 1e3,
+                                 alg_bytes_per_px=6 + ch, frac_8tbs=by / (k * 1e-9) / PEAK))
+        if not any(r["size"] == name for r in rows):
+            raise SystemExit(f"no decode kernels found in the {name} trace; kernels seen: {sorted(avg)}")
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--kernel-trace", default=None, metavar="DIR")
+    ap.add_argument("--launch-only", default=None, choices=sorted(SIZES))
+    args = ap.parse_args()
+    if args.kernel_trace:
+        rows = _kernel_trace(args.kernel_trace, args.iters)
+    else:
+        from libultrahdr_amd.ultrahdr import Context, UltraHdr
+
+        ctx = Context(0)
+        u = UltraHdr(ctx=ctx)
+        rng = np.random.default_rng(1)
+        if args.launch_only:
+            _per_call(u, [args.launch_only], args.iters, rng)
+            ctx.close()
+            return
+        rows = _per_call(u, list(SIZES), args.iters, rng) + _whole_file_and_facade(u, rng)
+        ctx.close()
+    for r in rows:
+        print(json.dumps(r))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
