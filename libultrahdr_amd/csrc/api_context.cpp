@@ -606,6 +606,13 @@ uhdr_hip_ctx_t* uhdr_hip_create(int device, uhdr_error_info_t* err) {
   if (e != hipSuccess) return fail("hipSetDevice", e);
   uhdr_hip_ctx* c = new uhdr_hip_ctx();
   c->device = device;
+  {  // read here and nowhere else: a non-zero UHDR_HIP_HUFF_TWO_PASS keeps the two-pass marker-less encoder, a non-zero
+     // UHDR_HIP_HUFF_ROUTE_LOG names the route of every marker-less encode on stderr (tests)
+    const char* e = getenv("UHDR_HIP_HUFF_TWO_PASS");
+    c->huff_two_pass = e && atoi(e) != 0;
+    e = getenv("UHDR_HIP_HUFF_ROUTE_LOG");
+    c->huff_route_log = e && atoi(e) != 0;
+  }
   e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
   if (e != hipSuccess) { delete c; return fail("hipStreamCreate", e); }
   c->stream = c->own_stream;
@@ -635,6 +642,7 @@ void uhdr_hip_destroy(uhdr_hip_ctx_t* c) {
   for (auto& b : c->scratch) if (b.p) (void)hipFree(b.p);
   for (auto& b : c->jpg) if (b.p) (void)hipFree(b.p);
   for (auto& b : c->enc) if (b.p) (void)hipFree(b.p);
+  if (c->huff_slots.p) (void)hipFree(c->huff_slots.p);
   for (auto& r : c->resident) if (r.buf.p) (void)hipFree(r.buf.p);
   if (c->pending.buf.p) (void)hipFree(c->pending.buf.p);
   if (c->pending.tmp.p) (void)hipFree(c->pending.tmp.p);
@@ -674,11 +682,13 @@ int uhdr_hip_recycle(uhdr_hip_ctx_t* c, size_t keep_bytes) {
   for (auto& h : c->huff_hint) h = uhdr_hip_ctx::HuffHint();
   c->stats = uhdr_hip_stats_t();
   c->deferred_md.valid = false;
+  c->huff_slots_refused = 0;  // (memory is about to be given back: the slots may fit again)
   // the retained buffers, largest first, until the rest fits keep_bytes
   std::vector<DeviceBuf*> bufs;
   for (auto& b : c->scratch) bufs.push_back(&b);
   for (auto& b : c->jpg) bufs.push_back(&b);
   for (auto& b : c->enc) bufs.push_back(&b);
+  bufs.push_back(&c->huff_slots);
   for (auto& r : c->resident) bufs.push_back(&r.buf);
   bufs.push_back(&c->pending.buf);
   bufs.push_back(&c->pending.tmp);

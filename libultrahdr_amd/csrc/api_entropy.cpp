@@ -103,6 +103,8 @@ uhdr_error_info_t uhdr_hip_huffman_encode_dev(uhdr_hip_ctx_t* c, const uhdr_hip_
   if (stream) {
     // scratch[4]: the unstuffed stream (as many bytes as the caller's buffer holds: stuffing only adds bytes);
     // scratch[5]: segment starts (nseg + 1) | stuffed size | meta (4 words) | segment bit counts | chunk counts
+    // huff_slots: one small-class bit buffer per segment (half the scan's coefficient bytes; only the used words are ever touched).
+    // Without it -- UHDR_HIP_HUFF_TWO_PASS when the context was created, or no memory for it -- the two-pass route codes the scan.
     if (out_capacity > 0xFFFFFFF0u) out_capacity = 0xFFFFFFF0u;
     HuffStream t;
     memset(&t, 0, sizeof t);
@@ -118,6 +120,20 @@ uhdr_error_info_t uhdr_hip_huffman_encode_dev(uhdr_hip_ctx_t* c, const uhdr_hip_
     t.meta = (uint32_t*)(d_total + 1);
     t.seg_bits = t.meta + 4;
     uint32_t* chunk_counts = t.seg_bits + a.nseg;
+    if (!c->huff_two_pass) {
+      const size_t need = huff_stream_slot_bytes(a.nseg);
+      // a refused allocation is remembered: a context under memory pressure stays on the two-pass route without a failing hipMalloc per call
+      if (c->huff_slots.cap >= need || !c->huff_slots_refused || need < c->huff_slots_refused) {
+        if (ensure(c->huff_slots, need).error_code == UHDR_CODEC_OK) {
+          t.slots = (uint32_t*)c->huff_slots.p;
+        } else {
+          (void)hipGetLastError();  // (the failed allocation must not surface as the launch's error)
+          c->huff_slots_refused = need;
+          fprintf(stderr, "uhdr_hip: no device memory for %zu bytes of Huffman segment slots: marker-less scans of that size take the two-pass route\n", need);
+        }
+      }
+    }
+    if (c->huff_route_log) fprintf(stderr, "uhdr_hip: huffman_encode stream route=%s nseg=%d\n", t.slots ? "one_walk" : "two_pass", a.nseg);
     {
       ProfScope ps(c, "huffman_encode");
       HIP_TRY(launch_huffman_encode_stream(a, t, chunk_counts, d_total, out, (uint64_t)out_capacity, c->stream));
@@ -807,6 +823,8 @@ uhdr_error_info_t uhdr_api::aux_context(uhdr_hip_ctx* c, uhdr_hip_ctx** out) {
   }
   c->aux->prof = c->prof;
   c->aux->huff_serial_ok = c->huff_serial_ok;
+  c->aux->huff_route_log = c->huff_route_log;
+  c->aux->huff_two_pass = c->huff_two_pass;  // (the route of the context the caller created, whenever the auxiliary one came to be)
   *out = c->aux;
   return ok_status();
 }

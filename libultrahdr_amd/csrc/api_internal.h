@@ -114,6 +114,12 @@ struct uhdr_hip_ctx {
   DeviceBuf scratch[8];
   uhdr_hip_stats_t stats = {};    // uhdr_hip_get_stats: which route the entropy stage took, call by call
   bool huff_serial_ok = true;  // uhdr_hip_jpeg_decode_scan clears it: a large marker-less scan that the parallel decoder cannot settle goes back to the caller
+  // marker-less Huffman encoder: the per-segment bit slots of the one-walk route (huffman_encode.hip), and the switch that keeps the
+  // two-pass route instead (UHDR_HIP_HUFF_TWO_PASS, read once when the context is created; the auxiliary context reads it the same way)
+  DeviceBuf huff_slots;
+  bool huff_two_pass = false;
+  bool huff_route_log = false;        // UHDR_HIP_HUFF_ROUTE_LOG (read with the switch): one stderr line per marker-less encode
+  size_t huff_slots_refused = 0;      // the smallest slot size the device had no memory for: not asked for again (0: never refused)
   DeviceBuf enc[3];  // uhdr_hip_encode_api1_scans: the six coefficient arrays | base scan | map scan
   // round 5: a second context on the same device (own stream, scratch, table cache), created on first use by the entry points that
   // code the TWO scans of an UltraHDR file concurrently (uhdr_hip_huffman_encode2_dev / _decode2_dev): the entropy stages are

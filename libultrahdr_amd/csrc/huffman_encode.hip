@@ -326,20 +326,28 @@ __global__ __launch_bounds__(256) void huff_gather_kernel(const uint8_t* __restr
 // coefficients are already in memory, the bit position of a block is a prefix sum of code lengths, and byte stuffing is a
 // prefix sum of 0xFF counts.  The scan is cut into SEGMENTS of `ri` MCUs (not restart intervals: no marker, no alignment,
 // no predictor reset), one wavefront each:
-//   pass A  lengths: the wave walks its blocks once and stores the segment's bit count; lanes [0, blocks_per_mcu) hold the
-//           MCU in FRONT of the segment (DC values only) so that the first MCU's predictors, libjpeg's dummy-block rule
-//           included, come out of the same LDS exchange as all the others
+//   walk    (huff_stream_walk_kernel: four segments per workgroup sharing the code tables) the wave stages its blocks once, walks them for the code lengths (a wave prefix sum gives every lane its bit offset
+//           inside the segment), stores the segment's bit count and walks them again to emit the bits at phase 0 into its LDS
+//           buffer; the used words go to the segment's SLOT in scratch (kSegBlocks * kWordsSmall words).  Lanes
+//           [0, blocks_per_mcu) hold the MCU in FRONT of the segment (DC values only) so that the first MCU's predictors,
+//           libjpeg's dummy-block rule included, come out of the same lane exchange as all the others.  A segment whose bits do
+//           not fit the small buffer writes no slot: its bit count alone marks it
 //   scan    exclusive scan of the segment bit counts (one workgroup) -> every segment's first bit in the stream; the words
-//           that two segments share are zeroed
-//   pass B  emit: same walk, bits go to the LDS buffer at phase (first bit & 31) and from there to the unstuffed stream in
+//           that two segments share are zeroed; the segments of the large size class are counted
+//   place   one wave per segment reads the slot, shifts it to phase (first bit & 31) and stores it to the unstuffed stream in
 //           memory: interior words are plain stores, the first / last word of a segment is OR-ed in (its neighbour writes the
-//           rest); the last segment appends flush_bits' one-padding
+//           rest); the last segment appends flush_bits' one-padding (the scan's last bit is only known after the scan)
+//   large   the rare segments of the large size class are coded again from their coefficients with the known first bit and the
+//           worst-case LDS buffer (leaves at once when the scan counted none)
 //   stuff   0xFF counts per 4 KiB chunk -> scan -> scatter with the stuffed zero bytes (jchuff.c emit_bits)
+// The two-pass route this replaced stays selectable (HuffStream::slots == nullptr; UHDR_HIP_HUFF_TWO_PASS, or no room for the
+// slots): a lengths-only walk, the scan, then an emit walk per size class that reads the coefficients a second time and writes
+// the stream itself -- three walks and two coefficient reads per scan where the slots need two walks and one read.
 // The result equals libjpeg's entropy-coded segment byte for byte (tests: against the sequential CPU restatement of jchuff.c
 // at restart_interval 0 and against the files the reference encoder writes).
 constexpr int kStuffChunk = 4096;  // raw bytes per workgroup of the stuffing passes (256 threads x 16 bytes)
 
-template <int WORDS, int PASS>  // PASS 0: lengths; 1: emit, small LDS buffer; 2: emit, worst-case buffer
+template <int WORDS, int PASS>  // PASS 0: lengths (two-pass route); 1: emit, small LDS buffer (two-pass route); 2: emit, worst-case buffer (both routes)
 __global__ __launch_bounds__(64) void huff_stream_kernel(const HuffArgs a, const HuffStream t) {
   __shared__ __attribute__((aligned(16))) uint32_t s_tab[2 * (16 + 256)];
   __shared__ uint32_t s_coef[kSegBlocks * kCoefRow];
@@ -458,6 +466,142 @@ __global__ __launch_bounds__(64) void huff_stream_kernel(const HuffArgs a, const
         else t.raw[w0 + i] = v;
       }
     }
+  }
+}
+
+// The one-walk route's walking kernel: kWalkSegs segments per workgroup, one wave each.  The waves share one copy of the code tables
+// and nothing else: a wave's staged coefficients and its bit buffer are its own, so inside the segment loop a wave only orders its own
+// LDS traffic (wave_sync: the LDS serves a wave's instructions in order) and no workgroup barrier couples the four.  The DC values are
+// exchanged by lane shuffles and the real-block flags as a ballot mask.  52 416 B of LDS per workgroup: three workgroups, twelve waves
+// per CU (a one-wave workgroup with its own tables and LDS exchange arrays held 15 312 B: ten).
+// A segment is emitted at bit 0 of its buffer (there is no first bit yet: the scan runs behind this kernel); the used words go to the
+// segment's slot.  A segment beyond the small class, or with coefficients outside the baseline range, stores its count / kBadCoef only.
+constexpr int kWalkSegs = 4;
+constexpr int kSlotWords = kSegBlocks * kWordsSmall;
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+__global__ __launch_bounds__(64 * kWalkSegs) void huff_stream_walk_kernel(const HuffArgs a, const HuffStream t) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_tab[2 * (16 + 256)];
+  __shared__ uint32_t s_coef_all[kWalkSegs][kSegBlocks * kCoefRow];
+  __shared__ uint32_t s_bits_all[kWalkSegs][kSlotWords];
+  __shared__ uint8_t s_zz[64];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  copy_words_to_lds<4>(s_tab, a.tables, 2 * (16 + 256), threadIdx.x, 64 * kWalkSegs);
+  if (threadIdx.x < 64) s_zz[threadIdx.x] = a.zigzag[threadIdx.x];
+  __syncthreads();  // (the only workgroup barrier)
+  uint32_t* s_coef = s_coef_all[wv];
+  uint32_t* s_bits = s_bits_all[wv];
+  const int bpm = a.blocks_per_mcu;
+  // the lane's place inside the wave does not depend on the segment
+  const int mcu_local = (int)lane / bpm, k_in_mcu = (int)lane - mcu_local * bpm;  // MCU 0 of the wave = the one before the segment
+  int c = 0, kk = k_in_mcu;
+  if (a.ncomp > 1) {
+    while (c < a.ncomp - 1 && kk >= a.hs[c] * a.vs[c]) { kk -= a.hs[c] * a.vs[c]; c++; }
+  }
+  const int hs = a.ncomp > 1 ? a.hs[c] : 1, vs = a.ncomp > 1 ? a.vs[c] : 1;
+  const int yi = kk / hs, xi = kk - yi * hs;
+  // the lane whose DC value predicts this one: the previous block of the component, in this MCU or the one before (emitting lanes: >= 0)
+  const int pred_lane = (kk > 0 ? (int)lane - 1 : (int)lane - bpm + hs * vs - 1) & 63;
+  const uint32_t* dct = s_tab + (c ? (16 + 256) : 0);
+  const uint32_t* act = dct + 16;
+  const uint32_t zz_of_lane = s_zz[lane];
+  uint32_t* crow = s_coef + lane * kCoefRow;
+  for (int seg = (int)blockIdx.x * kWalkSegs + (int)wv; seg < a.nseg; seg += (int)gridDim.x * kWalkSegs) {
+    wave_sync();  // the previous segment's LDS contents are dead
+    const int mcu = seg * a.ri + mcu_local - 1;
+    const bool valid = mcu_local <= a.ri && mcu >= 0 && mcu < a.total_mcus;
+    const bool emits = valid && mcu_local >= 1;
+    const int mcu_c = valid ? mcu : 0;
+    const int my = mcu_c / a.mcus_per_row, mx = mcu_c - my * a.mcus_per_row;
+    const int by = my * vs + yi, bx = mx * hs + xi;
+    const bool real = valid && by < a.bh[c] && bx < a.bw[c];
+    int dc0 = 0;
+    if (real) {
+      const uint4* src = (const uint4*)(a.coef[c] + ((size_t)by * a.bw[c] + bx) * 64);
+      if (emits) {
+        uint4 q[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) q[i] = src[i];
+#pragma unroll
+        for (int i = 0; i < 8; i++) { crow[4 * i] = q[i].x; crow[4 * i + 1] = q[i].y; crow[4 * i + 2] = q[i].z; crow[4 * i + 3] = q[i].w; }
+        dc0 = (int)(int16_t)(q[0].x & 0xffffu);
+      } else {
+        dc0 = (int)(int16_t)(*(const uint32_t*)src & 0xffffu);  // the MCU in front of the segment: its DC values are all that matters
+      }
+    }
+    // dummy block (jctrans.c compress_output): DC of the previous block of the MCU.  Every lane takes part in every shuffle.
+    const uint64_t real_mask = __builtin_amdgcn_ballot_w64(real);
+    const int up1 = __shfl_up(dc0, 1, 64), up2 = __shfl_up(dc0, 2, 64), up3 = __shfl_up(dc0, 3, 64);
+    int dcv = dc0;
+    if (valid && !real) {
+      if (k_in_mcu >= 1 && ((real_mask >> (lane - 1)) & 1ull)) dcv = up1;
+      else if (k_in_mcu >= 2 && ((real_mask >> (lane - 2)) & 1ull)) dcv = up2;
+      else if (k_in_mcu >= 3 && ((real_mask >> (lane - 3)) & 1ull)) dcv = up3;
+    }
+    const int pred_v = __shfl(dcv, pred_lane, 64);  // (0 in front of MCU 0: those lanes are not valid)
+    const int diff = dcv - (emits ? pred_v : 0);
+    wave_sync();  // the staged rows are visible to the whole wave
+    const uint64_t nz = zigzag_nonzero_map(s_coef, zz_of_lane, lane);  // (only rows of emitting lanes with a real block are ever walked)
+    uint32_t len = 0, oob = 0;
+    if (emits) walk_block(dct, act, diff, real, crow, s_zz, nz, oob, [&](uint32_t, uint32_t n) { len += n; });
+    const uint32_t incl = wave_incl_scan(len, lane);
+    const uint32_t total_bits = (uint32_t)__shfl((int)incl, 63, 64);
+    const bool bad = __builtin_amdgcn_ballot_w64(oob != 0) != 0;
+    if (lane == 0) t.seg_bits[seg] = bad ? kBadCoef : total_bits;
+    if (bad || total_bits + 32u > (uint32_t)kSlotWords * 32u) continue;  // (wave-uniform) the large class / the error: no slot
+    const uint32_t nwords = (total_bits + 31u) >> 5;  // <= kSlotWords - 1
+    for (uint32_t i = lane; i < nwords + 1u; i += 64) s_bits[i] = 0u;
+    wave_sync();
+    if (emits) {
+      const uint32_t off = incl - len;
+      uint64_t acc = 0;
+      uint32_t cnt = off & 31u, w = off >> 5;
+      walk_block(dct, act, diff, real, crow, s_zz, nz, oob, [&](uint32_t code, uint32_t n) {
+        acc = (acc << n) | (uint64_t)code;
+        cnt += n;
+        if (cnt >= 32u) {
+          cnt -= 32u;
+          atomicOr(&s_bits[w++], (uint32_t)(acc >> cnt));
+        }
+      });
+      if (cnt) atomicOr(&s_bits[w], (uint32_t)(acc << (32u - cnt)));
+    }
+    wave_sync();
+    uint32_t* slot = t.slots + (size_t)seg * (size_t)kSlotWords;
+    for (uint32_t i = lane; i < nwords; i += 64) slot[i] = s_bits[i];
+  }
+}
+
+// The small-class segments' slots -> the unstuffed stream: four segments per workgroup, one wave each, no LDS.  Output word i of a
+// segment is slot words i - 1 and i funnel-shifted by the phase of the segment's first bit; the rest is the tail of the emit pass above.
+constexpr int kPlaceSegs = 4;
+__global__ __launch_bounds__(64 * kPlaceSegs) void huff_stream_place_kernel(int nseg, const HuffStream t) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const int seg = (int)blockIdx.x * kPlaceSegs + (int)(threadIdx.x >> 6);
+  if (seg >= nseg) return;
+  const uint32_t total_bits = t.seg_bits[seg];
+  if (total_bits >= kRetry || total_bits + 32u > (uint32_t)(kSegBlocks * kWordsSmall) * 32u) return;  // large class: the launch behind this one
+  const uint64_t start = t.seg_start[seg];
+  const uint32_t phase = (uint32_t)(start & 31u);
+  const uint32_t nin = (total_bits + 31u) >> 5, nwords = (phase + total_bits + 31u) >> 5;  // (nwords <= nin + 1)
+  const uint32_t e = phase + total_bits, tail = e & 31u;
+  const bool flush = seg == nseg - 1 && (e & 7u);  // flush_bits: one-fill the last partial byte of the scan
+  const uint32_t* slot = t.slots + (size_t)seg * (size_t)(kSegBlocks * kWordsSmall);
+  const uint64_t w0 = start >> 5;
+  for (uint32_t i = lane; i < nwords; i += 64) {
+    if (w0 + i >= t.raw_words) break;  // capacity: the host reports the size the stream needs
+    const uint32_t cur = i < nin ? slot[i] : 0u, prev = (i > 0 && phase != 0) ? slot[i - 1] : 0u;
+    uint32_t v = __builtin_amdgcn_alignbit(prev, cur, phase);  // (prev : cur) >> phase
+    if (flush && i == (e >> 5)) {
+      const uint32_t pad = 8u - (e & 7u);
+      v |= ((1u << pad) - 1u) << (32u - tail - pad);
+    }
+    v = __builtin_bswap32(v);  // bytes are MSB first
+    const bool shared = (i == 0 && phase != 0) || (i == nwords - 1 && tail != 0);
+    if (shared) atomicOr(&t.raw[w0 + i], v);
+    else t.raw[w0 + i] = v;
   }
 }
 
@@ -640,17 +784,26 @@ hipError_t launch_huffman_encode(const HuffArgs& a, uint64_t* offsets, uint32_t*
 
 // MCUs per wavefront segment of the marker-less encoder: the wave's first blocks_per_mcu lanes carry the MCU in front
 int huff_stream_segment_mcus(int blocks_per_mcu) { return kSegBlocks / blocks_per_mcu - 1; }
+size_t huff_stream_slot_bytes(int nseg) { return (size_t)nseg * (size_t)kSlotWords * sizeof(uint32_t); }
 int huff_stuff_chunks(uint64_t raw_bytes) { return (int)((raw_bytes + kStuffChunk - 1) / kStuffChunk); }
 
-// a.ri = huff_stream_segment_mcus(), a.nseg segments; t.raw holds t.raw_words words; chunk_counts: huff_stuff_chunks(raw capacity)
+// a.ri = huff_stream_segment_mcus(), a.nseg segments; t.slots: huff_stream_slot_bytes(a.nseg) of scratch, or nullptr for the two-pass
+// route; t.raw holds t.raw_words words; chunk_counts: huff_stuff_chunks(raw capacity)
 // words; out_bytes (device): stuffed size.  Everything is stream ordered; the host reads t.meta / out_bytes afterwards.
 hipError_t launch_huffman_encode_stream(const HuffArgs& a, const HuffStream& t, uint32_t* chunk_counts, uint64_t* out_bytes, uint8_t* out, uint64_t cap,
                                         hipStream_t s) {
   const int grid = a.nseg < 16384 ? a.nseg : 16384;
   const int nchunks = huff_stuff_chunks(t.raw_words * 4u);
-  hipLaunchKernelGGL((huff_stream_kernel<1, 0>), dim3(grid), dim3(64), 0, s, a, t);
-  hipLaunchKernelGGL(huff_stream_scan_kernel, dim3(1), dim3(kStreamScanThreads), 0, s, (const uint32_t*)t.seg_bits, a.nseg, t);
-  hipLaunchKernelGGL((huff_stream_kernel<kWordsSmall, 1>), dim3(grid), dim3(64), 0, s, a, t);
+  if (t.slots) {
+    const int wgrid = (grid + kWalkSegs - 1) / kWalkSegs;
+    hipLaunchKernelGGL(huff_stream_walk_kernel, dim3(wgrid), dim3(64 * kWalkSegs), 0, s, a, t);
+    hipLaunchKernelGGL(huff_stream_scan_kernel, dim3(1), dim3(kStreamScanThreads), 0, s, (const uint32_t*)t.seg_bits, a.nseg, t);
+    hipLaunchKernelGGL(huff_stream_place_kernel, dim3((a.nseg + kPlaceSegs - 1) / kPlaceSegs), dim3(64 * kPlaceSegs), 0, s, a.nseg, t);
+  } else {
+    hipLaunchKernelGGL((huff_stream_kernel<1, 0>), dim3(grid), dim3(64), 0, s, a, t);
+    hipLaunchKernelGGL(huff_stream_scan_kernel, dim3(1), dim3(kStreamScanThreads), 0, s, (const uint32_t*)t.seg_bits, a.nseg, t);
+    hipLaunchKernelGGL((huff_stream_kernel<kWordsSmall, 1>), dim3(grid), dim3(64), 0, s, a, t);
+  }
   hipLaunchKernelGGL((huff_stream_kernel<kWordsPerBlock, 2>), dim3(grid < 2048 ? grid : 2048), dim3(64), 0, s, a, t);
   hipLaunchKernelGGL(huff_stuff_count_kernel, dim3(nchunks), dim3(256), 0, s, t, chunk_counts);
   hipLaunchKernelGGL(huff_stuff_scan_kernel, dim3(1), dim3(kStreamScanThreads), 0, s, chunk_counts, nchunks, t, out_bytes);

@@ -315,9 +315,11 @@ struct HuffStream {
   uint64_t* seg_start;  // [nseg + 1] first bit of every segment; [nseg] = total bits
   uint32_t* raw;        // the unstuffed stream, raw_words words
   uint64_t raw_words;
-  uint32_t* meta;       // [0..1] total bits, [2] status
+  uint32_t* meta;       // [0..1] total bits, [2] status, [3] segments of the large size class
+  uint32_t* slots;      // [nseg] x huff_stream_slot_bytes(1): the small-class segments' bits at phase 0 (nullptr: the two-pass route)
 };
 int huff_stream_segment_mcus(int blocks_per_mcu);
+size_t huff_stream_slot_bytes(int nseg);
 int huff_stuff_chunks(uint64_t raw_bytes);
 hipError_t launch_huffman_encode_stream(const HuffArgs& a, const HuffStream& t, uint32_t* chunk_counts, uint64_t* out_bytes, uint8_t* out, uint64_t cap,
                                         hipStream_t s);
