@@ -288,10 +288,12 @@ bool device_scan_decode(jpeg_decompress_struct* cinfo, bool want_rgb, unsigned c
 #endif
   }
   uhdr_error_info_t r;
-  if (want_rgb && planar_fmt == UHDR_IMG_FMT_12bppYCbCr420) {
-    // 4:2:0 -> RGB: the libjpeg family's chroma reconstruction on the device (turbo's fancy upsampling / IJG 9's 16x16 chroma IDCT)
+  if (want_rgb && (planar_fmt == UHDR_IMG_FMT_12bppYCbCr420 || planar_fmt == UHDR_IMG_FMT_16bppYCbCr422)) {
+    // 4:2:0 / 4:2:2 -> RGB: the libjpeg family's chroma reconstruction on the device (turbo's fancy upsampling / IJG 9's 16x16 or
+    // 16x8 chroma IDCT)
     if (reached) *reached = true;  // decode_rgb tallies its own outcome from here on
-    if (!decode_rgb(&hdr, cinfo->src->next_input_byte, cinfo->src->bytes_in_buffer, channels, variant, dest, hstride[0], &r)) return false;
+    const auto decode = planar_fmt == UHDR_IMG_FMT_16bppYCbCr422 ? decode_rgb422 : decode_rgb;
+    if (!decode(&hdr, cinfo->src->next_input_byte, cinfo->src->bytes_in_buffer, channels, variant, dest, hstride[0], &r)) return false;
     *st = r;
     if (r.error_code == UHDR_CODEC_OK) *out_fmt = channels == 4 ? UHDR_IMG_FMT_32bppRGBA8888 : UHDR_IMG_FMT_24bppRGB888;
     return true;
@@ -335,10 +337,9 @@ bool jpeg_decompress_on_device(jpeg_decompress_struct* cinfo, bool want_rgb, uns
       else if (mh == 2 && mv == 1) fmt = UHDR_IMG_FMT_16bppYCbCr422;
       else if (mh == 2 && mv == 2) fmt = UHDR_IMG_FMT_12bppYCbCr420;
       else return false;
-      if (want_rgb && fmt == UHDR_IMG_FMT_16bppYCbCr422) return false;  // libjpeg's h2v1 upsampling stays libjpeg's
     }
-    if (want_rgb && fmt == UHDR_IMG_FMT_12bppYCbCr420) {
-      // 4:2:0 -> RGB exists on the device only as the whole-file decode: the coefficient route below (jpeg_read_coefficients) has
+    if (want_rgb && (fmt == UHDR_IMG_FMT_12bppYCbCr420 || fmt == UHDR_IMG_FMT_16bppYCbCr422)) {
+      // 4:2:0 / 4:2:2 -> RGB exists on the device only as the whole-file decode: the coefficient route below (jpeg_read_coefficients) has
       // no way back to libjpeg's upsampler, so every reason to keep libjpeg is settled here, before that call
       if (getenv("UHDR_HIP_SEAM_CPU_UPSAMPLE")) { decline("jpeg_decode_rgb", "UHDR_HIP_SEAM_CPU_UPSAMPLE"); return false; }
       if (getenv("UHDR_HIP_SEAM_CPU_ENTROPY")) { decline("jpeg_decode_rgb", "UHDR_HIP_SEAM_CPU_ENTROPY"); return false; }

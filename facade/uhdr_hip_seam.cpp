@@ -613,13 +613,15 @@ bool decode_scan(const void* hdr, const unsigned char* data, size_t bytes, int o
   return on_device_;
 }
 
-bool decode_rgb(const void* hdr, const unsigned char* data, size_t bytes, int channels, int libjpeg_variant, unsigned char* rgb,
-                unsigned int stride_px, uhdr_error_info_t* st) {
+namespace {
+typedef uhdr_error_info_t (*decode_rgb_fn)(uhdr_hip_ctx_t*, const uhdr_hip_jpeg_header_t*, const uint8_t*, size_t, int, int, uint8_t*, unsigned int);
+bool decode_rgb_with(decode_rgb_fn fn, const void* hdr, const unsigned char* data, size_t bytes, int channels, int libjpeg_variant,
+                     unsigned char* rgb, unsigned int stride_px, uhdr_error_info_t* st) {
   // every exit that leaves the work to the reference's CPU code drops the device-resident copies
   const bool on_device_ = [&]() -> bool {
     if (!cur()) return false;
     enter();
-    *st = uhdr_hip_jpeg_decode_rgb(cur(), static_cast<const uhdr_hip_jpeg_header_t*>(hdr), data, bytes, channels, libjpeg_variant, rgb, stride_px);
+    *st = fn(cur(), static_cast<const uhdr_hip_jpeg_header_t*>(hdr), data, bytes, channels, libjpeg_variant, rgb, stride_px);
     // corrupt entropy-coded data: libjpeg decodes such files with warnings and padding; that behaviour stays libjpeg's
     if (st->error_code == UHDR_CODEC_INVALID_PARAM) {
       note("jpeg_decode_rgb", false, st->has_detail ? st->detail : "");
@@ -629,6 +631,17 @@ bool decode_rgb(const void* hdr, const unsigned char* data, size_t bytes, int ch
   }();
   if (!on_device_) drop_resident();
   return on_device_;
+}
+}  // namespace
+
+bool decode_rgb(const void* hdr, const unsigned char* data, size_t bytes, int channels, int libjpeg_variant, unsigned char* rgb,
+                unsigned int stride_px, uhdr_error_info_t* st) {
+  return decode_rgb_with(uhdr_hip_jpeg_decode_rgb, hdr, data, bytes, channels, libjpeg_variant, rgb, stride_px, st);
+}
+
+bool decode_rgb422(const void* hdr, const unsigned char* data, size_t bytes, int channels, int libjpeg_variant, unsigned char* rgb,
+                   unsigned int stride_px, uhdr_error_info_t* st) {
+  return decode_rgb_with(uhdr_hip_jpeg_decode_rgb_any, hdr, data, bytes, channels, libjpeg_variant, rgb, stride_px, st);
 }
 
 void decline(const char* stage, const char* why) {

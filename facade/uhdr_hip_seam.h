@@ -156,6 +156,9 @@ bool decode_scan(const void* hdr, const unsigned char* data, size_t bytes, int o
 // Same contract as decode_scan: false = the device path does not take this file, nothing was consumed.
 bool decode_rgb(const void* hdr, const unsigned char* data, size_t bytes, int channels, int libjpeg_variant, unsigned char* rgb,
                 unsigned int stride_px, uhdr_error_info_t* st);
+// The same for a 4:2:2 file (uhdr_hip_jpeg_decode_rgb_any: libjpeg's h2v1 chroma reconstruction); tallied as stage jpeg_decode_rgb.
+bool decode_rgb422(const void* hdr, const unsigned char* data, size_t bytes, int channels, int libjpeg_variant, unsigned char* rgb,
+                   unsigned int stride_px, uhdr_error_info_t* st);
 // a stage the seam leaves to the reference's CPU code before calling into the library (a route option, a layout it does not
 // take): tallied as that stage's reference route, and the device-resident copies are dropped
 void decline(const char* stage, const char* why);

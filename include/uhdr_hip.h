@@ -594,6 +594,27 @@ uhdr_error_info_t uhdr_hip_jpeg_decode_rgb(uhdr_hip_ctx_t* ctx, const uhdr_hip_j
                                            size_t scan_bytes, int out_channels, int libjpeg_variant, uint8_t* rgb,
                                            unsigned int stride_px);
 
+/* 4:2:2 JPEG (2x1 / 1x1 / 1x1, what jpegdecoderhelper.cpp:156 reports as UHDR_IMG_FMT_16bppYCbCr422 and jpegr.cpp:538, 1587
+ * accept as the SDR intent of API-2/3/4) -> packed RGB888 / RGBA8888 (alpha 255), libjpeg-exact: the same
+ * DECODE_TO_RGB_CS decode (jpegdecoderhelper.cpp:349-375, decodeToCSRGB :456-478) as above.  libjpeg_variant 0 =
+ * libjpeg-turbo (8x8 islow IDCT, h2v1_fancy_upsample; plain replication when ceil(w/2) <= 2), 1 = IJG libjpeg 9 (each chroma
+ * block rebuilt as 16 x 8 samples by jpeg_idct_16x8).
+ *
+ * uhdr_hip_idct_upsample_rgb422_dev: arguments as uhdr_hip_idct_upsample_rgb_dev; the chroma arrays are on the 4:2:2
+ * width_in_blocks grids, ceil(ceil(w/2)/8) x ceil(h/8) blocks per component.  Stream-ordered, no host synchronisation.
+ *
+ * uhdr_hip_jpeg_decode_rgb_any: arguments as uhdr_hip_jpeg_decode_rgb.  3-component 4:4:4 and 4:2:0 files run exactly what
+ * that entry runs; 4:2:2 files take the 4:2:2 kernel behind the same upload and entropy decode (the device copies the
+ * resident handoff keeps of rgb are dropped).  Any other sampling, and grayscale: UHDR_CODEC_UNSUPPORTED_FEATURE.  Its time
+ * is reported in uhdr_hip_stats_t::last_jpeg_decode_rgb_ns.  Synchronous. */
+uhdr_error_info_t uhdr_hip_idct_upsample_rgb422_dev(uhdr_hip_ctx_t* ctx, const int16_t* coef_y, const int16_t* coef_cb,
+                                                    const int16_t* coef_cr, unsigned int w, unsigned int h,
+                                                    const uint16_t qt_y[64], const uint16_t qt_cb[64],
+                                                    const uint16_t qt_cr[64], int libjpeg_variant, uhdr_raw_image_t* rgb);
+uhdr_error_info_t uhdr_hip_jpeg_decode_rgb_any(uhdr_hip_ctx_t* ctx, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data,
+                                               size_t scan_bytes, int out_channels, int libjpeg_variant, uint8_t* rgb,
+                                               unsigned int stride_px);
+
 /* The encode-side mirror: JpegEncoderHelper::compressImage's sample -> entropy-coded-data part
  * (jpegencoderhelper.cpp:131-309) on the device.  FDCT + quantization (uhdr_hip_fdct_quant_dev; for a packed RGB gain map
  * uhdr_hip_fdct_quant_rgb_dev, i.e. rgb_ycc_convert included) feed uhdr_hip_huffman_encode_dev without the coefficient
@@ -779,7 +800,7 @@ typedef struct uhdr_hip_stats {
    * C / C++ caller such as the facade pays, without the overhead of whatever binding drives the library */
   unsigned long long last_jpeg_decode_scan_ns;
   unsigned long long last_encode_api1_scans_ns;
-  unsigned long long last_jpeg_decode_rgb_ns;     /* uhdr_hip_jpeg_decode_rgb, the same way */
+  unsigned long long last_jpeg_decode_rgb_ns;     /* uhdr_hip_jpeg_decode_rgb / _rgb_any, the same way */
 } uhdr_hip_stats_t;
 void uhdr_hip_get_stats(uhdr_hip_ctx_t* ctx, uhdr_hip_stats_t* out);
 

@@ -463,6 +463,10 @@ hipError_t launch_idct_dequant_rgb(const int16_t* coef_y, const int16_t* coef_cb
 size_t upsample420_scratch_bytes(const int bw[3], const int bh[3]);
 hipError_t launch_idct_upsample_rgb(const int16_t* const coef[3], const int bw[3], const int bh[3], const uint16_t* const qt_host[3],
                                     int variant, const ImageViewMut& rgb, uint8_t* chroma_scratch, hipStream_t s);
+// jpeg_upsample422.hip: the same for 4:2:2 (2x1 / 1x1 / 1x1) coefficient blocks; the chroma grids cover ceil(w/2) x h samples
+size_t upsample422_scratch_bytes(const int bw[3], const int bh[3]);
+hipError_t launch_idct_upsample_rgb422(const int16_t* const coef[3], const int bw[3], const int bh[3], const uint16_t* const qt_host[3],
+                                       int variant, const ImageViewMut& rgb, uint8_t* chroma_scratch, hipStream_t s);
 hipError_t launch_jpeg_rgb_to_ycc(const ImageView& rgb, const ImageViewMut& ycc, hipStream_t s);
 hipError_t launch_jpeg_ycc_to_rgb(const ImageView& ycc, const ImageViewMut& rgb, int variant, hipStream_t s);
 
