@@ -1106,40 +1106,43 @@ static uhdr_error_info_t jpeg_decode_scan_impl(uhdr_hip_ctx_t* c, const uhdr_hip
   return ok_status();
 }
 
-// ---- 4:2:0 -> RGB: libjpeg's chroma reconstruction on the device (jpeg_upsample.hip) ------------------------------------
-static bool is_420(const uhdr_hip_jpeg_scan_t& sc) {
-  return sc.num_components == 3 && sc.h_samp[0] == 2 && sc.v_samp[0] == 2 && sc.h_samp[1] == 1 && sc.v_samp[1] == 1 && sc.h_samp[2] == 1 &&
-         sc.v_samp[2] == 1;
+// ---- 4:2:0 / 4:2:2 -> RGB: libjpeg's chroma reconstruction on the device (jpeg_upsample.hip) -------------------------------
+// the luma vertical sampling factor of a 4:2:0 (2) or 4:2:2 (1) scan; 0: neither
+static int subsampled_vsamp(const uhdr_hip_jpeg_scan_t& sc) {
+  if (sc.num_components != 3 || sc.h_samp[0] != 2 || sc.h_samp[1] != 1 || sc.v_samp[1] != 1 || sc.h_samp[2] != 1 || sc.v_samp[2] != 1) return 0;
+  return sc.v_samp[0] == 2 || sc.v_samp[0] == 1 ? sc.v_samp[0] : 0;
 }
 
 // grids: the arrays' block grids (libjpeg's width_in_blocks, or larger up to the MCU-padded grid); rgb: device image, w x h
 static uhdr_error_info_t idct_upsample_rgb_impl(uhdr_hip_ctx_t* c, const int16_t* const coef[3], const int bw[3], const int bh[3],
-                                                const uint16_t* const qt[3], int variant, uhdr_raw_image_t* rgb) {
+                                                const uint16_t* const qt[3], int variant, int vsamp, uhdr_raw_image_t* rgb) {
   if (bw[1] != bw[2] || bh[1] != bh[2]) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "Cb and Cr block grids differ");
+  // 4:2:2, variant 0 reads the chroma planes at the real samples, ceil(w/2) x h: the grids must hold them
+  if (vsamp == 1 && ((unsigned)bw[1] * 8 < (rgb->w + 1) / 2 || (unsigned)bh[1] * 8 < rgb->h))
+    return err_status(UHDR_CODEC_INVALID_PARAM, "a %dx%d chroma block grid does not cover a %ux%u 4:2:2 image", bw[1], bh[1], rgb->w, rgb->h);
   for (int k = 0; k < 3; k++)
     for (int i = 0; i < 64; i++)
       if (qt[k][i] == 0) return err_status(UHDR_CODEC_INVALID_PARAM, "quantization table %d entry %d is zero", k, i);
   uint8_t* scratch = nullptr;
   if (variant == 0) {
-    UHDR_TRY(ensure(c->jpg[5], upsample420_scratch_bytes(bw, bh)));
+    UHDR_TRY(ensure(c->jpg[5], upsample_scratch_bytes(bw, bh)));
     scratch = (uint8_t*)c->jpg[5].p;
   }
   rgb->range = UHDR_CR_FULL_RANGE;
-  ProfScope ps(c, "idct_upsample_rgb");
-  HIP_TRY(launch_idct_upsample_rgb(coef, bw, bh, qt, variant, view_mut_of(rgb), scratch, c->stream));
+  ProfScope ps(c, vsamp == 2 ? "idct_upsample_rgb" : "idct_upsample_rgb422");
+  HIP_TRY(launch_idct_upsample_rgb(coef, bw, bh, qt, variant, vsamp, view_mut_of(rgb), scratch, c->stream));
   return ok_status();
 }
 
-// JpegDecoderHelper::decompressImage's DECODE_TO_RGB_CS branch (jpegdecoderhelper.cpp:349-375, decodeToCSRGB :456-478) after the
-// entropy decode, for a 4:2:0 file: dequant + islow IDCT of luma, libjpeg's chroma reconstruction, ycc_rgb_convert.
-uhdr_error_info_t uhdr_hip_idct_upsample_rgb_dev(uhdr_hip_ctx_t* c, const int16_t* coef_y, const int16_t* coef_cb, const int16_t* coef_cr,
-                                                 unsigned int w, unsigned int h, const uint16_t qt_y[64], const uint16_t qt_cb[64],
-                                                 const uint16_t qt_cr[64], int variant, uhdr_raw_image_t* rgb) {
+// The two device entries behind their chroma grids (cbw x cbh blocks per chroma component); name: the entry, for its messages
+static uhdr_error_info_t idct_upsample_rgb_dev(const char* name, uhdr_hip_ctx_t* c, const int16_t* coef_y, const int16_t* coef_cb,
+                                               const int16_t* coef_cr, unsigned int w, unsigned int h, int cbw, int cbh, const uint16_t qt_y[64],
+                                               const uint16_t qt_cb[64], const uint16_t qt_cr[64], int variant, int vsamp, uhdr_raw_image_t* rgb) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!coef_y || !coef_cb || !coef_cr || !qt_y || !qt_cb || !qt_cr || !rgb || !rgb->planes[0])
-    return err_status(UHDR_CODEC_INVALID_PARAM, "received bad argument for idct_upsample_rgb");
+    return err_status(UHDR_CODEC_INVALID_PARAM, "received bad argument for %s", name);
   if (rgb->fmt != UHDR_IMG_FMT_24bppRGB888 && rgb->fmt != UHDR_IMG_FMT_32bppRGBA8888)
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "idct_upsample_rgb expects UHDR_IMG_FMT_24bppRGB888 or UHDR_IMG_FMT_32bppRGBA8888. Received %d", rgb->fmt);
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "%s expects UHDR_IMG_FMT_24bppRGB888 or UHDR_IMG_FMT_32bppRGBA8888. Received %d", name, rgb->fmt);
   if (variant != 0 && variant != 1) return err_status(UHDR_CODEC_INVALID_PARAM, "unknown libjpeg variant %d", variant);
   if (w == 0 || h == 0 || w > 65535 || h > 65535) return err_status(UHDR_CODEC_INVALID_PARAM, "image dimensions %ux%u are outside JPEG's 1..65535", w, h);
   if (rgb->w != w || rgb->h != h) return err_status(UHDR_CODEC_INVALID_PARAM, "destination is %ux%u, the image %ux%u", rgb->w, rgb->h, w, h);
@@ -1148,18 +1151,38 @@ uhdr_error_info_t uhdr_hip_idct_upsample_rgb_dev(uhdr_hip_ctx_t* c, const int16_
     return err_status(UHDR_CODEC_INVALID_PARAM, "coefficient buffers must be 16-byte aligned");
   HIP_TRY(hipSetDevice(c->device));
   const int16_t* coef[3] = {coef_y, coef_cb, coef_cr};
-  const int bw[3] = {(int)((w + 7) / 8), (int)((w + 15) / 16), (int)((w + 15) / 16)};
-  const int bh[3] = {(int)((h + 7) / 8), (int)((h + 15) / 16), (int)((h + 15) / 16)};
+  const int bw[3] = {(int)((w + 7) / 8), cbw, cbw};
+  const int bh[3] = {(int)((h + 7) / 8), cbh, cbh};
   const uint16_t* qt[3] = {qt_y, qt_cb, qt_cr};
-  return idct_upsample_rgb_impl(c, coef, bw, bh, qt, variant, rgb);
+  return idct_upsample_rgb_impl(c, coef, bw, bh, qt, variant, vsamp, rgb);
+}
+
+// JpegDecoderHelper::decompressImage's DECODE_TO_RGB_CS branch (jpegdecoderhelper.cpp:349-375, decodeToCSRGB :456-478) after the
+// entropy decode, for a 4:2:0 file: dequant + islow IDCT of luma, libjpeg's chroma reconstruction, ycc_rgb_convert.
+uhdr_error_info_t uhdr_hip_idct_upsample_rgb_dev(uhdr_hip_ctx_t* c, const int16_t* coef_y, const int16_t* coef_cb, const int16_t* coef_cr,
+                                                 unsigned int w, unsigned int h, const uint16_t qt_y[64], const uint16_t qt_cb[64],
+                                                 const uint16_t qt_cr[64], int variant, uhdr_raw_image_t* rgb) {
+  return idct_upsample_rgb_dev("idct_upsample_rgb", c, coef_y, coef_cb, coef_cr, w, h, (int)((w + 15) / 16), (int)((h + 15) / 16), qt_y, qt_cb, qt_cr,
+                               variant, 2, rgb);
+}
+
+// The same for a 4:2:2 file (the sampling jpegdecoderhelper.cpp:156 reports as UHDR_IMG_FMT_16bppYCbCr422).
+uhdr_error_info_t uhdr_hip_idct_upsample_rgb422_dev(uhdr_hip_ctx_t* c, const int16_t* coef_y, const int16_t* coef_cb, const int16_t* coef_cr,
+                                                    unsigned int w, unsigned int h, const uint16_t qt_y[64], const uint16_t qt_cb[64],
+                                                    const uint16_t qt_cr[64], int variant, uhdr_raw_image_t* rgb) {
+  return idct_upsample_rgb_dev("idct_upsample_rgb422", c, coef_y, coef_cb, coef_cr, w, h, (int)(((w + 1) / 2 + 7) / 8), (int)((h + 7) / 8), qt_y, qt_cb,
+                               qt_cr, variant, 1, rgb);
 }
 
 // JpegDecoderHelper::decompressImage(DECODE_TO_RGB_CS) (jpegdecoderhelper.cpp:169-535) for a whole baseline file: what uhdr_decode
-// runs for UHDR_CT_SRGB / RGBA8888 output (jpegr.cpp:1479-1525).  4:4:4 goes through uhdr_hip_jpeg_decode_scan's fused path.
+// runs for UHDR_CT_SRGB / RGBA8888 output (jpegr.cpp:1479-1525).  4:4:4 goes through uhdr_hip_jpeg_decode_scan's fused path, 4:2:0
+// and -- allow_422, uhdr_hip_jpeg_decode_rgb_any: the SDR intent jpegr.cpp:538, 1587 accept from API-2/3/4 callers -- 4:2:2 through
+// the upsampling kernel behind the shared upload and entropy stage.
 static uhdr_error_info_t jpeg_decode_rgb_impl(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data, size_t scan_bytes,
-                                              int out_channels, int variant, uint8_t* rgb, unsigned int stride_px) {
+                                              int out_channels, int variant, uint8_t* rgb, unsigned int stride_px, bool allow_422) {
+  const char* name = allow_422 ? "jpeg_decode_rgb_any" : "jpeg_decode_rgb";
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
-  if (!hdr || !scan_data || !rgb) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument for jpeg_decode_rgb");
+  if (!hdr || !scan_data || !rgb) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument for %s", name);
   if (out_channels != 3 && out_channels != 4) return err_status(UHDR_CODEC_INVALID_PARAM, "out_channels is 3 (RGB888) or 4 (RGBA8888), received %d", out_channels);
   if (variant != 0 && variant != 1) return err_status(UHDR_CODEC_INVALID_PARAM, "unknown libjpeg variant %d", variant);
   uhdr_hip_jpeg_scan_t sc = hdr->scan;
@@ -1173,7 +1196,8 @@ static uhdr_error_info_t jpeg_decode_rgb_impl(uhdr_hip_ctx_t* c, const uhdr_hip_
     const unsigned int hs[3] = {stride_px, 0, 0}, vs[3] = {sc.h, 0, 0};
     return jpeg_decode_scan_impl(c, hdr, scan_data, scan_bytes, out_channels, variant, planes, hs, vs);
   }
-  if (!is_420(sc))
+  const int vsamp = subsampled_vsamp(sc);
+  if (vsamp == 0 || (vsamp == 1 && !allow_422))
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "RGB output on the device takes 4:2:0 or 4:4:4 files; received %d components at %dx%d / %dx%d / %dx%d",
                       sc.num_components, sc.h_samp[0], sc.v_samp[0], sc.h_samp[1], sc.v_samp[1], sc.h_samp[2], sc.v_samp[2]);
   if (sc.blocks_w[1] != sc.blocks_w[2] || sc.blocks_h[1] != sc.blocks_h[2]) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "Cb and Cr block grids differ");
@@ -1191,118 +1215,31 @@ static uhdr_error_info_t jpeg_decode_rgb_impl(uhdr_hip_ctx_t* c, const uhdr_hip_
   img.planes[0] = c->jpg[4].p;
   img.stride[0] = (unsigned int)pitch_px;
   const uint16_t* qt[3] = {hdr->qtable[0], hdr->qtable[1], hdr->qtable[2]};
-  UHDR_TRY(idct_upsample_rgb_impl(c, sc.coef, sc.blocks_w, sc.blocks_h, qt, variant, &img));
+  UHDR_TRY(idct_upsample_rgb_impl(c, sc.coef, sc.blocks_w, sc.blocks_h, qt, variant, vsamp, &img));
   HIP_TRY(hipMemcpy2DAsync(rgb, (size_t)stride_px * out_channels, c->jpg[4].p, pitch_px * out_channels, (size_t)sc.w * out_channels, sc.h,
                            hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  dbg.mark("jpeg_decode_rgb: done");
+  dbg.mark(vsamp == 1 ? "jpeg_decode_rgb_any: done" : "jpeg_decode_rgb: done");
   return ok_status();
+}
+
+// fills stats.last_jpeg_decode_rgb_ns for both whole-file entries
+static uhdr_error_info_t jpeg_decode_rgb_timed(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data, size_t scan_bytes,
+                                               int out_channels, int variant, uint8_t* rgb, unsigned int stride_px, bool allow_422) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const uhdr_error_info_t r = jpeg_decode_rgb_impl(c, hdr, scan_data, scan_bytes, out_channels, variant, rgb, stride_px, allow_422);
+  if (c) c->stats.last_jpeg_decode_rgb_ns = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+  return r;
 }
 
 uhdr_error_info_t uhdr_hip_jpeg_decode_rgb(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data, size_t scan_bytes,
                                            int out_channels, int variant, uint8_t* rgb, unsigned int stride_px) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const uhdr_error_info_t r = jpeg_decode_rgb_impl(c, hdr, scan_data, scan_bytes, out_channels, variant, rgb, stride_px);
-  if (c) c->stats.last_jpeg_decode_rgb_ns = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-  return r;
-}
-
-// ---- 4:2:2 -> RGB: libjpeg's chroma reconstruction on the device (jpeg_upsample422.hip) -----------------------------------
-static bool is_422(const uhdr_hip_jpeg_scan_t& sc) {
-  return sc.num_components == 3 && sc.h_samp[0] == 2 && sc.v_samp[0] == 1 && sc.h_samp[1] == 1 && sc.v_samp[1] == 1 && sc.h_samp[2] == 1 &&
-         sc.v_samp[2] == 1;
-}
-
-// grids: the arrays' block grids (libjpeg's width_in_blocks, or larger up to the MCU-padded grid); rgb: device image, w x h
-static uhdr_error_info_t idct_upsample_rgb422_impl(uhdr_hip_ctx_t* c, const int16_t* const coef[3], const int bw[3], const int bh[3],
-                                                   const uint16_t* const qt[3], int variant, uhdr_raw_image_t* rgb) {
-  if (bw[1] != bw[2] || bh[1] != bh[2]) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "Cb and Cr block grids differ");
-  // variant 0 reads the chroma planes at the real samples, ceil(w/2) x h: the grids must hold them
-  if ((unsigned)bw[1] * 8 < (rgb->w + 1) / 2 || (unsigned)bh[1] * 8 < rgb->h)
-    return err_status(UHDR_CODEC_INVALID_PARAM, "a %dx%d chroma block grid does not cover a %ux%u 4:2:2 image", bw[1], bh[1], rgb->w, rgb->h);
-  for (int k = 0; k < 3; k++)
-    for (int i = 0; i < 64; i++)
-      if (qt[k][i] == 0) return err_status(UHDR_CODEC_INVALID_PARAM, "quantization table %d entry %d is zero", k, i);
-  uint8_t* scratch = nullptr;
-  if (variant == 0) {
-    UHDR_TRY(ensure(c->jpg[5], upsample422_scratch_bytes(bw, bh)));
-    scratch = (uint8_t*)c->jpg[5].p;
-  }
-  rgb->range = UHDR_CR_FULL_RANGE;
-  ProfScope ps(c, "idct_upsample_rgb422");
-  HIP_TRY(launch_idct_upsample_rgb422(coef, bw, bh, qt, variant, view_mut_of(rgb), scratch, c->stream));
-  return ok_status();
-}
-
-// JpegDecoderHelper::decompressImage's DECODE_TO_RGB_CS branch (jpegdecoderhelper.cpp:349-375, decodeToCSRGB :456-478) after the
-// entropy decode, for a 4:2:2 file (the sampling jpegdecoderhelper.cpp:156 reports as UHDR_IMG_FMT_16bppYCbCr422): dequant + islow
-// IDCT of luma, libjpeg's chroma reconstruction, ycc_rgb_convert.
-uhdr_error_info_t uhdr_hip_idct_upsample_rgb422_dev(uhdr_hip_ctx_t* c, const int16_t* coef_y, const int16_t* coef_cb, const int16_t* coef_cr,
-                                                    unsigned int w, unsigned int h, const uint16_t qt_y[64], const uint16_t qt_cb[64],
-                                                    const uint16_t qt_cr[64], int variant, uhdr_raw_image_t* rgb) {
-  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
-  if (!coef_y || !coef_cb || !coef_cr || !qt_y || !qt_cb || !qt_cr || !rgb || !rgb->planes[0])
-    return err_status(UHDR_CODEC_INVALID_PARAM, "received bad argument for idct_upsample_rgb422");
-  if (rgb->fmt != UHDR_IMG_FMT_24bppRGB888 && rgb->fmt != UHDR_IMG_FMT_32bppRGBA8888)
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "idct_upsample_rgb422 expects UHDR_IMG_FMT_24bppRGB888 or UHDR_IMG_FMT_32bppRGBA8888. Received %d", rgb->fmt);
-  if (variant != 0 && variant != 1) return err_status(UHDR_CODEC_INVALID_PARAM, "unknown libjpeg variant %d", variant);
-  if (w == 0 || h == 0 || w > 65535 || h > 65535) return err_status(UHDR_CODEC_INVALID_PARAM, "image dimensions %ux%u are outside JPEG's 1..65535", w, h);
-  if (rgb->w != w || rgb->h != h) return err_status(UHDR_CODEC_INVALID_PARAM, "destination is %ux%u, the image %ux%u", rgb->w, rgb->h, w, h);
-  if (rgb->stride[0] < w) return err_status(UHDR_CODEC_INVALID_PARAM, "stride (%u) cannot be less than width (%u)", rgb->stride[0], w);
-  if (((uintptr_t)coef_y | (uintptr_t)coef_cb | (uintptr_t)coef_cr) & 15)
-    return err_status(UHDR_CODEC_INVALID_PARAM, "coefficient buffers must be 16-byte aligned");
-  HIP_TRY(hipSetDevice(c->device));
-  const int16_t* coef[3] = {coef_y, coef_cb, coef_cr};
-  const int cbw = (int)(((w + 1) / 2 + 7) / 8);
-  const int bw[3] = {(int)((w + 7) / 8), cbw, cbw};
-  const int bh[3] = {(int)((h + 7) / 8), (int)((h + 7) / 8), (int)((h + 7) / 8)};
-  const uint16_t* qt[3] = {qt_y, qt_cb, qt_cr};
-  return idct_upsample_rgb422_impl(c, coef, bw, bh, qt, variant, rgb);
-}
-
-// JpegDecoderHelper::decompressImage(DECODE_TO_RGB_CS) (jpegdecoderhelper.cpp:169-535) for a whole baseline file of any sampling the
-// device rebuilds: 4:4:4 and 4:2:0 run uhdr_hip_jpeg_decode_rgb's own code, 4:2:2 (the SDR intent jpegr.cpp:538, 1587 accept from
-// API-2/3/4 callers) the kernel above behind the shared upload and entropy stage.
-static uhdr_error_info_t jpeg_decode_rgb_any_impl(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data, size_t scan_bytes,
-                                                  int out_channels, int variant, uint8_t* rgb, unsigned int stride_px) {
-  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
-  if (!hdr || !scan_data || !rgb) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument for jpeg_decode_rgb_any");
-  if (!is_422(hdr->scan)) return jpeg_decode_rgb_impl(c, hdr, scan_data, scan_bytes, out_channels, variant, rgb, stride_px);
-  if (out_channels != 3 && out_channels != 4) return err_status(UHDR_CODEC_INVALID_PARAM, "out_channels is 3 (RGB888) or 4 (RGBA8888), received %d", out_channels);
-  if (variant != 0 && variant != 1) return err_status(UHDR_CODEC_INVALID_PARAM, "unknown libjpeg variant %d", variant);
-  uhdr_hip_jpeg_scan_t sc = hdr->scan;
-  int mpr = 0, mrows = 0, bpm = 0;
-  UHDR_TRY(check_scan(&sc, false, &mpr, &mrows, &bpm));
-  if (stride_px < sc.w) return err_status(UHDR_CODEC_INVALID_PARAM, "stride (%u) cannot be less than width (%u)", stride_px, sc.w);
-  if (sc.blocks_w[1] != sc.blocks_w[2] || sc.blocks_h[1] != sc.blocks_h[2]) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "Cb and Cr block grids differ");
-  const DbgClock dbg;
-  UHDR_TRY(jpeg_scan_to_coefficients(c, hdr, scan_data, scan_bytes, dbg, sc));
-  // the image is written to the caller's buffer, so any device copy the resident handoff keeps of that buffer is stale
-  resident_drop(c, rgb);
-  uhdr_raw_image_t img;
-  memset(&img, 0, sizeof img);
-  img.fmt = out_channels == 3 ? UHDR_IMG_FMT_24bppRGB888 : UHDR_IMG_FMT_32bppRGBA8888;
-  img.w = sc.w;
-  img.h = sc.h;
-  const size_t pitch_px = ((size_t)sc.w + 63) & ~(size_t)63;
-  UHDR_TRY(ensure(c->jpg[4], pitch_px * (size_t)out_channels * sc.h));
-  img.planes[0] = c->jpg[4].p;
-  img.stride[0] = (unsigned int)pitch_px;
-  const uint16_t* qt[3] = {hdr->qtable[0], hdr->qtable[1], hdr->qtable[2]};
-  UHDR_TRY(idct_upsample_rgb422_impl(c, sc.coef, sc.blocks_w, sc.blocks_h, qt, variant, &img));
-  HIP_TRY(hipMemcpy2DAsync(rgb, (size_t)stride_px * out_channels, c->jpg[4].p, pitch_px * out_channels, (size_t)sc.w * out_channels, sc.h,
-                           hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  dbg.mark("jpeg_decode_rgb_any: done");
-  return ok_status();
+  return jpeg_decode_rgb_timed(c, hdr, scan_data, scan_bytes, out_channels, variant, rgb, stride_px, false);
 }
 
 uhdr_error_info_t uhdr_hip_jpeg_decode_rgb_any(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* hdr, const uint8_t* scan_data, size_t scan_bytes,
                                                int out_channels, int variant, uint8_t* rgb, unsigned int stride_px) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const uhdr_error_info_t r = jpeg_decode_rgb_any_impl(c, hdr, scan_data, scan_bytes, out_channels, variant, rgb, stride_px);
-  if (c) c->stats.last_jpeg_decode_rgb_ns = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-  return r;
+  return jpeg_decode_rgb_timed(c, hdr, scan_data, scan_bytes, out_channels, variant, rgb, stride_px, true);
 }
 
 // JpegR::decodeJPEGR behind its container parsing (jpegr.cpp:1469-1531) on DEVICE-resident data in ONE entry point (round 6): the two

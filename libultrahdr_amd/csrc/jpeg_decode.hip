@@ -20,11 +20,13 @@
 // 32-bit multiply path, whose wrap-around equals libjpeg's INT32 arithmetic.
 #include "idct_core.h"
 #include "uhdr_types.h"
+#include "upsample_core.h"
 
 namespace uhdr {
 namespace {
 
 using namespace idct;
+using namespace upsample;  // FIX16, ycc_px (jdcolor.c ycc_rgb_convert), ycc_green_constants, pack_rgb888, resident_grid
 
 constexpr int kBlock = 256;
 
@@ -69,8 +71,6 @@ __global__ __launch_bounds__(kBlock) void idct_dequant_kernel(const int16_t* __r
 }
 
 // ---- libjpeg colour conversions (16-bit fixed point) -----------------------------------------------
-#define FIX16(x) ((int)((x) * 65536.0 + 0.5))
-
 // jccolor.c rgb_ycc_convert.  (The 6b / libjpeg-turbo constants and IJG 9's longer ones give the same
 // result for every 8-bit (r, g, b): checked exhaustively, tests/test_host_logic.py.)
 __device__ __forceinline__ void rgb_to_ycc_px(uint32_t r, uint32_t g, uint32_t b, uint32_t& y, uint32_t& cb, uint32_t& cr) {
@@ -135,18 +135,6 @@ __global__ __launch_bounds__(kBlock) void jpeg_rgb_to_ycc_kernel(const JpegColor
   }
 }
 
-// jdcolor.c ycc_rgb_convert: r = y + ((FIX(1.402) v + half) >> 16), b likewise with 1.772 u,
-// g = y + ((-k_cb_g u + half - k_cr_g v) >> 16), each clamped to [0, 255]
-__device__ __forceinline__ uint32_t clamp255(int v) { return (uint32_t)min(max(v, 0), 255); }
-__device__ __forceinline__ uint32_t ycc_to_rgb_px(uint32_t y, uint32_t cb, uint32_t cr, int k_cr_g, int k_cb_g) {
-  const int half = 1 << 15;
-  const int yy = (int)y, u = (int)cb - 128, v = (int)cr - 128;
-  const uint32_t r = clamp255(yy + ((FIX16(1.40200) * v + half) >> 16));
-  const uint32_t g = clamp255(yy + (((-k_cb_g) * u + half + (-k_cr_g) * v) >> 16));
-  const uint32_t b = clamp255(yy + ((FIX16(1.77200) * u + half) >> 16));
-  return r | (g << 8) | (b << 16) | (255u << 24);
-}
-
 template <int BPP, bool VEC>
 __global__ __launch_bounds__(kBlock) void jpeg_ycc_to_rgb_kernel(const JpegColorParams p) {
   const uint32_t per_row = VEC ? p.w / 4 : p.w;
@@ -162,18 +150,15 @@ __global__ __launch_bounds__(kBlock) void jpeg_ycc_to_rgb_kernel(const JpegColor
       uint32_t px[4];
 #pragma unroll
       for (int k = 0; k < 4; k++)
-        px[k] = ycc_to_rgb_px((yv >> (8 * k)) & 0xff, (uv >> (8 * k)) & 0xff, (vv >> (8 * k)) & 0xff, p.k_cr_g, p.k_cb_g);
+        px[k] = ycc_px((yv >> (8 * k)) & 0xff, (uv >> (8 * k)) & 0xff, (vv >> (8 * k)) & 0xff, p.k_cr_g, p.k_cb_g);
       if constexpr (BPP == 4) {
         *(uint4*)(dst + j * 16) = make_uint4(px[0], px[1], px[2], px[3]);
       } else {
-        uint32_t* d3 = (uint32_t*)(dst + j * 12);
-        d3[0] = (px[0] & 0xffffff) | (px[1] << 24);
-        d3[1] = ((px[1] >> 8) & 0xffff) | (px[2] << 16);
-        d3[2] = ((px[2] >> 16) & 0xff) | (px[3] << 8);
+        pack_rgb888(px, (uint32_t*)(dst + j * 12));
       }
     } else {
-      const uint32_t px = ycc_to_rgb_px(p.p[0][(size_t)y * p.stride[0] + j], p.p[1][(size_t)y * p.stride[1] + j],
-                                        p.p[2][(size_t)y * p.stride[2] + j], p.k_cr_g, p.k_cb_g);
+      const uint32_t px = ycc_px(p.p[0][(size_t)y * p.stride[0] + j], p.p[1][(size_t)y * p.stride[1] + j],
+                                 p.p[2][(size_t)y * p.stride[2] + j], p.k_cr_g, p.k_cb_g);
       dst[j * BPP] = (uint8_t)px; dst[j * BPP + 1] = (uint8_t)(px >> 8); dst[j * BPP + 2] = (uint8_t)(px >> 16);
       if constexpr (BPP == 4) dst[j * BPP + 3] = 255;
     }
@@ -228,7 +213,7 @@ __global__ __launch_bounds__(kBlock) void idct_dequant_rgb_kernel(const IdctRgbA
     if (bx < bw && y < a.h && x0 < a.w) {
       uint32_t px[8];
 #pragma unroll
-      for (int c = 0; c < 8; c++) px[c] = ycc_to_rgb_px(sy[c], sb[c], sr[c], a.k_cr_g, a.k_cb_g);
+      for (int c = 0; c < 8; c++) px[c] = ycc_px(sy[c], sb[c], sr[c], a.k_cr_g, a.k_cb_g);
       uint8_t* dst = a.rgb + (size_t)y * a.pitch + (size_t)x0 * BPP;
       if (vec_ok && x0 + 8 <= a.w) {
         if constexpr (BPP == 4) {
@@ -236,13 +221,8 @@ __global__ __launch_bounds__(kBlock) void idct_dequant_rgb_kernel(const IdctRgbA
           *(uint4*)(dst + 16) = make_uint4(px[4], px[5], px[6], px[7]);
         } else {
           uint32_t d[6];
-#pragma unroll
-          for (int h = 0; h < 2; h++) {
-            const uint32_t* q4 = px + 4 * h;
-            d[3 * h + 0] = (q4[0] & 0xffffff) | (q4[1] << 24);
-            d[3 * h + 1] = ((q4[1] >> 8) & 0xffff) | (q4[2] << 16);
-            d[3 * h + 2] = ((q4[2] >> 16) & 0xff) | (q4[3] << 8);
-          }
+          pack_rgb888(px, d);
+          pack_rgb888(px + 4, d + 3);
           *(uint2*)dst = make_uint2(d[0], d[1]);
           *(uint2*)(dst + 8) = make_uint2(d[2], d[3]);
           *(uint2*)(dst + 16) = make_uint2(d[4], d[5]);
@@ -258,17 +238,6 @@ __global__ __launch_bounds__(kBlock) void idct_dequant_rgb_kernel(const IdctRgbA
       }
     }
   }
-}
-
-int resident_grid(uint32_t tiles, int per_cu) {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
-  const uint32_t r = (uint32_t)(cus * per_cu);
-  return (int)(tiles < r ? (tiles ? tiles : 1u) : r);
 }
 
 inline bool al(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
@@ -294,8 +263,7 @@ hipError_t launch_idct_dequant_rgb(const int16_t* coef_y, const int16_t* coef_cb
   const int bpp = rgb.fmt == UHDR_IMG_FMT_32bppRGBA8888 ? 4 : 3;
   a.pitch = (size_t)rgb.stride[0] * bpp;
   a.w = rgb.w; a.h = rgb.h; a.bw = bw; a.bh = bh;
-  a.k_cr_g = variant ? FIX16(0.714136286) : FIX16(0.71414);
-  a.k_cb_g = variant ? FIX16(0.344136286) : FIX16(0.34414);
+  ycc_green_constants(variant, &a.k_cr_g, &a.k_cb_g);
   for (int i = 0; i < 64; i++) { a.q[0][i] = qt_luma_host[i]; a.q[1][i] = qt_chroma_host[i]; }
   const int total = ((bw + 7) / 8) * bh;
   const int grid = resident_grid((uint32_t)(total + 3) / 4, 8);
@@ -332,8 +300,7 @@ hipError_t launch_jpeg_ycc_to_rgb(const ImageView& ycc, const ImageViewMut& rgb,
   p.w = ycc.w; p.h = ycc.h; p.rgb_stride_px = rgb.stride[0];
   p.bpp = rgb.fmt == UHDR_IMG_FMT_32bppRGBA8888 ? 4 : 3;
   for (int c = 0; c < 3; c++) { p.p[c] = (const uint8_t*)ycc.p[c]; p.stride[c] = ycc.stride[c]; }
-  p.k_cr_g = variant ? FIX16(0.714136286) : FIX16(0.71414);
-  p.k_cb_g = variant ? FIX16(0.344136286) : FIX16(0.34414);
+  ycc_green_constants(variant, &p.k_cr_g, &p.k_cb_g);
   const bool vec = (p.w % 4 == 0) && al(p.rgb_out, p.bpp == 4 ? 16 : 4) && ((size_t)p.rgb_stride_px * p.bpp) % (p.bpp == 4 ? 16 : 4) == 0 &&
                    al(p.p[0], 4) && al(p.p[1], 4) && al(p.p[2], 4) && p.stride[0] % 4 == 0 && p.stride[1] % 4 == 0 && p.stride[2] % 4 == 0;
   const uint32_t per_row = vec ? p.w / 4 : p.w;

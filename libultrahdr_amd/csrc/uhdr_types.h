@@ -459,14 +459,11 @@ hipError_t launch_idct_dequant(const int16_t* coef, int bw, int bh, const uint16
 hipError_t launch_idct_dequant_rgb(const int16_t* coef_y, const int16_t* coef_cb, const int16_t* coef_cr, int bw, int bh,
                                    const uint16_t* qt_luma_host, const uint16_t* qt_chroma_host, int variant,
                                    const ImageViewMut& rgb, hipStream_t s);
-// jpeg_upsample.hip: 4:2:0 coefficient blocks -> packed RGB888 / RGBA8888, libjpeg-turbo (0) or IJG 9 (1) chroma reconstruction
-size_t upsample420_scratch_bytes(const int bw[3], const int bh[3]);
+// jpeg_upsample.hip: 4:2:0 (vsamp 2) or 4:2:2 (vsamp 1: 2x1 / 1x1 / 1x1, the chroma grids cover ceil(w/2) x h samples) coefficient
+// blocks -> packed RGB888 / RGBA8888, libjpeg-turbo (0) or IJG 9 (1) chroma reconstruction
+size_t upsample_scratch_bytes(const int bw[3], const int bh[3]);
 hipError_t launch_idct_upsample_rgb(const int16_t* const coef[3], const int bw[3], const int bh[3], const uint16_t* const qt_host[3],
-                                    int variant, const ImageViewMut& rgb, uint8_t* chroma_scratch, hipStream_t s);
-// jpeg_upsample422.hip: the same for 4:2:2 (2x1 / 1x1 / 1x1) coefficient blocks; the chroma grids cover ceil(w/2) x h samples
-size_t upsample422_scratch_bytes(const int bw[3], const int bh[3]);
-hipError_t launch_idct_upsample_rgb422(const int16_t* const coef[3], const int bw[3], const int bh[3], const uint16_t* const qt_host[3],
-                                       int variant, const ImageViewMut& rgb, uint8_t* chroma_scratch, hipStream_t s);
+                                    int variant, int vsamp, const ImageViewMut& rgb, uint8_t* chroma_scratch, hipStream_t s);
 hipError_t launch_jpeg_rgb_to_ycc(const ImageView& rgb, const ImageViewMut& ycc, hipStream_t s);
 hipError_t launch_jpeg_ycc_to_rgb(const ImageView& ycc, const ImageViewMut& rgb, int variant, hipStream_t s);
 

@@ -551,31 +551,27 @@ class UltraHdr:
                    buf.size - hdr.scan_offset, rgb_channels, libjpeg_variant, ptrs, (C.c_uint * 3)(*hs), (C.c_uint * 3)(*vs))
         return outs[0] if rgb_channels else outs
 
-    def jpeg_decode_rgb(self, jpeg: bytes, channels: int = 4, variant: int = 0, out: np.ndarray = None) -> np.ndarray:
-        """JpegDecoderHelper::decompressImage(DECODE_TO_RGB_CS) for a baseline 4:2:0 or 4:4:4 file, entirely on the device:
-        entropy decode, IDCT, libjpeg's chroma reconstruction (variant 0: libjpeg-turbo's fancy upsampling, 1: IJG 9's
-        16x16 chroma IDCT) and ycc -> rgb.  Host bytes in, one [h, w, channels] uint8 array out (or into `out`)."""
+    def _jpeg_decode_rgb(self, fn, jpeg: bytes, channels: int, variant: int, out: np.ndarray) -> np.ndarray:
         hdr = self.jpeg_parse(jpeg)
         sc = hdr.scan
         buf = np.frombuffer(jpeg, dtype=np.uint8)
         out = np.empty((sc.h, sc.w, channels), dtype=np.uint8) if out is None else out
         assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.shape[0] >= sc.h and out.shape[2] == channels
-        self._call(False, self.lib.uhdr_hip_jpeg_decode_rgb, self.ctx.handle, C.byref(hdr), C.c_void_p(buf.ctypes.data + hdr.scan_offset),
+        self._call(False, fn, self.ctx.handle, C.byref(hdr), C.c_void_p(buf.ctypes.data + hdr.scan_offset),
                    buf.size - hdr.scan_offset, channels, variant, C.c_void_p(out.ctypes.data), out.shape[1])
         return out
+
+    def jpeg_decode_rgb(self, jpeg: bytes, channels: int = 4, variant: int = 0, out: np.ndarray = None) -> np.ndarray:
+        """JpegDecoderHelper::decompressImage(DECODE_TO_RGB_CS) for a baseline 4:2:0 or 4:4:4 file, entirely on the device:
+        entropy decode, IDCT, libjpeg's chroma reconstruction (variant 0: libjpeg-turbo's fancy upsampling, 1: IJG 9's
+        16x16 chroma IDCT) and ycc -> rgb.  Host bytes in, one [h, w, channels] uint8 array out (or into `out`)."""
+        return self._jpeg_decode_rgb(self.lib.uhdr_hip_jpeg_decode_rgb, jpeg, channels, variant, out)
 
     def jpeg_decode_rgb_any(self, jpeg: bytes, channels: int = 4, variant: int = 0, out: np.ndarray = None) -> np.ndarray:
         """jpeg_decode_rgb for every sampling the device rebuilds (uhdr_hip_jpeg_decode_rgb_any): 4:4:4 and 4:2:0 files as
         jpeg_decode_rgb decodes them, 4:2:2 files with libjpeg's h2v1 chroma reconstruction (variant 0: libjpeg-turbo's fancy
         upsampling, 1: IJG 9's 16x8 chroma IDCT).  Host bytes in, one [h, w, channels] uint8 array out (or into `out`)."""
-        hdr = self.jpeg_parse(jpeg)
-        sc = hdr.scan
-        buf = np.frombuffer(jpeg, dtype=np.uint8)
-        out = np.empty((sc.h, sc.w, channels), dtype=np.uint8) if out is None else out
-        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.shape[0] >= sc.h and out.shape[2] == channels
-        self._call(False, self.lib.uhdr_hip_jpeg_decode_rgb_any, self.ctx.handle, C.byref(hdr), C.c_void_p(buf.ctypes.data + hdr.scan_offset),
-                   buf.size - hdr.scan_offset, channels, variant, C.c_void_p(out.ctypes.data), out.shape[1])
-        return out
+        return self._jpeg_decode_rgb(self.lib.uhdr_hip_jpeg_decode_rgb_any, jpeg, channels, variant, out)
 
     def jpeg_encode(self, planes, w: int, h: int, sampling, qt_luma, qt_chroma, rgb_channels: int = 0) -> bytes:
         """JpegEncoderHelper::compressImage on the device, Huffman pass included (restart intervals of 64 // blocks-per-MCU
@@ -683,39 +679,33 @@ class UltraHdr:
                    ql, qc, libjpeg_variant, C.byref(dst.raw))
         return dst
 
+    def _idct_upsample_rgb(self, fn, chroma_grid, coefs, qts, w: int, h: int, fmt, libjpeg_variant: int, dst: Image) -> Image:
+        import torch
+
+        assert all(c.is_cuda and c.dtype == torch.int16 and c.is_contiguous() for c in coefs)
+        assert tuple(coefs[0].shape) == ((h + 7) // 8, (w + 7) // 8, 64)
+        assert all(tuple(c.shape) == (*chroma_grid, 64) for c in coefs[1:])
+        q = [(C.c_uint16 * 64)(*[int(v) for v in t]) for t in qts]
+        if dst is None:
+            dst = Image(fmt, w, h, align=64, device=str(coefs[0].device))
+        self._call(True, fn, self.ctx.handle, *[C.c_void_p(c.data_ptr()) for c in coefs], w, h, *q, libjpeg_variant, C.byref(dst.raw))
+        return dst
+
     def idct_upsample_rgb(self, coefs, qts, w: int, h: int, fmt=A.UHDR_IMG_FMT_32bppRGBA8888, libjpeg_variant: int = 0,
                           dst: Image = None) -> Image:
         """A 4:2:0 image straight from its coefficients (uhdr_hip_idct_upsample_rgb_dev): three int16 CUDA tensors on
         libjpeg's width_in_blocks grids -- [ceil(h/8), ceil(w/8), 64] luma, [ceil(h/16), ceil(w/16), 64] per chroma
         component -- and three natural-order tables -> packed RGB888 / RGBA8888 device image, stream-ordered."""
-        import torch
-
-        assert all(c.is_cuda and c.dtype == torch.int16 and c.is_contiguous() for c in coefs)
-        assert tuple(coefs[0].shape) == ((h + 7) // 8, (w + 7) // 8, 64)
-        assert all(tuple(c.shape) == ((h + 15) // 16, (w + 15) // 16, 64) for c in coefs[1:])
-        q = [(C.c_uint16 * 64)(*[int(v) for v in t]) for t in qts]
-        if dst is None:
-            dst = Image(fmt, w, h, align=64, device=str(coefs[0].device))
-        self._call(True, self.lib.uhdr_hip_idct_upsample_rgb_dev, self.ctx.handle, *[C.c_void_p(c.data_ptr()) for c in coefs], w, h,
-                   *q, libjpeg_variant, C.byref(dst.raw))
-        return dst
+        return self._idct_upsample_rgb(self.lib.uhdr_hip_idct_upsample_rgb_dev, ((h + 15) // 16, (w + 15) // 16), coefs, qts, w, h, fmt,
+                                       libjpeg_variant, dst)
 
     def idct_upsample_rgb422(self, coefs, qts, w: int, h: int, fmt=A.UHDR_IMG_FMT_32bppRGBA8888, libjpeg_variant: int = 0,
                              dst: Image = None) -> Image:
         """A 4:2:2 image straight from its coefficients (uhdr_hip_idct_upsample_rgb422_dev): three int16 CUDA tensors on
         libjpeg's width_in_blocks grids -- [ceil(h/8), ceil(w/8), 64] luma, [ceil(h/8), ceil(ceil(w/2)/8), 64] per chroma
         component -- and three natural-order tables -> packed RGB888 / RGBA8888 device image, stream-ordered."""
-        import torch
-
-        assert all(c.is_cuda and c.dtype == torch.int16 and c.is_contiguous() for c in coefs)
-        assert tuple(coefs[0].shape) == ((h + 7) // 8, (w + 7) // 8, 64)
-        assert all(tuple(c.shape) == ((h + 7) // 8, ((w + 1) // 2 + 7) // 8, 64) for c in coefs[1:])
-        q = [(C.c_uint16 * 64)(*[int(v) for v in t]) for t in qts]
-        if dst is None:
-            dst = Image(fmt, w, h, align=64, device=str(coefs[0].device))
-        self._call(True, self.lib.uhdr_hip_idct_upsample_rgb422_dev, self.ctx.handle, *[C.c_void_p(c.data_ptr()) for c in coefs], w, h,
-                   *q, libjpeg_variant, C.byref(dst.raw))
-        return dst
+        return self._idct_upsample_rgb(self.lib.uhdr_hip_idct_upsample_rgb422_dev, ((h + 7) // 8, ((w + 1) // 2 + 7) // 8), coefs, qts, w, h,
+                                       fmt, libjpeg_variant, dst)
 
     def jpeg_rgb_to_ycc(self, rgb: Image) -> Image:
         """libjpeg's JCS_RGB -> YCbCr (what happens to a 3-channel gain map inside jpeg_write_scanlines):

@@ -1,5 +1,5 @@
-"""The 4:2:0 / 4:2:2 -> RGB decode on the device (uhdr_hip_idct_upsample_rgb_dev, jpeg_upsample.hip;
-uhdr_hip_idct_upsample_rgb422_dev, jpeg_upsample422.hip) at 4K and 8K, next to the 4:4:4 idct_dequant_rgb_kernel, the
+"""The 4:2:0 / 4:2:2 -> RGB decode on the device (uhdr_hip_idct_upsample_rgb_dev, uhdr_hip_idct_upsample_rgb422_dev: one kernel
+template in jpeg_upsample.hip, idct_upsample_rgb_kernel<BPP, VARIANT, VSAMP>) at 4K and 8K, next to the 4:4:4 idct_dequant_rgb_kernel, the
 whole-file entry (uhdr_hip_jpeg_decode_rgb / _rgb_any), and uhdr_decode to SRGB / RGBA8888 through the drop-in libuhdr.so with
 and without GPU acceleration.
 
@@ -224,10 +224,12 @@ def _kernel_trace(outdir, iters, sampling="420", sizes=tuple(SIZES)):
                         std_us=float(v.std()) / 1e3, ns_per_mpx=ns / (w * h / 1e6), alg_bytes_per_px=in_bytes + ch,
                         frac_8tbs=(in_bytes + ch) * w * h / (ns * 1e-9) / PEAK)
 
+        # the rows keep the labels of the time when 4:2:2 had a kernel of its own (profiles/srgb422_decode_times.json); a
+        # library of that time is still found by those names, so that it can be timed next to a current one
         for ch in (4, 3):
-            for kname, in_bytes in (("idct_upsample_rgb_kernel", 3), ("idct_upsample_rgb422_kernel", 4)):
+            for kname, vsamp, in_bytes in (("idct_upsample_rgb_kernel", 2, 3), ("idct_upsample_rgb422_kernel", 1, 4)):
                 for variant in (0, 1):
-                    v = find(kname, ch, variant)
+                    v = find("idct_upsample_rgb_kernel", ch, variant, vsamp) or find(kname, ch, variant)
                     if v is not None:
                         rows.append(row(f"{kname}<{ch},{variant}>" + (" + 2 x idct_dequant_kernel" if variant == 0 else ""), v, ch, in_bytes))
             v = find("idct_dequant_rgb_kernel", ch)
