@@ -27,7 +27,7 @@
  *   uhdr_hip_encode_api0_fused_dev (toneMap + generateGainMap + convert_raw_input_to_ycbcr in one pass),
  *   uhdr_hip_fdct_quant_rgb_dev (colour conversion + FDCT of a 3-channel map in one pass),
  *   uhdr_hip_idct_dequant_rgb_dev (its decode-side mirror: dequant + IDCT + colour conversion in one pass),
- *   uhdr_hip_apply_gainmap_coef_dev (applyGainMap on a base image still in coefficient form: IDCT inside the kernel),
+ *   uhdr_hip_apply_gainmap_coef_dev / _coef422_dev (applyGainMap on a base image still in coefficient form: IDCT inside the kernel),
  *   uhdr_hip_huffman_encode_dev + uhdr_hip_jpeg_assemble (baseline Huffman entropy coding, without restart markers or one
  *   restart interval per wavefront, and the file wrapper around it), uhdr_hip_huffman_decode_dev (its inverse: the
  *   self-synchronising parallel decoder, or one interval per lane), uhdr_hip_jpeg_parse (host: the headers of a
@@ -458,6 +458,22 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_coef_dev(uhdr_hip_ctx_t* ctx,
                                                   uhdr_color_transfer_t output_ct,
                                                   uhdr_img_fmt_t output_format, float max_display_boost,
                                                   uhdr_raw_image_t* dest);
+/* uhdr_hip_apply_gainmap_coef422_dev: arguments as uhdr_hip_apply_gainmap_coef_dev; the base image is a 4:2:2 frame (sampling
+ * factors 2x1 / 1x1 / 1x1, what most cameras write): luma on a ceil(w/8) x ceil(h/8) block grid, each chroma component on a
+ * ceil(ceil(w/2)/8) x ceil(h/8) one (UHDR_CODEC_INVALID_PARAM for any other grid -- a uhdr_hip_jpeg_coefficients_t cannot say
+ * which sampling a small grid belongs to, hence the entry point of its own).  A 128 x 16 pixel tile is then 32 + 16 + 16 blocks
+ * (4 B/px of coefficients in instead of 4 in + 2 out + 2 in over four launches), and each pixel row reads its own chroma row.
+ * Result == uhdr_hip_idct_dequant_dev x 3 followed by uhdr_hip_apply_gainmap_dev on the UHDR_IMG_FMT_16bppYCbCr422 image, bit
+ * for bit; the same cases covered, UHDR_CODEC_UNSUPPORTED_FEATURE otherwise. */
+uhdr_error_info_t uhdr_hip_apply_gainmap_coef422_dev(uhdr_hip_ctx_t* ctx,
+                                                     const uhdr_hip_jpeg_coefficients_t* base,
+                                                     unsigned int w, unsigned int h,
+                                                     uhdr_color_gamut_t base_cg,
+                                                     const uhdr_raw_image_t* gainmap_img,
+                                                     const uhdr_gainmap_metadata_t* gainmap_metadata,
+                                                     uhdr_color_transfer_t output_ct,
+                                                     uhdr_img_fmt_t output_format, float max_display_boost,
+                                                     uhdr_raw_image_t* dest);
 
 /* ---- JPEG entropy stage (the step after uhdr_hip_fdct_quant) ---------------------------------
  * Baseline Huffman coding of quantized coefficient blocks with the Annex K tables -- what libjpeg does behind
@@ -750,7 +766,8 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans(uhdr_hip_ctx_t* ctx, const uhdr_raw
  * headers (uhdr_hip_jpeg_parse, or filled by the caller: scan geometry, DQT, DHT -- all zeros selects the Annex K tables; scan.coef is ignored) and their entropy-coded
  * bytes in device memory (between the SOS header and the marker that ends them) -> both scans entropy-decoded concurrently ->
  * the gain map's dequant + IDCT (+ ycc -> rgb, alpha 255, for a three-channel map) -> applyGainMap (base image's dequant + IDCT inside
- * the kernel) -> dest (device image).  base: a 4:2:0 three-component scan; map: one component, or three at 4:4:4.  base_cg / map_cg:
+ * the kernel) -> dest (device image).  base: a 4:2:0 or 4:2:2 three-component scan (2x2 or 2x1 / 1x1 / 1x1; any other sampling is
+ * UHDR_CODEC_UNSUPPORTED_FEATURE); map: one component, or three at 4:4:4.  base_cg / map_cg:
  * what the decoded images' uhdr_raw_image_t::cg would carry (the ICC profile's gamut; the gain map's from the metadata's use_base_cg
  * logic upstream); libjpeg_variant: the ycc -> rgb constants of a three-channel map, as for uhdr_hip_jpeg_ycc_to_rgb (0: libjpeg-turbo, which
  * the reference pins).  The entropy stage is synchronous; the two sample-domain launches behind it are only enqueued. */

@@ -108,6 +108,20 @@ class UltraHdr {
     return uhdr_hip_apply_gainmap(mCtx, sdr_intent, gainmap_img, gainmap_metadata, output_ct, output_format, max_display_boost, dest);
   }
 
+  // applyGainMap on a base image still in coefficient form (device pointers; gainmap_img and dest are device images): the
+  // dequantize + IDCT stage runs inside the kernel.  sampling422: the coefficients are a 4:2:2 frame's, not a 4:2:0 one's.
+  uhdr_error_info_t applyGainMapFromCoefficients(const uhdr_hip_jpeg_coefficients_t* base, unsigned int w, unsigned int h,
+                                                 uhdr_color_gamut_t base_cg, uhdr_raw_image_t* gainmap_img,
+                                                 uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_color_transfer_t output_ct,
+                                                 uhdr_img_fmt_t output_format, float max_display_boost, uhdr_raw_image_t* dest,
+                                                 bool sampling422 = false) {
+    if (!mCtx) return mCreateStatus;
+    return sampling422 ? uhdr_hip_apply_gainmap_coef422_dev(mCtx, base, w, h, base_cg, gainmap_img, gainmap_metadata, output_ct, output_format,
+                                                            max_display_boost, dest)
+                       : uhdr_hip_apply_gainmap_coef_dev(mCtx, base, w, h, base_cg, gainmap_img, gainmap_metadata, output_ct, output_format,
+                                                         max_display_boost, dest);
+  }
+
   uhdr_error_info_t convertYuv(uhdr_raw_image_t* image, uhdr_color_gamut_t src_encoding, uhdr_color_gamut_t dst_encoding) {
     if (!mCtx) return mCreateStatus;
     return uhdr_hip_convert_yuv(mCtx, image, src_encoding, dst_encoding);

@@ -1245,6 +1245,7 @@ uhdr_error_info_t uhdr_hip_jpeg_decode_rgb_any(uhdr_hip_ctx_t* c, const uhdr_hip
 // JpegR::decodeJPEGR behind its container parsing (jpegr.cpp:1469-1531) on DEVICE-resident data in ONE entry point (round 6): the two
 // JPEG streams' parsed headers + their entropy-coded bytes in HBM -> [both scans entropy-decoded concurrently] -> the gain map's
 // dequant + IDCT (+ ycc -> rgb for a three-channel map) -> applyGainMap with the base image's dequant + IDCT inside the kernel -> dest.
+// The base image is a 4:2:0 scan (the form JpegR writes) or a 4:2:2 one (a camera's file kept as the base image).
 // Only enqueues the two sample-domain launches after the (synchronous) entropy stage: dest is ready in stream order.
 uhdr_error_info_t uhdr_hip_decode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* base, const uint8_t* base_data, size_t base_bytes,
                                                  uhdr_color_gamut_t base_cg, const uhdr_hip_jpeg_header_t* map, const uint8_t* map_data, size_t map_bytes,
@@ -1257,7 +1258,8 @@ uhdr_error_info_t uhdr_hip_decode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_h
   uhdr_hip_jpeg_scan_t sb = base->scan, sm = map->scan;
   int mpr = 0, mrows = 0, bpm = 0;
   UHDR_TRY(check_scan(&sb, false, &mpr, &mrows, &bpm));
-  if (sb.num_components != 3 || sb.h_samp[0] != 2 || sb.v_samp[0] != 2 || sb.h_samp[1] != 1 || sb.v_samp[1] != 1 || sb.h_samp[2] != 1 || sb.v_samp[2] != 1)
+  const int vsamp = subsampled_vsamp(sb);  // 2: 4:2:0, 1: 4:2:2
+  if (vsamp == 0)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "decode_api1_scans takes a 4:2:0 base image (the form JpegR writes); decode the scans with uhdr_hip_jpeg_decode_scan");
   UHDR_TRY(check_scan(&sm, false, &mpr, &mrows, &bpm));
   const int nm = sm.num_components;
@@ -1315,7 +1317,8 @@ uhdr_error_info_t uhdr_hip_decode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_h
     bc.blocks_h[i] = sb.blocks_h[i];
     memcpy(bc.qtable[i], base->qtable[i], sizeof bc.qtable[i]);
   }
-  uhdr_error_info_t ap = uhdr_hip_apply_gainmap_coef_dev(c, &bc, sb.w, sb.h, base_cg, &gm, md, output_ct, output_format, max_display_boost, dest);
+  uhdr_error_info_t ap = vsamp == 2 ? uhdr_hip_apply_gainmap_coef_dev(c, &bc, sb.w, sb.h, base_cg, &gm, md, output_ct, output_format, max_display_boost, dest)
+                                    : uhdr_hip_apply_gainmap_coef422_dev(c, &bc, sb.w, sb.h, base_cg, &gm, md, output_ct, output_format, max_display_boost, dest);
   if (ap.error_code != UHDR_CODEC_UNSUPPORTED_FEATURE) return ap;
   // a geometry the coefficient-input kernel does not take: the planes after all (three IDCT launches), then the operator
   size_t ppitch[3], poff[3], total = 0;
@@ -1327,7 +1330,7 @@ uhdr_error_info_t uhdr_hip_decode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_h
   UHDR_TRY(ensure(c->jpg[0], total));
   uhdr_raw_image_t bi;
   memset(&bi, 0, sizeof bi);
-  bi.fmt = UHDR_IMG_FMT_12bppYCbCr420;
+  bi.fmt = vsamp == 2 ? UHDR_IMG_FMT_12bppYCbCr420 : UHDR_IMG_FMT_16bppYCbCr422;
   bi.cg = base_cg;
   bi.ct = UHDR_CT_SRGB;
   bi.range = UHDR_CR_FULL_RANGE;

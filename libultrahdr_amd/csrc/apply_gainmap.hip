@@ -430,11 +430,14 @@ struct QuadRaw {
 // columns, weight-table column, edge flags) is therefore loop invariant and lives in VGPRs;
 // everything that depends on the row is wave-uniform and is computed on the scalar unit.
 //
-// SRC 1 (BASE 0 only): the base image arrives as JPEG coefficient blocks (p.coef_src, what jpeg_read_coefficients()
+// SRC 1 (BASE 0 / 3): the base image arrives as JPEG coefficient blocks (p.coef_src, what jpeg_read_coefficients()
 // yields) and never exists as planes in HBM.  A wave then owns 128 x 16 pixel tiles (one 4:2:0 MCU row of sixteen
 // luma blocks): it dequantizes and inverse-transforms the tile's 32 + 8 + 8 blocks into its private LDS tile
 // (idct_core.h, six eight-block passes) and feeds the same per-quad arithmetic from there; the gain map is still
 // read from memory.  3 B/px of coefficients in instead of 3 in + 1.5 out + 1.5 in over four launches.
+// A 4:2:2 image (BASE 3) has two chroma block rows per tile: 32 + 16 + 16 blocks, eight passes (Y x 4, Cb x 2, Cr x 2), a
+// chroma tile of 16 rows x 64 bytes per component, and each row of a quad reads its own chroma row.  4 B/px in instead of
+// 4 in + 2 out + 2 in.
 // Workgroup size: 256 for the linear F16 output (8 workgroups per CU share nothing but 14 KB of tables); 1024 for the
 // HLG / PQ outputs, whose output-code bucket table is 41 / 17 KB -- sixteen waves share one copy and two such
 // workgroups (32 waves) still fit a CU's 160 KB.
@@ -454,7 +457,7 @@ template <int SMODE, int SRC> constexpr int quad_sgprs() { return (SMODE == 0 &&
 #endif
 template <int OUT, int MAPFMT, int SMODE, int BASE, int SRC = 0>
 __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
-  static_assert(SRC == 0 || BASE == 0, "coefficient input is a 4:2:0 base image");
+  static_assert(SRC == 0 || BASE == 0 || BASE == 3, "coefficient input is a 4:2:0 or a 4:2:2 base image");
   constexpr int BLK = quad_block<OUT>();
   constexpr int NCH = (MAPFMT == 0) ? 1 : 3;
   constexpr int BPP = (MAPFMT == 0) ? 1 : (MAPFMT == 1 ? 3 : 4);
@@ -643,6 +646,7 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
     // scalar row offset (SGPR) + per-lane column offset (VGPR, loop invariant), added by the memory pipeline
     if constexpr (SRC == 1) {  // luma / chroma come from the wave's LDS tile (filled in by the tile loop)
       r.y0 = r.y1 = r.u = r.v = 0;
+      if constexpr (BASE == 3) r.c[0] = r.c[1] = r.c[2] = r.c[3] = 0;
     } else if constexpr (BASE == 2) {  // packed RGBA8888: two pixels (8 bytes) per row
       const uint32_t prow = y * sy * 4;
       const uint2 a = ld_u64(ry, xc * 4, prow), b = ld_u64(ry, xc * 4, prow + sy * 4);
@@ -954,7 +958,14 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
     __shared__ int s_ws[BLK / 64][8 * 8 * 9];
     __shared__ int s_q[3][64];
     __shared__ __attribute__((aligned(8))) uint8_t s_yt[BLK / 64][16 * 128];
-    __shared__ __attribute__((aligned(8))) uint8_t s_ct[BLK / 64][2][8 * 64];
+    constexpr int CROWS = BASE == 3 ? 16 : 8;  // chroma rows of a tile: 4:2:2 chroma is not subsampled vertically
+    constexpr int NU = BASE == 3 ? 8 : 6;      // eight-block units of a tile
+    __shared__ __attribute__((aligned(8))) uint8_t s_ct[BLK / 64][2][CROWS * 64];
+    // one workgroup's tables and tiles must fit a CU's LDS (the 768-thread HLG / PQ workgroups carry twelve tiles next to the
+    // output-code buckets)
+    static_assert(sizeof s_srgb + sizeof s_gain + sizeof s_u8f + sizeof s_tap + sizeof s_fac + sizeof s_cv + sizeof s_cu + sizeof s_code + sizeof s_idw +
+                      sizeof s_ws + sizeof s_q + sizeof s_yt + sizeof s_ct <= 160 * 1024,
+                  "the coefficient-input workgroup exceeds the 160 KB of LDS of a CU");
     const CoefSrc* __restrict__ cs = p.coef_src;
     if (tid < 192) s_q[tid >> 6][tid & 63] = cs->q[tid >> 6][tid & 63];
     __syncthreads();
@@ -973,9 +984,10 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
     auto tiles = [&](auto GM) {
     for (uint32_t t = wave; t < ntiles; t += nwaves) {
       const uint32_t ty = t / tiles_x, tx = t - ty * tiles_x;
-      // the tile's six eight-block units: Y rows 2ty, 2ty+1 x two halves, Cb, Cr (all loads issued up front)
-      int v[6][8];
-      int big[6] = {0, 0, 0, 0, 0, 0};
+      // the tile's eight-block units: Y rows 2ty, 2ty+1 x two halves, then Cb, Cr (4:2:0) or Cb rows 2ty, 2ty+1, Cr rows 2ty,
+      // 2ty+1 (4:2:2) (all loads issued up front)
+      int v[NU][8];
+      int big[NU] = {};
       {
         int q[8];
 #pragma unroll
@@ -987,23 +999,45 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
         }
 #pragma unroll
         for (int c = 0; c < 8; c++) q[c] = s_q[1][rr * 8 + c];
-        idct::load_dequant_row(ccb, bw1, (int)ty, (int)(tx * 8) + rb, rr, q, v[4], big[4], (int)ty < bh1);
+        if constexpr (BASE == 3) {
+#pragma unroll
+          for (int k = 0; k < 2; k++) {
+            const int by = (int)(2 * ty) + k;
+            idct::load_dequant_row(ccb, bw1, by, (int)(tx * 8) + rb, rr, q, v[4 + k], big[4 + k], by < bh1);
+          }
+        } else {
+          idct::load_dequant_row(ccb, bw1, (int)ty, (int)(tx * 8) + rb, rr, q, v[4], big[4], (int)ty < bh1);
+        }
 #pragma unroll
         for (int c = 0; c < 8; c++) q[c] = s_q[2][rr * 8 + c];
-        idct::load_dequant_row(ccr, bw2, (int)ty, (int)(tx * 8) + rb, rr, q, v[5], big[5], (int)ty < bh2);
+        if constexpr (BASE == 3) {
+#pragma unroll
+          for (int k = 0; k < 2; k++) {
+            const int by = (int)(2 * ty) + k;
+            idct::load_dequant_row(ccr, bw2, by, (int)(tx * 8) + rb, rr, q, v[6 + k], big[6 + k], by < bh2);
+          }
+        } else {
+          idct::load_dequant_row(ccr, bw2, (int)ty, (int)(tx * 8) + rb, rr, q, v[5], big[5], (int)ty < bh2);
+        }
       }
       const uint32_t xraw = tx * 128 + lane * 2;
       const bool lane_ok = xraw < p.sdr.w;
       col[0] = make_col(min(xraw, p.sdr.w - 2));
       Raw a = fetch(ty * 8, H0{});  // the first quad row's gain-map bytes are in flight during the transforms
 #pragma unroll
-      for (int u = 0; u < 6; u++) {
+      for (int u = 0; u < NU; u++) {
         uint32_t sm8[8];
         idct::idct_wave(ws, v[u], big[u], rr, rb, sm8);
         const uint32_t lo = sm8[0] | (sm8[1] << 8) | (sm8[2] << 16) | (sm8[3] << 24);
         const uint32_t hi = sm8[4] | (sm8[5] << 8) | (sm8[6] << 16) | (sm8[7] << 24);
-        uint8_t* d = (u < 4) ? yt + ((u >> 1) * 8 + rr) * 128 + ((u & 1) * 8 + rb) * 8
-                             : (u == 4 ? cbt : crt) + rr * 64 + rb * 8;
+        uint8_t* d;
+        if constexpr (BASE == 3) {
+          d = (u < 4) ? yt + ((u >> 1) * 8 + rr) * 128 + ((u & 1) * 8 + rb) * 8
+                      : (u < 6 ? cbt : crt) + ((u & 1) * 8 + rr) * 64 + rb * 8;
+        } else {
+          d = (u < 4) ? yt + ((u >> 1) * 8 + rr) * 128 + ((u & 1) * 8 + rb) * 8
+                      : (u == 4 ? cbt : crt) + rr * 64 + rb * 8;
+        }
         *(uint2*)d = make_uint2(lo, hi);
       }
       __builtin_amdgcn_wave_barrier();
@@ -1015,8 +1049,16 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
         if (qr < 7) nxt = fetch(qy + 1, H0{});
         a.y0 = *(const uint16_t*)(yt + (2 * qr) * 128 + lane * 2);
         a.y1 = *(const uint16_t*)(yt + (2 * qr + 1) * 128 + lane * 2);
-        a.u = cbt[qr * 64 + lane];
-        a.v = crt[qr * 64 + lane];
+        if constexpr (BASE == 3) {  // as fetch fills a 4:2:2 quad: row 0's chroma sample in u / v, row 1's in c[2] / c[3]
+          a.u = cbt[(2 * qr) * 64 + lane];
+          a.v = crt[(2 * qr) * 64 + lane];
+          a.c[2] = cbt[(2 * qr + 1) * 64 + lane];
+          a.c[3] = crt[(2 * qr + 1) * 64 + lane];
+          a.c[0] = a.c[1] = 0;
+        } else {
+          a.u = cbt[qr * 64 + lane];
+          a.v = crt[qr * 64 + lane];
+        }
         store_ok = lane_ok && (qy < qh);
         process(a, H0{}, GM);
         a = nxt;
@@ -1138,10 +1180,10 @@ hipError_t launch_quad(const ApplyParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 // coefficient input (SRC 1): resident workgroups, waves stride over the 128 x 16 pixel tiles
-template <int OUT, int MAPFMT, int SMODE>
+template <int OUT, int MAPFMT, int SMODE, int BASE>
 hipError_t launch_quad_coef(const ApplyParams& p, hipStream_t s) {
   constexpr int BLK = quad_block<OUT>();
-  static const int resident = resident_blocks(apply_quad_kernel_s96<OUT, MAPFMT, SMODE, 0, 1>, BLK, 96);
+  static const int resident = resident_blocks(apply_quad_kernel_s96<OUT, MAPFMT, SMODE, BASE, 1>, BLK, 96);
   const uint32_t ntiles = ((p.sdr.w + 127) / 128) * ((p.sdr.h + 15) / 16);
   uint32_t grid = (ntiles + BLK / 64 - 1) / (BLK / 64);
   if (grid > (uint32_t)resident) grid = (uint32_t)resident;
@@ -1149,19 +1191,27 @@ hipError_t launch_quad_coef(const ApplyParams& p, hipStream_t s) {
   q.n_frames = 1;
   q.row_groups = 1;
   q.tiles_per_wave = 0;
-  hipLaunchKernelGGL((apply_quad_kernel_s96<OUT, MAPFMT, SMODE, 0, 1>), dim3(grid), dim3(BLK), 0, s, q);
+  hipLaunchKernelGGL((apply_quad_kernel_s96<OUT, MAPFMT, SMODE, BASE, 1>), dim3(grid), dim3(BLK), 0, s, q);
   return hipGetLastError();
 }
-template <int OUT, int MAPFMT>
+template <int OUT, int MAPFMT, int BASE>
 hipError_t launch_quad_coef_s(const ApplyParams& p, int smode, hipStream_t s) {
-  return smode == 0 ? launch_quad_coef<OUT, MAPFMT, 0>(p, s) : launch_quad_coef<OUT, MAPFMT, 1>(p, s);
+  return smode == 0 ? launch_quad_coef<OUT, MAPFMT, 0, BASE>(p, s) : launch_quad_coef<OUT, MAPFMT, 1, BASE>(p, s);
 }
-template <int OUT>
+template <int OUT, int BASE>
 hipError_t launch_quad_coef_m(const ApplyParams& p, int mapfmt, int smode, hipStream_t s) {
   switch (mapfmt) {
-    case 0: return launch_quad_coef_s<OUT, 0>(p, smode, s);
-    case 1: return launch_quad_coef_s<OUT, 1>(p, smode, s);
-    default: return launch_quad_coef_s<OUT, 2>(p, smode, s);
+    case 0: return launch_quad_coef_s<OUT, 0, BASE>(p, smode, s);
+    case 1: return launch_quad_coef_s<OUT, 1, BASE>(p, smode, s);
+    default: return launch_quad_coef_s<OUT, 2, BASE>(p, smode, s);
+  }
+}
+template <int BASE>
+hipError_t launch_quad_coef_o(const ApplyParams& p, int out, int mapfmt, int smode, hipStream_t s) {
+  switch (out) {
+    case 0: return launch_quad_coef_m<0, BASE>(p, mapfmt, smode, s);
+    case 1: return launch_quad_coef_m<1, BASE>(p, mapfmt, smode, s);
+    default: return launch_quad_coef_m<2, BASE>(p, mapfmt, smode, s);
   }
 }
 
@@ -1232,18 +1282,17 @@ int apply_quad_mode(const ApplyParams& p) {
   return -1;
 }
 
-// Base image in coefficient form (p.coef_src, a device CoefSrc; p.sdr carries the geometry of the 4:2:0 image the
-// coefficients decode to).  Only the quad kernel has this input: hipErrorInvalidValue when its contract does not hold.
+// Base image in coefficient form (p.coef_src, a device CoefSrc; p.sdr carries the geometry and the sampling -- 4:2:0 or
+// 4:2:2 -- of the image the coefficients decode to).  Only the quad kernel has this input: hipErrorInvalidValue when its
+// contract does not hold.
 hipError_t launch_apply_gainmap_coef(const ApplyParams& p, hipStream_t s) {
   const int out = p.out_ct == UHDR_CT_LINEAR ? 0 : (p.out_ct == UHDR_CT_HLG ? 1 : 2);
   const int mapfmt = p.gm.fmt == UHDR_IMG_FMT_8bppYCbCr400 ? 0 : (p.gm.fmt == UHDR_IMG_FMT_24bppRGB888 ? 1 : 2);
   const int smode = apply_quad_mode(p);
-  if (smode < 0 || p.sdr.fmt != UHDR_IMG_FMT_12bppYCbCr420 || !p.coef_src || p.n_frames > 1) return hipErrorInvalidValue;
-  switch (out) {
-    case 0: return launch_quad_coef_m<0>(p, mapfmt, smode, s);
-    case 1: return launch_quad_coef_m<1>(p, mapfmt, smode, s);
-    default: return launch_quad_coef_m<2>(p, mapfmt, smode, s);
-  }
+  if (smode < 0 || !p.coef_src || p.n_frames > 1) return hipErrorInvalidValue;
+  if (p.sdr.fmt == UHDR_IMG_FMT_12bppYCbCr420) return launch_quad_coef_o<0>(p, out, mapfmt, smode, s);
+  if (p.sdr.fmt == UHDR_IMG_FMT_16bppYCbCr422) return launch_quad_coef_o<3>(p, out, mapfmt, smode, s);
+  return hipErrorInvalidValue;
 }
 
 // Picks the quad kernel when its layout assumptions hold, otherwise the generic one.

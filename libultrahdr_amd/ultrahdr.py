@@ -323,7 +323,8 @@ class UltraHdr:
                         gainmap_metadata: A.GainmapMetadata, output_ct: int, output_format: int, max_display_boost: float, dest: Image,
                         libjpeg_variant: int = 0):
         """JpegR::decodeJPEGR behind its container parsing (jpegr.cpp:1469-1531) on device data in ONE C call
-        (uhdr_hip_decode_api1_scans_dev): both scans entropy-decoded, the map's IDCT, applyGainMap with the base image's IDCT inside."""
+        (uhdr_hip_decode_api1_scans_dev): both scans entropy-decoded, the map's IDCT, applyGainMap with the base image's IDCT inside.
+        The base scan is 4:2:0 or 4:2:2 (base_hdr says which)."""
         assert base_data.is_cuda and map_data.is_cuda and _is_dev(dest)
         self._call(True, self.lib.uhdr_hip_decode_api1_scans_dev, self.ctx.handle, C.byref(base_hdr), C.c_void_p(base_data.data_ptr()), int(base_data.numel()), base_cg,
                    C.byref(map_hdr), C.c_void_p(map_data.data_ptr()), int(map_data.numel()), map_cg, libjpeg_variant, C.byref(gainmap_metadata), output_ct, output_format,
@@ -346,18 +347,22 @@ class UltraHdr:
 
     def applyGainMapFromCoefficients(self, coefs, qtables, w: int, h: int, base_cg: int, gainmap_img: Image,
                                      gainmap_metadata: A.GainmapMetadata, output_ct: int, output_format: int,
-                                     max_display_boost: float, dest: Image):
-        """applyGainMap on a 4:2:0 base image still in coefficient form (what jpeg_read_coefficients() yields): coefs =
-        three int16 [blocks_h, blocks_w, 64] CUDA tensors (Y, Cb, Cr), qtables = their three quantization tables; the
-        dequantize + IDCT stage runs inside the kernel.  == idct_dequant x 3 + applyGainMap, bit for bit."""
+                                     max_display_boost: float, dest: Image, sampling: str = "420"):
+        """applyGainMap on a 4:2:0 (sampling "420") or 4:2:2 ("422": uhdr_hip_apply_gainmap_coef422_dev) base image still in
+        coefficient form (what jpeg_read_coefficients() yields): coefs = three int16 [blocks_h, blocks_w, 64] CUDA tensors
+        (Y, Cb, Cr), qtables = their three quantization tables; the dequantize + IDCT stage runs inside the kernel.
+        == idct_dequant x 3 + applyGainMap, bit for bit."""
         assert all(c.is_cuda for c in coefs) and _is_dev(gainmap_img, dest)
+        if sampling not in ("420", "422"):
+            raise ValueError(f"sampling is '420' or '422', received {sampling!r}")
+        fn = self.lib.uhdr_hip_apply_gainmap_coef_dev if sampling == "420" else self.lib.uhdr_hip_apply_gainmap_coef422_dev
         jc = A.JpegCoefficients()
         for i in range(3):
             jc.coef[i] = coefs[i].data_ptr()
             jc.blocks_h[i], jc.blocks_w[i] = int(coefs[i].shape[0]), int(coefs[i].shape[1])
             for k in range(64):
                 jc.qtable[i][k] = int(qtables[i][k])
-        self._call(True, self.lib.uhdr_hip_apply_gainmap_coef_dev, self.ctx.handle, C.byref(jc), w, h, base_cg, C.byref(gainmap_img.raw),
+        self._call(True, fn, self.ctx.handle, C.byref(jc), w, h, base_cg, C.byref(gainmap_img.raw),
                    C.byref(gainmap_metadata), output_ct, output_format, max_display_boost, C.byref(dest.raw))
 
     def applyGainMapBatch(self, sdr_intents, gainmap_imgs, gainmap_metadata: A.GainmapMetadata, output_ct: int,
