@@ -27,7 +27,7 @@
  *   uhdr_hip_encode_api0_fused_dev (toneMap + generateGainMap + convert_raw_input_to_ycbcr in one pass),
  *   uhdr_hip_fdct_quant_rgb_dev (colour conversion + FDCT of a 3-channel map in one pass),
  *   uhdr_hip_idct_dequant_rgb_dev (its decode-side mirror: dequant + IDCT + colour conversion in one pass),
- *   uhdr_hip_apply_gainmap_coef_dev / _coef422_dev (applyGainMap on a base image still in coefficient form: IDCT inside the kernel),
+ *   uhdr_hip_apply_gainmap_coef_dev / _coef422_dev / _coef444_dev (applyGainMap on a base image still in coefficient form: IDCT inside the kernel),
  *   uhdr_hip_huffman_encode_dev + uhdr_hip_jpeg_assemble (baseline Huffman entropy coding, without restart markers or one
  *   restart interval per wavefront, and the file wrapper around it), uhdr_hip_huffman_decode_dev (its inverse: the
  *   self-synchronising parallel decoder, or one interval per lane), uhdr_hip_jpeg_parse (host: the headers of a
@@ -474,6 +474,23 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_coef422_dev(uhdr_hip_ctx_t* ctx,
                                                      uhdr_color_transfer_t output_ct,
                                                      uhdr_img_fmt_t output_format, float max_display_boost,
                                                      uhdr_raw_image_t* dest);
+/* uhdr_hip_apply_gainmap_coef444_dev: arguments as uhdr_hip_apply_gainmap_coef_dev; the base image is a 4:4:4 frame (sampling
+ * factors 1x1 / 1x1 / 1x1, what editors write at high quality), the third YCbCr layout JpegR::applyGainMap takes
+ * (jpegr.cpp:1586-1638) with JpegDecoderHelper's dequantize + IDCT stage (jpegdecoderhelper.cpp:468-535) in front of it: all
+ * three components on a ceil(w/8) x ceil(h/8) block grid (UHDR_CODEC_INVALID_PARAM for any other grid).  A wave works on
+ * 128 x 8 pixel tiles, one MCU row of 16 + 16 + 16 blocks (6 B/px of coefficients in instead of 6 in + 3 out + 3 in over four
+ * launches), and each pixel reads its own chroma sample.  Result == uhdr_hip_idct_dequant_dev x 3 followed by
+ * uhdr_hip_apply_gainmap_dev on the UHDR_IMG_FMT_24bppYCbCr444 image, bit for bit; the same cases covered,
+ * UHDR_CODEC_UNSUPPORTED_FEATURE otherwise. */
+uhdr_error_info_t uhdr_hip_apply_gainmap_coef444_dev(uhdr_hip_ctx_t* ctx,
+                                                     const uhdr_hip_jpeg_coefficients_t* base,
+                                                     unsigned int w, unsigned int h,
+                                                     uhdr_color_gamut_t base_cg,
+                                                     const uhdr_raw_image_t* gainmap_img,
+                                                     const uhdr_gainmap_metadata_t* gainmap_metadata,
+                                                     uhdr_color_transfer_t output_ct,
+                                                     uhdr_img_fmt_t output_format, float max_display_boost,
+                                                     uhdr_raw_image_t* dest);
 
 /* ---- JPEG entropy stage (the step after uhdr_hip_fdct_quant) ---------------------------------
  * Baseline Huffman coding of quantized coefficient blocks with the Annex K tables -- what libjpeg does behind
@@ -782,6 +799,17 @@ uhdr_error_info_t uhdr_hip_decode_api1_scans_dev(uhdr_hip_ctx_t* ctx, const uhdr
                                                  const uint8_t* map_data, size_t map_bytes, uhdr_color_gamut_t map_cg,
                                                  int libjpeg_variant, const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t output_ct,
                                                  uhdr_img_fmt_t output_format, float max_display_boost, uhdr_raw_image_t* dest);
+/* uhdr_hip_decode_api1_scans_any_dev: arguments and behaviour as uhdr_hip_decode_api1_scans_dev (JpegR::decodeJPEGR behind its
+ * container parsing, jpegr.cpp:1469-1531) for every base image JpegR::applyGainMap takes (jpegr.cpp:1586-1638): a 1x1 / 1x1 / 1x1
+ * (4:4:4) three-component base scan goes through uhdr_hip_apply_gainmap_coef444_dev, and through three uhdr_hip_idct_dequant_dev
+ * launches into a UHDR_IMG_FMT_24bppYCbCr444 image + uhdr_hip_apply_gainmap_dev where that answers
+ * UHDR_CODEC_UNSUPPORTED_FEATURE.  4:2:0 and 4:2:2 base scans are decoded exactly as by the entry point above, which keeps refusing
+ * 4:4:4; grayscale (the reference refuses a Y400 base image too), 1x2 (4:4:0) and 4:1:1 stay UHDR_CODEC_UNSUPPORTED_FEATURE. */
+uhdr_error_info_t uhdr_hip_decode_api1_scans_any_dev(uhdr_hip_ctx_t* ctx, const uhdr_hip_jpeg_header_t* base, const uint8_t* base_data,
+                                                     size_t base_bytes, uhdr_color_gamut_t base_cg, const uhdr_hip_jpeg_header_t* map,
+                                                     const uint8_t* map_data, size_t map_bytes, uhdr_color_gamut_t map_cg,
+                                                     int libjpeg_variant, const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t output_ct,
+                                                     uhdr_img_fmt_t output_format, float max_display_boost, uhdr_raw_image_t* dest);
 
 /* ---- handing a context to its next user (round 6; what the facade's context pool calls when a codec lets go of one) --------------------
  * Forgets everything that belonged to the previous user: the device-resident image copies, a write-back error that was latched for

@@ -122,6 +122,28 @@ class UltraHdr {
                                                          max_display_boost, dest);
   }
 
+  // ... of a 4:4:4 frame (uhdr_hip_apply_gainmap_coef444_dev): all three components on the ceil(w/8) x ceil(h/8) block grid.
+  uhdr_error_info_t applyGainMapFromCoefficients444(const uhdr_hip_jpeg_coefficients_t* base, unsigned int w, unsigned int h,
+                                                    uhdr_color_gamut_t base_cg, uhdr_raw_image_t* gainmap_img,
+                                                    uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_color_transfer_t output_ct,
+                                                    uhdr_img_fmt_t output_format, float max_display_boost, uhdr_raw_image_t* dest) {
+    if (!mCtx) return mCreateStatus;
+    return uhdr_hip_apply_gainmap_coef444_dev(mCtx, base, w, h, base_cg, gainmap_img, gainmap_metadata, output_ct, output_format,
+                                              max_display_boost, dest);
+  }
+
+  // JpegR::decodeJPEGR behind its container parsing on device data in one call (uhdr_hip_decode_api1_scans_any_dev): two parsed
+  // headers + their entropy-coded bytes in device memory -> dest (device image).  The base scan is 4:2:0, 4:2:2 or 4:4:4.
+  uhdr_error_info_t decodeApi1ScansAny(const uhdr_hip_jpeg_header_t* base, const uint8_t* base_data, size_t base_bytes,
+                                       uhdr_color_gamut_t base_cg, const uhdr_hip_jpeg_header_t* map, const uint8_t* map_data,
+                                       size_t map_bytes, uhdr_color_gamut_t map_cg, uhdr_gainmap_metadata_t* gainmap_metadata,
+                                       uhdr_color_transfer_t output_ct, uhdr_img_fmt_t output_format, float max_display_boost,
+                                       uhdr_raw_image_t* dest, int libjpeg_variant = 0) {
+    if (!mCtx) return mCreateStatus;
+    return uhdr_hip_decode_api1_scans_any_dev(mCtx, base, base_data, base_bytes, base_cg, map, map_data, map_bytes, map_cg, libjpeg_variant,
+                                              gainmap_metadata, output_ct, output_format, max_display_boost, dest);
+  }
+
   uhdr_error_info_t convertYuv(uhdr_raw_image_t* image, uhdr_color_gamut_t src_encoding, uhdr_color_gamut_t dst_encoding) {
     if (!mCtx) return mCreateStatus;
     return uhdr_hip_convert_yuv(mCtx, image, src_encoding, dst_encoding);

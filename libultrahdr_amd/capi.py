@@ -221,6 +221,8 @@ _SIGS = {
                                                    _P(RawImage), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "uhdr_hip_decode_api1_scans_dev": (ErrorInfo, [C.c_void_p, _P(JpegHeader), C.c_void_p, C.c_size_t, C.c_int, _P(JpegHeader), C.c_void_p, C.c_size_t, C.c_int,
                                                    C.c_int, _P(GainmapMetadata), C.c_int, C.c_int, C.c_float, _P(RawImage)]),
+    "uhdr_hip_decode_api1_scans_any_dev": (ErrorInfo, [C.c_void_p, _P(JpegHeader), C.c_void_p, C.c_size_t, C.c_int, _P(JpegHeader), C.c_void_p, C.c_size_t, C.c_int,
+                                                       C.c_int, _P(GainmapMetadata), C.c_int, C.c_int, C.c_float, _P(RawImage)]),
     "uhdr_hip_comm_all_reduce_min_dev": (ErrorInfo, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "uhdr_hip_selftest": (ErrorInfo, [C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, _P(C.c_float), _P(C.c_ulonglong)]),
     "uhdr_hip_fdct_quant": (ErrorInfo, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, _P(C.c_uint16), C.c_void_p]),
@@ -239,6 +241,8 @@ _SIGS = {
     "uhdr_hip_apply_gainmap_coef_dev": (ErrorInfo, [C.c_void_p, _P(JpegCoefficients), C.c_uint, C.c_uint, C.c_int, _P(RawImage), _P(GainmapMetadata),
                                                     C.c_int, C.c_int, C.c_float, _P(RawImage)]),
     "uhdr_hip_apply_gainmap_coef422_dev": (ErrorInfo, [C.c_void_p, _P(JpegCoefficients), C.c_uint, C.c_uint, C.c_int, _P(RawImage), _P(GainmapMetadata),
+                                                       C.c_int, C.c_int, C.c_float, _P(RawImage)]),
+    "uhdr_hip_apply_gainmap_coef444_dev": (ErrorInfo, [C.c_void_p, _P(JpegCoefficients), C.c_uint, C.c_uint, C.c_int, _P(RawImage), _P(GainmapMetadata),
                                                        C.c_int, C.c_int, C.c_float, _P(RawImage)]),
     "uhdr_hip_huffman_encode_dev": (ErrorInfo, [C.c_void_p, _P(JpegScan), C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "uhdr_hip_huffman_decode_dev": (ErrorInfo, [C.c_void_p, _P(JpegScan), _P(HuffTables), C.c_void_p, C.c_size_t]),

@@ -201,24 +201,24 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_batch_dev(uhdr_hip_ctx_t* c, unsigned i
 
 // applyGainMap with the base image still in coefficient form: JpegDecoderHelper's dequantize + IDCT stage
 // (jpegdecoderhelper.cpp:468-535) runs inside the applyGainMap kernel, the 8-bit planes never exist in memory.
-// Both samplings share this body (and the context's descriptor slots); a uhdr_hip_jpeg_coefficients_t cannot say which
-// sampling a small block grid belongs to, hence one entry point each.  vsamp: the luma vertical sampling factor, 2 (4:2:0) or 1 (4:2:2).
-static uhdr_error_info_t apply_gainmap_coef_impl(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_coefficients_t* base, unsigned int w, unsigned int h, int vsamp,
+// All three samplings share this body (and the context's descriptor slots); a uhdr_hip_jpeg_coefficients_t cannot say which
+// sampling a small block grid belongs to, hence one entry point each.  sampling: 420, 422 or 444.
+static uhdr_error_info_t apply_gainmap_coef_impl(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_coefficients_t* base, unsigned int w, unsigned int h, int sampling,
                                                  uhdr_color_gamut_t base_cg, const uhdr_raw_image_t* gm, const uhdr_gainmap_metadata_t* md,
                                                  uhdr_color_transfer_t out_ct, float max_display_boost, uhdr_raw_image_t* dest) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!base) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for the base image coefficients");
   if (w == 0 || h == 0) return err_status(UHDR_CODEC_INVALID_PARAM, "image dimensions cannot be zero, received %ux%u", w, h);
-  // the block grid of a 4:2:0 / 4:2:2 frame (jpeg_component_info::width_in_blocks / height_in_blocks)
-  const unsigned int cw = (w + 1) / 2, ch = vsamp == 2 ? (h + 1) / 2 : h;
+  // the block grid of a 4:2:0 / 4:2:2 / 4:4:4 frame (jpeg_component_info::width_in_blocks / height_in_blocks)
+  const unsigned int cw = sampling == 444 ? w : (w + 1) / 2, ch = sampling == 420 ? (h + 1) / 2 : h;
   const unsigned int want_w[3] = {(w + 7) / 8, (cw + 7) / 8, (cw + 7) / 8}, want_h[3] = {(h + 7) / 8, (ch + 7) / 8, (ch + 7) / 8};
   CoefSrc cs;
   for (int i = 0; i < 3; i++) {
     if (!base->coef[i] || ((uintptr_t)base->coef[i] & 15))
       return err_status(UHDR_CODEC_INVALID_PARAM, "coefficient buffer %d is null or not 16-byte aligned", i);
     if (base->blocks_w[i] != (int)want_w[i] || base->blocks_h[i] != (int)want_h[i])
-      return err_status(UHDR_CODEC_INVALID_PARAM, "component %d: a %dx%d block grid does not match a 4:2:%d image of %ux%u (expected %ux%u)", i,
-                        base->blocks_w[i], base->blocks_h[i], vsamp == 2 ? 0 : 2, w, h, want_w[i], want_h[i]);
+      return err_status(UHDR_CODEC_INVALID_PARAM, "component %d: a %dx%d block grid does not match a 4:%d:%d image of %ux%u (expected %ux%u)", i,
+                        base->blocks_w[i], base->blocks_h[i], sampling == 444 ? 4 : 2, sampling == 420 ? 0 : (sampling == 422 ? 2 : 4), w, h, want_w[i], want_h[i]);
     cs.coef[i] = base->coef[i];
     cs.bw[i] = base->blocks_w[i];
     cs.bh[i] = base->blocks_h[i];
@@ -231,15 +231,16 @@ static uhdr_error_info_t apply_gainmap_coef_impl(uhdr_hip_ctx_t* c, const uhdr_h
   // geometry-only view of the image the coefficients decode to (the kernel never dereferences these planes)
   uhdr_raw_image_t sdr;
   memset(&sdr, 0, sizeof sdr);
-  sdr.fmt = vsamp == 2 ? UHDR_IMG_FMT_12bppYCbCr420 : UHDR_IMG_FMT_16bppYCbCr422;
+  sdr.fmt = sampling == 420 ? UHDR_IMG_FMT_12bppYCbCr420 : (sampling == 422 ? UHDR_IMG_FMT_16bppYCbCr422 : UHDR_IMG_FMT_24bppYCbCr444);
   sdr.cg = base_cg; sdr.ct = UHDR_CT_SRGB; sdr.range = UHDR_CR_FULL_RANGE;
   sdr.w = w; sdr.h = h;
   for (int i = 0; i < 3; i++) { sdr.planes[i] = (void*)base->coef[i]; sdr.stride[i] = (unsigned int)base->blocks_w[i] * 8; }
   ApplyParams p;
   UHDR_TRY(build_apply_params(c, &sdr, gm, md, out_ct, max_display_boost, dest, 0, 0, &p));
   if (apply_quad_mode(p) < 0)
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "apply_gainmap_coef / _coef422 cover the 2x2-quad kernel's cases (even dimensions, width >= 128, 16-byte "
-                      "aligned destination rows, gain map at scale 1 or an even scale <= 8 with gamma 1); decode with idct_dequant and call apply_gainmap");
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "%s the 2x2-quad kernel's cases (even dimensions, width >= 128, 16-byte "
+                      "aligned destination rows, gain map at scale 1 or an even scale <= 8 with gamma 1); decode with idct_dequant and call apply_gainmap",
+                      sampling == 444 ? "apply_gainmap_coef444 covers" : "apply_gainmap_coef / _coef422 cover");
   constexpr unsigned int kSlots = 8;
   if (!c->d_coef_src) HIP_TRY(hipMalloc((void**)&c->d_coef_src, sizeof(CoefSrc) * kSlots));
   CoefSrc* slot = c->coef_src_last_slot;
@@ -264,7 +265,7 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_coef_dev(uhdr_hip_ctx_t* c, const uhdr_
                                                   const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct,
                                                   uhdr_img_fmt_t out_fmt, float max_display_boost, uhdr_raw_image_t* dest) {
   (void)out_fmt;
-  return apply_gainmap_coef_impl(c, base, w, h, 2, base_cg, gm, md, out_ct, max_display_boost, dest);
+  return apply_gainmap_coef_impl(c, base, w, h, 420, base_cg, gm, md, out_ct, max_display_boost, dest);
 }
 
 // The same operator on the coefficients of a 4:2:2 base image (h_samp 2x1 / 1x1 / 1x1: what most cameras write).
@@ -273,7 +274,17 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_coef422_dev(uhdr_hip_ctx_t* c, const uh
                                                      const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct,
                                                      uhdr_img_fmt_t out_fmt, float max_display_boost, uhdr_raw_image_t* dest) {
   (void)out_fmt;
-  return apply_gainmap_coef_impl(c, base, w, h, 1, base_cg, gm, md, out_ct, max_display_boost, dest);
+  return apply_gainmap_coef_impl(c, base, w, h, 422, base_cg, gm, md, out_ct, max_display_boost, dest);
+}
+
+// ... and of a 4:4:4 one (1x1 / 1x1 / 1x1: what editors write at high quality), the third YCbCr layout JpegR::applyGainMap takes
+// (jpegr.cpp:1586-1638).
+uhdr_error_info_t uhdr_hip_apply_gainmap_coef444_dev(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_coefficients_t* base, unsigned int w,
+                                                     unsigned int h, uhdr_color_gamut_t base_cg, const uhdr_raw_image_t* gm,
+                                                     const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct,
+                                                     uhdr_img_fmt_t out_fmt, float max_display_boost, uhdr_raw_image_t* dest) {
+  (void)out_fmt;
+  return apply_gainmap_coef_impl(c, base, w, h, 444, base_cg, gm, md, out_ct, max_display_boost, dest);
 }
 
 uhdr_error_info_t uhdr_hip_apply_gainmap(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr,

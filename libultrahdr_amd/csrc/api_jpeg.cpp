@@ -1247,11 +1247,13 @@ uhdr_error_info_t uhdr_hip_jpeg_decode_rgb_any(uhdr_hip_ctx_t* c, const uhdr_hip
 // dequant + IDCT (+ ycc -> rgb for a three-channel map) -> applyGainMap with the base image's dequant + IDCT inside the kernel -> dest.
 // The base image is a 4:2:0 scan (the form JpegR writes) or a 4:2:2 one (a camera's file kept as the base image).
 // Only enqueues the two sample-domain launches after the (synchronous) entropy stage: dest is ready in stream order.
-uhdr_error_info_t uhdr_hip_decode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* base, const uint8_t* base_data, size_t base_bytes,
-                                                 uhdr_color_gamut_t base_cg, const uhdr_hip_jpeg_header_t* map, const uint8_t* map_data, size_t map_bytes,
-                                                 uhdr_color_gamut_t map_cg, int libjpeg_variant, const uhdr_gainmap_metadata_t* md,
-                                                 uhdr_color_transfer_t output_ct, uhdr_img_fmt_t output_format, float max_display_boost,
-                                                 uhdr_raw_image_t* dest) {
+// allow_444 (uhdr_hip_decode_api1_scans_any_dev): a 1x1 / 1x1 / 1x1 base scan is taken as well -- the third YCbCr layout JpegR::applyGainMap
+// accepts (jpegr.cpp:1586-1638) -- where the first entry point keeps refusing it.
+static uhdr_error_info_t decode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* base, const uint8_t* base_data, size_t base_bytes,
+                                                uhdr_color_gamut_t base_cg, const uhdr_hip_jpeg_header_t* map, const uint8_t* map_data, size_t map_bytes,
+                                                uhdr_color_gamut_t map_cg, int libjpeg_variant, const uhdr_gainmap_metadata_t* md,
+                                                uhdr_color_transfer_t output_ct, uhdr_img_fmt_t output_format, float max_display_boost,
+                                                uhdr_raw_image_t* dest, bool allow_444) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!base || !base_data || !map || !map_data || !md || !dest) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument for decode_api1_scans");
   if (libjpeg_variant != 0 && libjpeg_variant != 1) return err_status(UHDR_CODEC_INVALID_PARAM, "unknown libjpeg variant %d", libjpeg_variant);
@@ -1259,8 +1261,11 @@ uhdr_error_info_t uhdr_hip_decode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_h
   int mpr = 0, mrows = 0, bpm = 0;
   UHDR_TRY(check_scan(&sb, false, &mpr, &mrows, &bpm));
   const int vsamp = subsampled_vsamp(sb);  // 2: 4:2:0, 1: 4:2:2
-  if (vsamp == 0)
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "decode_api1_scans takes a 4:2:0 base image (the form JpegR writes); decode the scans with uhdr_hip_jpeg_decode_scan");
+  bool is444 = allow_444 && sb.num_components == 3;
+  for (int i = 0; i < 3 && is444; i++) is444 = sb.h_samp[i] == 1 && sb.v_samp[i] == 1;
+  if (vsamp == 0 && !is444)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, allow_444 ? "decode_api1_scans_any takes a 4:2:0, 4:2:2 or 4:4:4 base image; decode the scans with uhdr_hip_jpeg_decode_scan"
+                                                                : "decode_api1_scans takes a 4:2:0 base image (the form JpegR writes); decode the scans with uhdr_hip_jpeg_decode_scan");
   UHDR_TRY(check_scan(&sm, false, &mpr, &mrows, &bpm));
   const int nm = sm.num_components;
   if (nm == 3 && (bpm != 3 || memcmp(map->qtable[1], map->qtable[2], sizeof map->qtable[1])))
@@ -1317,8 +1322,9 @@ uhdr_error_info_t uhdr_hip_decode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_h
     bc.blocks_h[i] = sb.blocks_h[i];
     memcpy(bc.qtable[i], base->qtable[i], sizeof bc.qtable[i]);
   }
-  uhdr_error_info_t ap = vsamp == 2 ? uhdr_hip_apply_gainmap_coef_dev(c, &bc, sb.w, sb.h, base_cg, &gm, md, output_ct, output_format, max_display_boost, dest)
-                                    : uhdr_hip_apply_gainmap_coef422_dev(c, &bc, sb.w, sb.h, base_cg, &gm, md, output_ct, output_format, max_display_boost, dest);
+  uhdr_error_info_t ap = is444      ? uhdr_hip_apply_gainmap_coef444_dev(c, &bc, sb.w, sb.h, base_cg, &gm, md, output_ct, output_format, max_display_boost, dest)
+                         : vsamp == 2 ? uhdr_hip_apply_gainmap_coef_dev(c, &bc, sb.w, sb.h, base_cg, &gm, md, output_ct, output_format, max_display_boost, dest)
+                                      : uhdr_hip_apply_gainmap_coef422_dev(c, &bc, sb.w, sb.h, base_cg, &gm, md, output_ct, output_format, max_display_boost, dest);
   if (ap.error_code != UHDR_CODEC_UNSUPPORTED_FEATURE) return ap;
   // a geometry the coefficient-input kernel does not take: the planes after all (three IDCT launches), then the operator
   size_t ppitch[3], poff[3], total = 0;
@@ -1330,7 +1336,7 @@ uhdr_error_info_t uhdr_hip_decode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_h
   UHDR_TRY(ensure(c->jpg[0], total));
   uhdr_raw_image_t bi;
   memset(&bi, 0, sizeof bi);
-  bi.fmt = vsamp == 2 ? UHDR_IMG_FMT_12bppYCbCr420 : UHDR_IMG_FMT_16bppYCbCr422;
+  bi.fmt = is444 ? UHDR_IMG_FMT_24bppYCbCr444 : (vsamp == 2 ? UHDR_IMG_FMT_12bppYCbCr420 : UHDR_IMG_FMT_16bppYCbCr422);
   bi.cg = base_cg;
   bi.ct = UHDR_CT_SRGB;
   bi.range = UHDR_CR_FULL_RANGE;
@@ -1343,6 +1349,26 @@ uhdr_error_info_t uhdr_hip_decode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_h
     bi.stride[i] = (unsigned int)ppitch[i];
   }
   return uhdr_hip_apply_gainmap_dev(c, &bi, &gm, md, output_ct, output_format, max_display_boost, dest, 0, 0);
+}
+
+uhdr_error_info_t uhdr_hip_decode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* base, const uint8_t* base_data, size_t base_bytes,
+                                                 uhdr_color_gamut_t base_cg, const uhdr_hip_jpeg_header_t* map, const uint8_t* map_data, size_t map_bytes,
+                                                 uhdr_color_gamut_t map_cg, int libjpeg_variant, const uhdr_gainmap_metadata_t* md,
+                                                 uhdr_color_transfer_t output_ct, uhdr_img_fmt_t output_format, float max_display_boost,
+                                                 uhdr_raw_image_t* dest) {
+  return decode_api1_scans_impl(c, base, base_data, base_bytes, base_cg, map, map_data, map_bytes, map_cg, libjpeg_variant, md, output_ct, output_format,
+                                max_display_boost, dest, false);
+}
+
+// The same decode for any base image JpegR::applyGainMap takes (jpegr.cpp:1586-1638): 4:2:0, 4:2:2 and 4:4:4 (what editors write
+// at high quality); grayscale, 4:4:0 and 4:1:1 stay refused.
+uhdr_error_info_t uhdr_hip_decode_api1_scans_any_dev(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* base, const uint8_t* base_data, size_t base_bytes,
+                                                     uhdr_color_gamut_t base_cg, const uhdr_hip_jpeg_header_t* map, const uint8_t* map_data, size_t map_bytes,
+                                                     uhdr_color_gamut_t map_cg, int libjpeg_variant, const uhdr_gainmap_metadata_t* md,
+                                                     uhdr_color_transfer_t output_ct, uhdr_img_fmt_t output_format, float max_display_boost,
+                                                     uhdr_raw_image_t* dest) {
+  return decode_api1_scans_impl(c, base, base_data, base_bytes, base_cg, map, map_data, map_bytes, map_cg, libjpeg_variant, md, output_ct, output_format,
+                                max_display_boost, dest, true);
 }
 
 // Host helper: a complete baseline JFIF file around entropy-coded data (marker order of jcmarker.c: SOI, APP0, DQT,

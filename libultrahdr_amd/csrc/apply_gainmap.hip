@@ -430,7 +430,7 @@ struct QuadRaw {
 // columns, weight-table column, edge flags) is therefore loop invariant and lives in VGPRs;
 // everything that depends on the row is wave-uniform and is computed on the scalar unit.
 //
-// SRC 1 (BASE 0 / 3): the base image arrives as JPEG coefficient blocks (p.coef_src, what jpeg_read_coefficients()
+// SRC 1 (BASE 0 / 3 / 1): the base image arrives as JPEG coefficient blocks (p.coef_src, what jpeg_read_coefficients()
 // yields) and never exists as planes in HBM.  A wave then owns 128 x 16 pixel tiles (one 4:2:0 MCU row of sixteen
 // luma blocks): it dequantizes and inverse-transforms the tile's 32 + 8 + 8 blocks into its private LDS tile
 // (idct_core.h, six eight-block passes) and feeds the same per-quad arithmetic from there; the gain map is still
@@ -438,6 +438,10 @@ struct QuadRaw {
 // A 4:2:2 image (BASE 3) has two chroma block rows per tile: 32 + 16 + 16 blocks, eight passes (Y x 4, Cb x 2, Cr x 2), a
 // chroma tile of 16 rows x 64 bytes per component, and each row of a quad reads its own chroma row.  4 B/px in instead of
 // 4 in + 2 out + 2 in.
+// A 4:4:4 image (BASE 1) takes 128 x 8 tiles, one MCU row of sixteen MCUs: 16 + 16 + 16 blocks, six passes again (Y, Cb, Cr x
+// two halves), three tiles of 8 rows x 128 bytes (the 3 KB per wave of 4:2:0; a 128 x 16 tile would be twelve passes, 96
+// VGPRs of coefficients in flight and 6 KB per wave), four quad rows, each reading both of its rows' chroma pairs.  6 B/px
+// in instead of 6 in + 3 out + 3 in.
 // Workgroup size: 256 for the linear F16 output (8 workgroups per CU share nothing but 14 KB of tables); 1024 for the
 // HLG / PQ outputs, whose output-code bucket table is 41 / 17 KB -- sixteen waves share one copy and two such
 // workgroups (32 waves) still fit a CU's 160 KB.
@@ -457,7 +461,7 @@ template <int SMODE, int SRC> constexpr int quad_sgprs() { return (SMODE == 0 &&
 #endif
 template <int OUT, int MAPFMT, int SMODE, int BASE, int SRC = 0>
 __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
-  static_assert(SRC == 0 || BASE == 0 || BASE == 3, "coefficient input is a 4:2:0 or a 4:2:2 base image");
+  static_assert(SRC == 0 || BASE == 0 || BASE == 1 || BASE == 3, "coefficient input is a 4:2:0, a 4:2:2 or a 4:4:4 base image");
   constexpr int BLK = quad_block<OUT>();
   constexpr int NCH = (MAPFMT == 0) ? 1 : 3;
   constexpr int BPP = (MAPFMT == 0) ? 1 : (MAPFMT == 1 ? 3 : 4);
@@ -646,7 +650,7 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
     // scalar row offset (SGPR) + per-lane column offset (VGPR, loop invariant), added by the memory pipeline
     if constexpr (SRC == 1) {  // luma / chroma come from the wave's LDS tile (filled in by the tile loop)
       r.y0 = r.y1 = r.u = r.v = 0;
-      if constexpr (BASE == 3) r.c[0] = r.c[1] = r.c[2] = r.c[3] = 0;
+      if constexpr (BASE == 3 || BASE == 1) r.c[0] = r.c[1] = r.c[2] = r.c[3] = 0;
     } else if constexpr (BASE == 2) {  // packed RGBA8888: two pixels (8 bytes) per row
       const uint32_t prow = y * sy * 4;
       const uint2 a = ld_u64(ry, xc * 4, prow), b = ld_u64(ry, xc * 4, prow + sy * 4);
@@ -953,14 +957,17 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
     else rows(G0{});
     if (touched == 0x9e3779b9u && p.n_frames == 0xffffffffu) dp[0] = 0;  // never true: keeps the sweep's loads alive
   } else {
-    // ---- coefficient input: 128 x 16 pixel tiles, IDCT into the wave's LDS tile, then eight quad rows -------
+    // ---- coefficient input: 128 x 16 pixel tiles (128 x 8 for 4:4:4), IDCT into the wave's LDS tile, then eight (four) quad rows -------
     stage_tables();
     __shared__ int s_ws[BLK / 64][8 * 8 * 9];
     __shared__ int s_q[3][64];
-    __shared__ __attribute__((aligned(8))) uint8_t s_yt[BLK / 64][16 * 128];
+    constexpr int TROWS = BASE == 1 ? 8 : 16;  // pixel rows of a tile: a 4:4:4 MCU row is eight rows high
+    constexpr int QROWS = TROWS / 2;           // its quad rows
+    __shared__ __attribute__((aligned(8))) uint8_t s_yt[BLK / 64][TROWS * 128];
     constexpr int CROWS = BASE == 3 ? 16 : 8;  // chroma rows of a tile: 4:2:2 chroma is not subsampled vertically
+    constexpr int CPITCH = BASE == 1 ? 128 : 64;  // bytes of a chroma row: 4:4:4 chroma is not subsampled at all
     constexpr int NU = BASE == 3 ? 8 : 6;      // eight-block units of a tile
-    __shared__ __attribute__((aligned(8))) uint8_t s_ct[BLK / 64][2][CROWS * 64];
+    __shared__ __attribute__((aligned(8))) uint8_t s_ct[BLK / 64][2][CROWS * CPITCH];
     // one workgroup's tables and tiles must fit a CU's LDS (the 768-thread HLG / PQ workgroups carry twelve tiles next to the
     // output-code buckets)
     static_assert(sizeof s_srgb + sizeof s_gain + sizeof s_u8f + sizeof s_tap + sizeof s_fac + sizeof s_cv + sizeof s_cu + sizeof s_code + sizeof s_idw +
@@ -979,16 +986,26 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
     const int16_t* ccb = cs->coef[1];
     const int16_t* ccr = cs->coef[2];
     const int bw0 = cs->bw[0], bh0 = cs->bh[0], bw1 = cs->bw[1], bh1 = cs->bh[1], bw2 = cs->bw[2], bh2 = cs->bh[2];
-    const uint32_t tiles_x = (p.sdr.w + 127) >> 7, tiles_y = (p.sdr.h + 15) >> 4, ntiles = tiles_x * tiles_y;
+    const uint32_t tiles_x = (p.sdr.w + 127) >> 7, tiles_y = (p.sdr.h + TROWS - 1) / TROWS, ntiles = tiles_x * tiles_y;
     const uint32_t nwaves = gridDim.x * (BLK / 64);
     auto tiles = [&](auto GM) {
     for (uint32_t t = wave; t < ntiles; t += nwaves) {
       const uint32_t ty = t / tiles_x, tx = t - ty * tiles_x;
       // the tile's eight-block units: Y rows 2ty, 2ty+1 x two halves, then Cb, Cr (4:2:0) or Cb rows 2ty, 2ty+1, Cr rows 2ty,
-      // 2ty+1 (4:2:2) (all loads issued up front)
+      // 2ty+1 (4:2:2) (all loads issued up front); 4:4:4: block row ty of Y, Cb, Cr x two halves
       int v[NU][8];
       int big[NU] = {};
-      {
+      if constexpr (BASE == 1) {
+        const int16_t* const cc[3] = {cy, ccb, ccr};
+        const int bwc[3] = {bw0, bw1, bw2}, bhc[3] = {bh0, bh1, bh2};
+#pragma unroll
+        for (int u = 0; u < 6; u++) {
+          int q[8];
+#pragma unroll
+          for (int c = 0; c < 8; c++) q[c] = s_q[u >> 1][rr * 8 + c];
+          idct::load_dequant_row(cc[u >> 1], bwc[u >> 1], (int)ty, (int)(tx * 16) + (u & 1) * 8 + rb, rr, q, v[u], big[u], (int)ty < bhc[u >> 1]);
+        }
+      } else {
         int q[8];
 #pragma unroll
         for (int c = 0; c < 8; c++) q[c] = s_q[0][rr * 8 + c];
@@ -1023,7 +1040,7 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
       const uint32_t xraw = tx * 128 + lane * 2;
       const bool lane_ok = xraw < p.sdr.w;
       col[0] = make_col(min(xraw, p.sdr.w - 2));
-      Raw a = fetch(ty * 8, H0{});  // the first quad row's gain-map bytes are in flight during the transforms
+      Raw a = fetch(ty * QROWS, H0{});  // the first quad row's gain-map bytes are in flight during the transforms
 #pragma unroll
       for (int u = 0; u < NU; u++) {
         uint32_t sm8[8];
@@ -1031,7 +1048,9 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
         const uint32_t lo = sm8[0] | (sm8[1] << 8) | (sm8[2] << 16) | (sm8[3] << 24);
         const uint32_t hi = sm8[4] | (sm8[5] << 8) | (sm8[6] << 16) | (sm8[7] << 24);
         uint8_t* d;
-        if constexpr (BASE == 3) {
+        if constexpr (BASE == 1) {
+          d = (u < 2 ? yt : (u < 4 ? cbt : crt)) + rr * 128 + ((u & 1) * 8 + rb) * 8;
+        } else if constexpr (BASE == 3) {
           d = (u < 4) ? yt + ((u >> 1) * 8 + rr) * 128 + ((u & 1) * 8 + rb) * 8
                       : (u < 6 ? cbt : crt) + ((u & 1) * 8 + rr) * 64 + rb * 8;
         } else {
@@ -1043,10 +1062,10 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the tile is complete in LDS
 #pragma unroll 1
-      for (uint32_t qr = 0; qr < 8; qr++) {
-        const uint32_t qy = ty * 8 + qr;
+      for (uint32_t qr = 0; qr < QROWS; qr++) {
+        const uint32_t qy = ty * QROWS + qr;
         Raw nxt = a;
-        if (qr < 7) nxt = fetch(qy + 1, H0{});
+        if (qr < QROWS - 1) nxt = fetch(qy + 1, H0{});
         a.y0 = *(const uint16_t*)(yt + (2 * qr) * 128 + lane * 2);
         a.y1 = *(const uint16_t*)(yt + (2 * qr + 1) * 128 + lane * 2);
         if constexpr (BASE == 3) {  // as fetch fills a 4:2:2 quad: row 0's chroma sample in u / v, row 1's in c[2] / c[3]
@@ -1054,6 +1073,12 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
           a.v = crt[(2 * qr) * 64 + lane];
           a.c[2] = cbt[(2 * qr + 1) * 64 + lane];
           a.c[3] = crt[(2 * qr + 1) * 64 + lane];
+          a.c[0] = a.c[1] = 0;
+        } else if constexpr (BASE == 1) {  // as fetch fills a 4:4:4 quad: row 0's chroma pairs in u / v, row 1's in c[2] / c[3]
+          a.u = *(const uint16_t*)(cbt + (2 * qr) * 128 + lane * 2);
+          a.v = *(const uint16_t*)(crt + (2 * qr) * 128 + lane * 2);
+          a.c[2] = *(const uint16_t*)(cbt + (2 * qr + 1) * 128 + lane * 2);
+          a.c[3] = *(const uint16_t*)(crt + (2 * qr + 1) * 128 + lane * 2);
           a.c[0] = a.c[1] = 0;
         } else {
           a.u = cbt[qr * 64 + lane];
@@ -1179,12 +1204,13 @@ hipError_t launch_quad(const ApplyParams& p, hipStream_t s) {
   }
   return hipGetLastError();
 }
-// coefficient input (SRC 1): resident workgroups, waves stride over the 128 x 16 pixel tiles
+// coefficient input (SRC 1): resident workgroups, waves stride over the 128 x 16 (4:4:4: 128 x 8) pixel tiles
 template <int OUT, int MAPFMT, int SMODE, int BASE>
 hipError_t launch_quad_coef(const ApplyParams& p, hipStream_t s) {
   constexpr int BLK = quad_block<OUT>();
   static const int resident = resident_blocks(apply_quad_kernel_s96<OUT, MAPFMT, SMODE, BASE, 1>, BLK, 96);
-  const uint32_t ntiles = ((p.sdr.w + 127) / 128) * ((p.sdr.h + 15) / 16);
+  constexpr uint32_t trows = BASE == 1 ? 8 : 16;
+  const uint32_t ntiles = ((p.sdr.w + 127) / 128) * ((p.sdr.h + trows - 1) / trows);
   uint32_t grid = (ntiles + BLK / 64 - 1) / (BLK / 64);
   if (grid > (uint32_t)resident) grid = (uint32_t)resident;
   ApplyParams q = p;
@@ -1282,8 +1308,8 @@ int apply_quad_mode(const ApplyParams& p) {
   return -1;
 }
 
-// Base image in coefficient form (p.coef_src, a device CoefSrc; p.sdr carries the geometry and the sampling -- 4:2:0 or
-// 4:2:2 -- of the image the coefficients decode to).  Only the quad kernel has this input: hipErrorInvalidValue when its
+// Base image in coefficient form (p.coef_src, a device CoefSrc; p.sdr carries the geometry and the sampling -- 4:2:0,
+// 4:2:2 or 4:4:4 -- of the image the coefficients decode to).  Only the quad kernel has this input: hipErrorInvalidValue when its
 // contract does not hold.
 hipError_t launch_apply_gainmap_coef(const ApplyParams& p, hipStream_t s) {
   const int out = p.out_ct == UHDR_CT_LINEAR ? 0 : (p.out_ct == UHDR_CT_HLG ? 1 : 2);
@@ -1292,6 +1318,7 @@ hipError_t launch_apply_gainmap_coef(const ApplyParams& p, hipStream_t s) {
   if (smode < 0 || !p.coef_src || p.n_frames > 1) return hipErrorInvalidValue;
   if (p.sdr.fmt == UHDR_IMG_FMT_12bppYCbCr420) return launch_quad_coef_o<0>(p, out, mapfmt, smode, s);
   if (p.sdr.fmt == UHDR_IMG_FMT_16bppYCbCr422) return launch_quad_coef_o<3>(p, out, mapfmt, smode, s);
+  if (p.sdr.fmt == UHDR_IMG_FMT_24bppYCbCr444) return launch_quad_coef_o<1>(p, out, mapfmt, smode, s);
   return hipErrorInvalidValue;
 }
 

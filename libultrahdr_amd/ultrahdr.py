@@ -330,6 +330,17 @@ class UltraHdr:
                    C.byref(map_hdr), C.c_void_p(map_data.data_ptr()), int(map_data.numel()), map_cg, libjpeg_variant, C.byref(gainmap_metadata), output_ct, output_format,
                    max_display_boost, C.byref(dest.raw))
 
+    def decodeApi1ScansAny(self, base_hdr: "A.JpegHeader", base_data, base_cg: int, map_hdr: "A.JpegHeader", map_data, map_cg: int,
+                           gainmap_metadata: A.GainmapMetadata, output_ct: int, output_format: int, max_display_boost: float, dest: Image,
+                           libjpeg_variant: int = 0):
+        """decodeApi1Scans for every base image JpegR::applyGainMap takes (jpegr.cpp:1586-1638), in ONE C call
+        (uhdr_hip_decode_api1_scans_any_dev): the base scan is 4:2:0, 4:2:2 or 4:4:4 (base_hdr says which); the first two are
+        decoded exactly as by decodeApi1Scans, which keeps refusing 4:4:4."""
+        assert base_data.is_cuda and map_data.is_cuda and _is_dev(dest)
+        self._call(True, self.lib.uhdr_hip_decode_api1_scans_any_dev, self.ctx.handle, C.byref(base_hdr), C.c_void_p(base_data.data_ptr()), int(base_data.numel()), base_cg,
+                   C.byref(map_hdr), C.c_void_p(map_data.data_ptr()), int(map_data.numel()), map_cg, libjpeg_variant, C.byref(gainmap_metadata), output_ct, output_format,
+                   max_display_boost, C.byref(dest.raw))
+
     # ---- applyGainMap (ultrahdrcommon.h:531-534) -----------------------------------------------
     def applyGainMap(self, sdr_intent: Image, gainmap_img: Image, gainmap_metadata: A.GainmapMetadata,
                      output_ct: int, output_format: int, max_display_boost: float, dest: Image,
@@ -363,6 +374,21 @@ class UltraHdr:
             for k in range(64):
                 jc.qtable[i][k] = int(qtables[i][k])
         self._call(True, fn, self.ctx.handle, C.byref(jc), w, h, base_cg, C.byref(gainmap_img.raw),
+                   C.byref(gainmap_metadata), output_ct, output_format, max_display_boost, C.byref(dest.raw))
+
+    def applyGainMapFromCoefficients444(self, coefs, qtables, w: int, h: int, base_cg: int, gainmap_img: Image,
+                                        gainmap_metadata: A.GainmapMetadata, output_ct: int, output_format: int,
+                                        max_display_boost: float, dest: Image):
+        """applyGainMapFromCoefficients for a 4:4:4 base image (uhdr_hip_apply_gainmap_coef444_dev): all three components on
+        the ceil(w/8) x ceil(h/8) block grid.  == idct_dequant x 3 + applyGainMap on the 24bppYCbCr444 image, bit for bit."""
+        assert all(c.is_cuda for c in coefs) and _is_dev(gainmap_img, dest)
+        jc = A.JpegCoefficients()
+        for i in range(3):
+            jc.coef[i] = coefs[i].data_ptr()
+            jc.blocks_h[i], jc.blocks_w[i] = int(coefs[i].shape[0]), int(coefs[i].shape[1])
+            for k in range(64):
+                jc.qtable[i][k] = int(qtables[i][k])
+        self._call(True, self.lib.uhdr_hip_apply_gainmap_coef444_dev, self.ctx.handle, C.byref(jc), w, h, base_cg, C.byref(gainmap_img.raw),
                    C.byref(gainmap_metadata), output_ct, output_format, max_display_boost, C.byref(dest.raw))
 
     def applyGainMapBatch(self, sdr_intents, gainmap_imgs, gainmap_metadata: A.GainmapMetadata, output_ct: int,

@@ -1,14 +1,15 @@
 """The one-call decode to HDR (uhdr_hip_decode_api1_scans_dev: both scans entropy-decoded, the map's IDCT, applyGainMap with the
 base image's dequantize + IDCT inside the kernel) against the staged route on the same device-resident scans, at 3840 x 2160:
 
-    fused    UltraHdr.decodeApi1Scans (arguments marshalled once: bindDecodeApi1Scans)
+    fused    UltraHdr.decodeApi1Scans (arguments marshalled once: bindDecodeApi1Scans); for a 4:4:4 base image the same call of
+             uhdr_hip_decode_api1_scans_any_dev, marshalled once here
     staged   huffman_decode2 (both scans, concurrently, as the one-call decode does), the map's IDCT, three idct_dequant launches into
              a planar base image, applyGainMap on the planes -- what a caller had to do for a 4:2:2 base image before the
-             coefficient-input kernel took that sampling (2 B/px of planes written to HBM and read back)
+             coefficient-input kernel took that sampling (2 B/px of planes written to HBM and read back; 3 B/px for 4:4:4)
 
     python tools/hdr_decode_time.py --sampling 422 [--iters 30] [--rounds 3] [--json out.json]
-    --sampling 420 | 422 | both      the base image's sampling (both: the two in one run, so that the 4:2:0 figures are a reference
-                                     point taken under the same conditions)
+    --sampling 420 | 422 | 444 | both | all    the base image's sampling (both: 4:2:0 and 4:2:2 in one run, all: the three, so that
+                                               the 4:2:0 figures are a reference point taken under the same conditions)
 
 Times are HIP events on the context's stream around a loop of calls, each loop behind its own warm-up of the same calls; the two
 routes alternate, `rounds` times, and the median round is reported next to the spread.  The entropy stage synchronises with the
@@ -27,8 +28,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 W, H = 3840, 2160
-SAMPLING = {"420": [(2, 2), (1, 1), (1, 1)], "422": [(2, 1), (1, 1), (1, 1)]}
 S444 = [(1, 1)] * 3
+SAMPLING = {"420": [(2, 2), (1, 1), (1, 1)], "422": [(2, 1), (1, 1), (1, 1)], "444": S444}
 
 
 def grids(w, h, sampling):
@@ -67,13 +68,31 @@ def event_ms(ctx, fn, iters):
     return e0.elapsed_time(e1) / iters
 
 
+def bind_any(u, base_hdr, base_data, base_cg, map_hdr, map_data, map_cg, md, output_ct, output_format, max_display_boost, dest):
+    """UltraHdr.decodeApi1ScansAny with the arguments marshalled once, as bindDecodeApi1Scans does for decodeApi1Scans."""
+    import ctypes as C
+
+    from libultrahdr_amd import capi as A
+
+    fn = u.lib.uhdr_hip_decode_api1_scans_any_dev
+    args = (u.ctx.handle, C.byref(base_hdr), C.c_void_p(base_data.data_ptr()), int(base_data.numel()), base_cg, C.byref(map_hdr),
+            C.c_void_p(map_data.data_ptr()), int(map_data.numel()), map_cg, 0, C.byref(md), output_ct, output_format, max_display_boost, C.byref(dest.raw))
+    ordered, check = u.ctx.ordered, A.check
+
+    def run(_keep=(base_hdr, base_data, map_hdr, map_data, md, dest)):
+        with ordered():
+            check(fn(*args))
+
+    return run
+
+
 def case(u, ctx, sampling, nch, scale, iters, rounds, rng):
     from libultrahdr_amd import capi as A
     from libultrahdr_amd import synth
     from libultrahdr_amd.images import Image
 
     f16 = A.UHDR_IMG_FMT_64bppRGBAHalfFloat
-    planar = A.UHDR_IMG_FMT_12bppYCbCr420 if sampling == "420" else A.UHDR_IMG_FMT_16bppYCbCr422
+    planar = {"420": A.UHDR_IMG_FMT_12bppYCbCr420, "422": A.UHDR_IMG_FMT_16bppYCbCr422, "444": A.UHDR_IMG_FMT_24bppYCbCr444}[sampling]
     qy, qc = u.quant_table(90, False), u.quant_table(90, True)
     qts = [qy, qc, qc]
     samp = SAMPLING[sampling]
@@ -84,11 +103,12 @@ def case(u, ctx, sampling, nch, scale, iters, rounds, rng):
     md = synth.default_metadata(use_base_cg=0, per_channel=(nch == 3))
     base_cg, map_cg = A.UHDR_CG_BT_709, A.UHDR_CG_BT_2100
     d_fused, d_staged = Image(f16, W, H, align=64, device="cuda:0"), Image(f16, W, H, align=64, device="cuda:0")
-    fused = u.bindDecodeApi1Scans(hb, scan_b, base_cg, hm, scan_m, map_cg, md, A.UHDR_CT_LINEAR, f16, A.FLT_MAX, d_fused)
+    bind = (lambda *a: bind_any(u, *a)) if sampling == "444" else u.bindDecodeApi1Scans  # the first entry point refuses 4:4:4
+    fused = bind(hb, scan_b, base_cg, hm, scan_m, map_cg, md, A.UHDR_CT_LINEAR, f16, A.FLT_MAX, d_fused)
 
     shp_b, shp_m = grids(W, H, samp), grids(mw, mh, msamp)
     base = Image(planar, W, H, base_cg, A.UHDR_CT_SRGB, A.UHDR_CR_FULL_RANGE, align=64, device="cuda:0")  # 3840 x 2160: whole blocks
-    assert W % 128 == 0 and H % 8 == 0 and (sampling == "422" or H % 16 == 0)
+    assert W % 128 == 0 and H % 8 == 0 and (sampling != "420" or H % 16 == 0)
     if nch == 3:
         gm = Image(A.UHDR_IMG_FMT_32bppRGBA8888, mw, mh, map_cg, align=64, device="cuda:0")
     else:
@@ -123,7 +143,7 @@ def case(u, ctx, sampling, nch, scale, iters, rounds, rng):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--sampling", default="422", choices=("420", "422", "both"))
+    ap.add_argument("--sampling", default="422", choices=("420", "422", "444", "both", "all"))
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--json", default=None)
@@ -133,7 +153,7 @@ def main():
     ctx = Context(0)  # raises without a GPU: there is nothing to time on a CPU
     u = UltraHdr(ctx=ctx)
     rows = []
-    for s in (("420", "422") if args.sampling == "both" else (args.sampling,)):
+    for s in {"both": ("420", "422"), "all": ("420", "422", "444")}.get(args.sampling, (args.sampling,)):
         for nch, scale in ((1, 4), (3, 1)):
             rows.append(case(u, ctx, s, nch, scale, args.iters, args.rounds, np.random.default_rng(7)))
             print(json.dumps(rows[-1]), flush=True)
