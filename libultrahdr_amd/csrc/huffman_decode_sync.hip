@@ -1256,9 +1256,9 @@ __global__ __launch_bounds__(64 * kStragWaves) void hyp_straggler_kernel(const H
   const uint32_t H = (uint32_t)a.hyp_h, bpm = (uint32_t)a.blocks_per_mcu;
   const uint32_t l_main = (uint32_t)a.hyp_main_levels;
   const uint32_t l_cap = (uint32_t)min(a.hyp_levels, a.strag_levels);
-  uint32_t cpack = 0;
+  uint32_t cmask = 0;  // bit j: block j of the MCU is a chroma block
 #pragma unroll
-  for (int j = 0; j < 16; j++) cpack |= ((uint32_t)a.comp_of[j] & 3u) << (2 * j);
+  for (int j = 0; j < 16; j++) cmask |= (a.comp_of[j] != 0 ? 1u : 0u) << j;
   constexpr uint32_t kWords = sizeof(HuffFastTable) / 2;
   const uint16_t* T = (const uint16_t*)L.t;
   const uint32_t* clean32 = (const uint32_t*)a.clean;
@@ -1319,7 +1319,11 @@ __global__ __launch_bounds__(64 * kStragWaves) void hyp_straggler_kernel(const H
         for (uint32_t pq = 0; pq < Q; pq++) {
         const uint32_t cut = pq + 1u < Q ? min(j * a.sub_bits + (pq + 1u) * piece_bits, end_bit) : end_bit;
         while (p < cut) {
-          const uint32_t q = p + lane - (w0 << 5);  // the lane's bit, relative to the stage
+          // The window ends at lane 64: a round that may take fewer than 64 bits (the last one before a cut or the end) starts at lane
+          // bias = 64 - lim instead of lane 0, so that "off reached lim" is bit 6 of the lane index in every round.  (Lanes below the
+          // bias look at bits in front of p, or at the clamped end of the stage where p is near its start; the chain never reads them.)
+          const uint32_t lim = min(64u, cut - p), bias = 64u - lim;
+          const uint32_t q = p + lane - bias - (w0 << 5);  // the lane's bit, relative to the stage
           const uint32_t wi = min(q >> 5, (uint32_t)kStragStageWords - 2u);
           const uint64_t two = ((uint64_t)stage[wi] << 32) | stage[wi + 1];
           const uint32_t w16 = (uint32_t)(two >> (48u - (q & 31u))) & 0xffffu;
@@ -1329,34 +1333,39 @@ __global__ __launch_bounds__(64 * kStragWaves) void hyp_straggler_kernel(const H
             const uint32_t tb = t * kWords;
             uint32_t e = T[tb + (w16 >> 7)];
             const uint32_t e2 = T[tb + 512u + ((e & 0x8000u) ? (e & 31u) : 0u) * 128u + (w16 & 127u)];
-            ent[t] = (e & 0x8000u) ? e2 : e;
+            e = (e & 0x8000u) ? e2 : e;
+            ent[t] = (e & 31u) | ((e & 0xfe0u) << 11);  // bits | advance << 16: one addition moves the lane index and the zig-zag index
           }
-          const uint32_t lim = min(64u, cut - p);
-          uint32_t off = 0;
           // The chain: per block one DC step, then AC steps until the zig-zag index passes 63 -- the inner loop is the whole cost
-          // (24 of 25 symbols of a busy block): v_readlane, two field extractions, two additions, two compares.  The component's
-          // entry registers are picked once per block, not per symbol.
-          while (off < lim) {
-            const bool is_chroma = ((cpack >> (2u * b)) & 3u) != 0;
-            const int dc = (int)(is_chroma ? ent[2] : ent[0]), ac = (int)(is_chroma ? ent[3] : ent[1]);
-            if (k == 0) {
-              const uint32_t e = (uint32_t)__builtin_amdgcn_readlane(dc, (int)off);
-              off += e & 31u;
-              k = (e >> 5) & 127u;  // 1 for every DC symbol
-            }
-            while ((int32_t)((k - 64u) & (off - lim)) < 0) {  // k < 64 && off < lim (both small): one compare
-              const uint32_t e = (uint32_t)__builtin_amdgcn_readlane(ac, (int)off);
-              off += e & 31u;
-              k += (e >> 5) & 127u;
-            }
-            if (k >= 64u) {
-              k = 0;
+          // (24 of 25 symbols of a busy block).  Lane index and zig-zag index share one SGPR, w = off | k << 16: off <= 63 + 31 and
+          // k <= 63 + 64 where a step starts, so "off reached 64" is bit 6 and "k reached 64" is bit 22, and a step is v_readlane
+          // (the lane select is the operand's low six bits: off itself while bit 6 is clear), one addition, one s_and of both bits,
+          // the branch.  Luma and chroma blocks get a copy of the loop each, on their own entry registers: picking the registers per
+          // block (v_cndmask) put a VALU write, and the wait state v_readlane needs after one, in front of every step.  Only a
+          // round's first block can start past its DC symbol (k != 0), so that case is peeled off and the DC step has no test.
+          constexpr uint32_t kOffEnd = 1u << 6, kBlockEnd = 1u << 22;
+          auto ac_steps = [](uint32_t w, uint32_t ac) {
+            while (!(w & (kOffEnd | kBlockEnd))) w += (uint32_t)__builtin_amdgcn_readlane((int)ac, (int)w);
+            return w;
+          };
+          auto end_block = [&](uint32_t w) {
+            if (w & kBlockEnd) {
+              w &= 0xffffu;  // k = 0
               b++;
               nblk++;
               if (b == bpm) b = 0;
             }
+            return w;
+          };
+          uint32_t w = bias | (k << 16);
+          if (k != 0) w = end_block(((cmask >> b) & 1u) ? ac_steps(w, ent[3]) : ac_steps(w, ent[1]));
+          while (!(w & kOffEnd)) {  // k == 0; the advance is 1 for every DC symbol
+            if ((cmask >> b) & 1u) w = ac_steps(w + (uint32_t)__builtin_amdgcn_readlane((int)ent[2], (int)w), ent[3]);
+            else w = ac_steps(w + (uint32_t)__builtin_amdgcn_readlane((int)ent[0], (int)w), ent[1]);
+            w = end_block(w);
           }
-          p += off;
+          p += (w & 0xffffu) - bias;
+          k = w >> 16;
         }
         if (pq + 1u < Q && lane == 0) {
           a.mid_state[mo + pq] = pack_state(p, b, k);
