@@ -68,16 +68,17 @@ def _has_zrl(c):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(name, quality, short_tail=False):
+def _case(name, quality, short_tail=False, noise=None):
     """(coefficients, scan) of a noise-textured image: a smooth field under noise whose amplitude varies over the picture -- calm
-    regions (end-of-block codes, zero runs) next to busy ones (blocks coded up to the last term).  Built once, left unchanged."""
+    regions (end-of-block codes, zero runs) next to busy ones (blocks coded up to the last term).  Built once, left unchanged.
+    noise: the noise's scale, None = AMP[quality] (tests/huff_tables.py asks for calmer and busier variants)."""
     sampling = SAMPLINGS[name]
     rng = np.random.default_rng(1000 * SEED[name, quality] + quality)
     coefs = []
     for c, (bw, bh) in enumerate(_grids(sampling)):
         yy, xx = np.mgrid[0:bh * 8, 0:bw * 8]
         amp = 0.3 + 7.0 * (0.5 + 0.5 * np.sin(xx / 23.0 + c) * np.cos(yy / 17.0)) ** 2
-        pl = 128 + 70 * np.sin(xx / (29.0 + 5 * c)) * np.cos(yy / (21.0 + 3 * c)) + rng.normal(0, 1, (bh * 8, bw * 8)) * amp * AMP[quality]
+        pl = 128 + 70 * np.sin(xx / (29.0 + 5 * c)) * np.cos(yy / (21.0 + 3 * c)) + rng.normal(0, 1, (bh * 8, bw * 8)) * amp * (AMP[quality] if noise is None else noise)
         qt = L.quant_table_port(quality, c > 0)
         coefs.append(L.fdct_quant_port(np.ascontiguousarray(np.clip(np.rint(pl), 0, 255).astype(np.uint8)), bw * 8, bw, bh, qt))
     scan = L.huffman_encode_port(coefs, W, H, sampling, 0)
@@ -92,10 +93,10 @@ def _case(name, quality, short_tail=False):
             scan = L.huffman_encode_port(coefs, W, H, sampling, 0)
         nclean = len(scan) - scan.count(b"\xff\x00")
         assert 1 <= nclean % 64 <= 7, nclean
-    if quality == 100:
+    if quality == 100 and noise is None:
         assert any((c[..., 63] != 0).any() for c in coefs), "no block is coded up to its last term"
         assert any(_has_zrl(c) for c in coefs), "no ZRL run"
-    assert len(scan) >= 4096
+    assert len(scan) >= 4096 or noise is not None
     return coefs, scan
 
 
@@ -118,16 +119,18 @@ def _parallel(uhdr):
     return st.entropy_decode_parallel
 
 
-def decode_with_stragglers(uhdr, monkeypatch, capfd, name, quality, sub_bits, main_levels, short_tail=False):
-    """Decodes the case with the stragglers forced; returns the number of paths they were handed.  Asserts everything else."""
-    coefs, scan = _case(name, quality, short_tail)
+def decode_with_stragglers(uhdr, monkeypatch, capfd, name, quality, sub_bits, main_levels, short_tail=False, tables=None, coded=None):
+    """Decodes the case with the stragglers forced; returns the number of paths they were handed.  Asserts everything else.
+    tables / coded: the DHT tables (None: Annex K) and the (coefficients, scan) coded with them, in place of the case's own
+    (tests/test_gpu_huff_tables.py)."""
+    coefs, scan = coded if coded is not None else _case(name, quality, short_tail)
     sampling = SAMPLINGS[name]
     monkeypatch.setenv("UHDR_HIP_HUFF_DEBUG", "1")
     monkeypatch.setenv("UHDR_HIP_HUFF_SUB_BITS", str(sub_bits))
     monkeypatch.setenv("UHDR_HIP_HUFF_MAIN_LEVELS", str(main_levels))
     capfd.readouterr()
     before = _parallel(uhdr)
-    got = uhdr.huffman_decode(_dev(scan), [c.shape[:2] for c in coefs], W, H, sampling, 0)
+    got = uhdr.huffman_decode(_dev(scan), [c.shape[:2] for c in coefs], W, H, sampling, 0, tables=tables)
     host = [g.cpu().numpy() for g in got]
     err = capfd.readouterr().err
     lines = [ln for ln in err.splitlines() if "paths handed to the straggler waves" in ln]
