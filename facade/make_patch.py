@@ -120,11 +120,12 @@ def jpegr_cpp(t):
                      "      UHDR_ERR_CHECK(appendGainMap(&sdr_intent_compressed, &gainmap_compressed, exif, /* icc */ nullptr,\n"
                      "                                   /* icc size */ 0, &metadata, dest));\n"
                      "      return g_no_error;\n    }\n  }\n#endif\n")
-    # encodeJPEGR API-0 (round 6): RGBA1010102 / RGBA half-float intents as one device sequence (BASELINE config 3); P010 keeps the stage seams
+    # encodeJPEGR API-0 (round 6): RGBA1010102 / RGBA half-float intents as one device sequence (BASELINE config 3); P010 intents reach the
+    # seam too, which takes them only under UHDR_HIP_SEAM_FUSED_P010 and otherwise leaves them to the stage seams
     t = insert_before(t, "  std::unique_ptr<uhdr_raw_image_ext_t> sdr_intent = std::make_unique<uhdr_raw_image_ext_t>(\n"
                          "      sdr_intent_fmt, UHDR_CG_UNSPECIFIED, UHDR_CT_UNSPECIFIED, UHDR_CR_UNSPECIFIED, hdr_intent->w,\n"
                          "      hdr_intent->h, 64);\n\n  // tone map\n",
-                      "#ifdef UHDR_ENABLE_HIP\n  if (uhdr_hip_seam::enabled() && sdr_intent_fmt == UHDR_IMG_FMT_32bppRGBA8888) {\n"
+                      "#ifdef UHDR_ENABLE_HIP\n  if (uhdr_hip_seam::enabled() && (sdr_intent_fmt == UHDR_IMG_FMT_32bppRGBA8888 || sdr_intent_fmt == UHDR_IMG_FMT_12bppYCbCr420)) {\n"
                       "    uhdr_gainmap_metadata_ext_t hip_metadata(kJpegrVersion);\n"
                       "    std::shared_ptr<DataStruct> hip_icc_map =  // compressGainMap's choice (jpegr.cpp:520-528)\n"
                       "        kWriteXmpMetadata ? nullptr : IccHelper::writeIccProfile(hdr_intent->ct, hdr_intent->cg);\n"

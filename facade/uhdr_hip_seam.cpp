@@ -407,10 +407,14 @@ bool encode_api0(uhdr_raw_image_t* hdr_intent, int base_quality, int map_quality
   if (getenv("UHDR_HIP_SEAM_NO_FUSED_ENCODE") || getenv("UHDR_HIP_SEAM_CPU_ENTROPY") || getenv("UHDR_HIP_SEAM_RESTART_INTERVAL") ||
       getenv("UHDR_HIP_SEAM_DEVICE_ENTROPY") || getenv("UHDR_HIP_SEAM_EAGER_DOWNLOADS"))
     return false;
-  if (hdr_intent->fmt != UHDR_IMG_FMT_32bppRGBA1010102 && hdr_intent->fmt != UHDR_IMG_FMT_64bppRGBAHalfFloat) return false;
+  // a P010 intent (its base image is the tone mapper's 4:2:0 planes, compressed as they are) takes the fused route only when asked to:
+  // UHDR_HIP_SEAM_FUSED_P010; without it the per-stage seams run as before
+  const bool p010 = hdr_intent->fmt == UHDR_IMG_FMT_24bppYCbCrP010 && getenv("UHDR_HIP_SEAM_FUSED_P010") != nullptr;
+  if (!p010 && hdr_intent->fmt != UHDR_IMG_FMT_32bppRGBA1010102 && hdr_intent->fmt != UHDR_IMG_FMT_64bppRGBAHalfFloat) return false;
   if (*scale_factor != 1) return false;
   const unsigned w = hdr_intent->w, h = hdr_intent->h;
-  if (w == 0 || h == 0 || w % 8 || h % 8 || w > 65535 || h > 65535) return false;
+  const unsigned grid = p010 ? 16 : 8;  // whole MCUs: 2x2 / 1x1 / 1x1 sampling for P010, 1x1 otherwise
+  if (w == 0 || h == 0 || w % grid || h % grid || w > 65535 || h > 65535) return false;
   if (map_icc_size > 65533 || (map_comment && strlen(map_comment) > 65533)) return false;
   if (base_quality < 0 || base_quality > 100 || map_quality < 0 || map_quality > 100) return false;
   enter();
@@ -437,7 +441,11 @@ bool encode_api0(uhdr_raw_image_t* hdr_intent, int base_quality, int map_quality
   sm.num_components = nch;
   sb.w = sm.w = w;
   sb.h = sm.h = h;
-  for (int i = 0; i < 3; i++) { sb.blocks_w[i] = (int)(w / 8); sb.blocks_h[i] = (int)(h / 8); sb.h_samp[i] = sb.v_samp[i] = 1; }
+  for (int i = 0; i < 3; i++) {
+    const unsigned sub = (p010 && i) ? 16 : 8;
+    sb.blocks_w[i] = (int)(w / sub); sb.blocks_h[i] = (int)(h / sub);
+    sb.h_samp[i] = sb.v_samp[i] = (p010 && !i) ? 2 : 1;
+  }
   for (int i = 0; i < nch; i++) { sm.blocks_w[i] = (int)(w / 8); sm.blocks_h[i] = (int)(h / 8); sm.h_samp[i] = sm.v_samp[i] = 1; }
   unsigned char hb[2048], hm[2048];
   const unsigned char none = 0;
@@ -466,8 +474,8 @@ bool encode_api0(uhdr_raw_image_t* hdr_intent, int base_quality, int map_quality
     out->gainmap_data.reset(new (std::nothrow) unsigned char[lead_m + cap_m + 2]);
     if (!out->base_data || !out->gainmap_data) return false;
     nb = nm = 0;
-    *st = uhdr_hip_encode_api0_scans(cur(), hdr_intent, &cfg, qt_base, qt_map, &md, &gm_desc, &cg, out->base_data.get() + lead_b_max, cap_b, &nb,
-                                     out->gainmap_data.get() + lead_m, cap_m, &nm);
+    *st = uhdr_hip_encode_api0_scans_any(cur(), hdr_intent, &cfg, qt_base, qt_map, &md, &gm_desc, &cg, out->base_data.get() + lead_b_max, cap_b, &nb,
+                                         out->gainmap_data.get() + lead_m, cap_m, &nm);
     if (st->error_code == UHDR_CODEC_MEM_ERROR && attempt == 0 && (nb > cap_b || nm > cap_m)) {  // (as in encode_api1: once more with the reported sizes)
       note("encode_api0_fused", true, "scan larger than one byte per coefficient: second attempt with the reported sizes");
       if (nb > cap_b) cap_b = nb + nb / 16 + (1u << 16);

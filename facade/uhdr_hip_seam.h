@@ -123,6 +123,8 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
 // base_icc(cg): the caller's IccHelper::writeIccProfile(UHDR_CT_SRGB, cg) for the gamut the tone-mapped rendition gets -- asked for through
 // the callback because that gamut is only known once the device has answered.  false: declined (P010 / YCbCr 4:4:4 intents, a scale factor
 // other than 1, dimensions that are not multiples of 8, ...): the per-stage seams run as before.
+// With UHDR_HIP_SEAM_FUSED_P010 in the environment a P010 intent whose dimensions are multiples of 16 is taken too (uhdr_hip_encode_api0_scans_any:
+// tone map to YCbCr 4:2:0 + one-pass gain map fused, the 4:2:0 planes to the FDCT as they are, base header 2x2 / 1x1 / 1x1); without it P010 is declined.
 struct IccBytes { const void* data; size_t size; };
 bool encode_api0(uhdr_raw_image_t* hdr_intent, int base_quality, int map_quality, int* scale_factor, bool multi_channel, float gamma,
                  float min_content_boost, float max_content_boost, float target_disp_peak_brightness,

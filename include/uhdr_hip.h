@@ -25,6 +25,7 @@
  *   uhdr_hip_apply_gainmap_batch_dev (n frames, one launch), uhdr_hip_generate_gainmap_pass1_dev / _finalize /
  *   _pass2_dev (two-pass generation split at its only exchange step, for row stripes across GPUs),
  *   uhdr_hip_encode_api0_fused_dev (toneMap + generateGainMap + convert_raw_input_to_ycbcr in one pass),
+ *   uhdr_hip_encode_api0_p010_fused_dev (toneMap + generateGainMap of a P010 intent in one pass),
  *   uhdr_hip_fdct_quant_rgb_dev (colour conversion + FDCT of a 3-channel map in one pass),
  *   uhdr_hip_idct_dequant_rgb_dev (its decode-side mirror: dequant + IDCT + colour conversion in one pass),
  *   uhdr_hip_apply_gainmap_coef_dev / _coef422_dev / _coef444_dev (applyGainMap on a base image still in coefficient form: IDCT inside the kernel),
@@ -370,6 +371,19 @@ uhdr_error_info_t uhdr_hip_encode_api0_fused_dev(uhdr_hip_ctx_t* ctx, const uhdr
                                                  const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* sdr_rgba,
                                                  uhdr_raw_image_t* base_ycc, uhdr_gainmap_metadata_t* metadata,
                                                  uhdr_raw_image_t* gainmap);
+
+/* MI355X extension: the same for a P010 intent, where JpegR::encodeJPEGR API-0 runs two full-image loops (lib/src/jpegr.cpp:206-220:
+ * toneMap from P010 to YCbCr 4:2:0, generateGainMap on both images) and compresses the 4:2:0 planes as they are (no
+ * convert_raw_input_to_ycbcr, jpegr.cpp:222-238).  ONE pass over the HDR image: 3 B/px in, 1.5 + 3 B/px out instead of 12 B/px.
+ * Device images only.  hdr: UHDR_IMG_FMT_24bppYCbCrP010 with the gamuts / transfers uhdr_hip_tone_map_dev takes, even dimensions,
+ * even strides and 4-byte aligned plane bases; cfg->map_dimension_scale_factor must be 1 (UHDR_CODEC_UNSUPPORTED_FEATURE otherwise,
+ * nothing is launched: use the two operators); both presets, one or three channels and cfg->gamma as uhdr_hip_generate_gainmap_dev.
+ * base_ycc420 receives the three 4:2:0 planes (even luma stride and base) and the descriptor uhdr_hip_tone_map_dev gives its P010
+ * rendition; md / gainmap as uhdr_hip_generate_gainmap_dev.  Outputs are bit-identical to uhdr_hip_tone_map_dev ->
+ * uhdr_hip_generate_gainmap_dev. */
+uhdr_error_info_t uhdr_hip_encode_api0_p010_fused_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* hdr,
+                                                      const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* base_ycc420,
+                                                      uhdr_gainmap_metadata_t* metadata, uhdr_raw_image_t* gainmap);
 
 /* copy_raw_image(src, dst) (lib/src/gainmapmath.cpp:1492-1613) between device images: strided plane copies
  * for equal formats, RGB888 -> RGBA8888 (alpha 0xff), RGBA8888 -> Y400 (R byte); same error codes
@@ -774,6 +788,17 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans(uhdr_hip_ctx_t* ctx, const uhdr_raw
                                              uhdr_raw_image_t* gainmap_desc, uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan,
                                              size_t base_capacity, size_t* base_bytes, uint8_t* map_scan, size_t map_capacity,
                                              size_t* map_bytes);
+
+/* uhdr_hip_encode_api0_scans for every HDR intent a fused front end takes: RGBA1010102 and RGBA half float go to the entry point above
+ * unchanged; a UHDR_IMG_FMT_24bppYCbCrP010 intent (lib/src/jpegr.cpp:179-244: toneMap to YCbCr 4:2:0, generateGainMap, compressImage of the
+ * 4:2:0 planes as they are) runs uhdr_hip_encode_api0_p010_fused_dev + FDCT / quantize + both scans Huffman-coded; its base scan is
+ * 2x2 / 1x1 / 1x1.  P010: scale factor 1 and dimensions that are multiples of 16 (UHDR_CODEC_UNSUPPORTED_FEATURE otherwise, nothing was
+ * uploaded).  Everything else as uhdr_hip_encode_api0_scans, including UHDR_CODEC_MEM_ERROR with the needed sizes in *_bytes. */
+uhdr_error_info_t uhdr_hip_encode_api0_scans_any(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                 const uint16_t qt_base[2][64], const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md,
+                                                 uhdr_raw_image_t* gainmap_desc, uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan,
+                                                 size_t base_capacity, size_t* base_bytes, uint8_t* map_scan, size_t map_capacity,
+                                                 size_t* map_bytes);
 
 /* The same on DEVICE-resident intents into DEVICE buffers, and its inverse (round 6): one entry point per direction of the API-1
  * round trip, for callers whose images live in HBM (a transcoding service; bench.py's headline).

@@ -144,6 +144,29 @@ class UltraHdr {
                                               gainmap_metadata, output_ct, output_format, max_display_boost, dest);
   }
 
+  // toneMap (P010 -> YCbCr 4:2:0) + generateGainMap of an API-0 encode in one pass over a device-resident P010 intent
+  // (uhdr_hip_encode_api0_p010_fused_dev): base_ycc420 and gainmap_img are device images the caller allocated; scale factor 1.
+  uhdr_error_info_t encodeApi0FusedP010(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* base_ycc420, uhdr_gainmap_metadata_t* gainmap_metadata,
+                                        uhdr_raw_image_t* gainmap_img, bool use_luminance = false) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, 0, use_luminance ? 1 : 0};
+    return uhdr_hip_encode_api0_p010_fused_dev(mCtx, hdr_intent, &cfg, base_ycc420, gainmap_metadata, gainmap_img);
+  }
+
+  // JpegR::encodeJPEGR API-0 without the container in one call (uhdr_hip_encode_api0_scans_any): a host RGBA1010102, RGBA half-float or
+  // P010 intent -> the two entropy-coded scans in host buffers.  qt_base / qt_map: {luma, chroma} tables.
+  uhdr_error_info_t encodeApi0ScansAny(uhdr_raw_image_t* hdr_intent, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                       uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_raw_image_t* gainmap_desc, uhdr_color_gamut_t* sdr_cg,
+                                       uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan, size_t map_capacity,
+                                       size_t* map_bytes) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, 0, 0};
+    return uhdr_hip_encode_api0_scans_any(mCtx, hdr_intent, &cfg, qt_base, qt_map, gainmap_metadata, gainmap_desc, sdr_cg, base_scan, base_capacity,
+                                          base_bytes, map_scan, map_capacity, map_bytes);
+  }
+
   uhdr_error_info_t convertYuv(uhdr_raw_image_t* image, uhdr_color_gamut_t src_encoding, uhdr_color_gamut_t dst_encoding) {
     if (!mCtx) return mCreateStatus;
     return uhdr_hip_convert_yuv(mCtx, image, src_encoding, dst_encoding);

@@ -195,6 +195,90 @@ uhdr_error_info_t uhdr_hip_encode_api0_fused_dev(uhdr_hip_ctx_t* c, const uhdr_r
 }
 
 // -------------------------------------------------------------------------------------------------
+// API-0 front end fused for P010 intents: toneMap (P010 -> YCbCr 4:2:0) + generateGainMap in one pass
+// -------------------------------------------------------------------------------------------------
+// jpegr.cpp:179-244 compresses the tone mapper's 4:2:0 planes as they are, so the base image leaves here in the form the base JPEG's
+// FDCT takes.  Declines (UHDR_CODEC_UNSUPPORTED_FEATURE, before anything is launched) what the quad kernel cannot read with its vector
+// accesses; the caller then runs uhdr_hip_tone_map_dev + uhdr_hip_generate_gainmap_dev.
+uhdr_error_info_t uhdr_hip_encode_api0_p010_fused_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                      uhdr_raw_image_t* base_ycc420, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  if (!hdr || !cfg || !base_ycc420 || !md || !gm || !gm->planes[0]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
+  if (hdr->fmt != UHDR_IMG_FMT_24bppYCbCrP010)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused P010 API-0 front end takes UHDR_IMG_FMT_24bppYCbCrP010. Received %d", hdr->fmt);
+  if (cfg->map_dimension_scale_factor != 1)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused P010 API-0 front end needs a full-resolution gain map (scale factor 1), received %d; "
+                      "use tone_map + generate_gainmap", cfg->map_dimension_scale_factor);
+  if (hdr->cg < UHDR_CG_BT_709 || hdr->cg > UHDR_CG_BT_2100)  // (what uhdr_hip_tone_map_dev accepts for P010)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "No implementation available for color gamut %d", hdr->cg);
+  if (hdr->ct < UHDR_CT_LINEAR || hdr->ct > UHDR_CT_SRGB)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "No implementation available for color transfer %d", hdr->ct);
+  for (int i = 0; i < 3; i++) {
+    if (!base_ycc420->planes[i]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for base image plane %d", i);
+    const unsigned need = i ? (hdr->w + 1) / 2 : hdr->w;
+    if (base_ycc420->stride[i] < need) return err_status(UHDR_CODEC_INVALID_PARAM, "base image stride (%u) cannot be less than width (%u)", base_ycc420->stride[i], need);
+  }
+  UHDR_TRY(validate_image(hdr, "hdr intent"));
+  // the SDR rendition uhdr_hip_tone_map_dev would hand to generateGainMap: YCbCr 4:2:0, Display-P3, sRGB, full range
+  base_ycc420->fmt = UHDR_IMG_FMT_12bppYCbCr420; base_ycc420->cg = UHDR_CG_DISPLAY_P3; base_ycc420->ct = UHDR_CT_SRGB; base_ycc420->range = UHDR_CR_FULL_RANGE;
+  base_ycc420->w = hdr->w; base_ycc420->h = hdr->h;
+  if (!encode_api0_p010_layout_ok(view_of(hdr), view_of(base_ycc420)))
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused P010 API-0 front end reads quads with vector loads: even dimensions, even strides, a 4-byte aligned "
+                      "luma and chroma base of the HDR intent and a 2-byte aligned luma base of the base image; use tone_map + generate_gainmap");
+  HIP_TRY(hipSetDevice(c->device));
+  FusedParams p;
+  memset(&p.ycc, 0, sizeof p.ycc);
+  memset(&p.base_k, 0, sizeof p.base_k);
+  UHDR_TRY(fill_tone_map_params(c, hdr, &p.tm));
+  p.tm.sdr = view_mut_of(base_ycc420);
+  int use_base_cg = 1;
+  float hdr_white_nits;
+  UHDR_TRY(fill_gen_params(c, base_ycc420, hdr, cfg, &p.gen, &use_base_cg, &hdr_white_nits, /*sdr_in_registers=*/true));
+  fill_gainmap_desc(hdr, p.gen, gm);
+  if (gm->stride[0] < gm->w) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap stride (%u) cannot be less than its width (%u)", gm->stride[0], gm->w);
+  if (cfg->preset == UHDR_USAGE_REALTIME) {  // one pass: jpegr.cpp:724-737
+    for (int i = 0; i < 3; i++) {
+      md->max_content_boost[i] = hdr_white_nits / 203.0f;
+      md->min_content_boost[i] = 1.0f;
+      md->gamma[i] = cfg->gamma;
+      md->offset_sdr[i] = 0.0f;
+      md->offset_hdr[i] = 0.0f;
+    }
+    md->hdr_capacity_min = 1.0f;
+    md->hdr_capacity_max = cfg->target_disp_peak_nits != -1.0f ? cfg->target_disp_peak_nits / 203.0f : md->max_content_boost[0];
+    md->use_base_cg = use_base_cg;
+    p.gen.min_boost = md->min_content_boost[0];
+    p.gen.max_boost = md->max_content_boost[0];
+    p.gen.log2min = log2f(md->min_content_boost[0]);
+    p.gen.log2max = log2f(md->max_content_boost[0]);
+    p.gen.log2_range = (double)(p.gen.log2max - p.gen.log2min);
+    p.gen.log2_range_rcp = 1.0 / p.gen.log2_range;
+    UHDR_TRY(gain_step_table(c, p.gen, &p.gen.gain8));
+    p.gen.out = (uint8_t*)gm->planes[0];
+    p.gen.out_stride = gm->stride[0];
+    ProfScope ps(c, "encode_api0_fused");
+    HIP_TRY(launch_encode_api0_p010_fused(p, false, nullptr, c->stream));
+    return ok_status();
+  }
+  const size_t nfl = (size_t)p.gen.map_w * p.gen.map_h * (p.gen.multichannel ? 3 : 1);
+  UHDR_TRY(ensure(c->scratch[7], nfl * sizeof(float)));
+  UHDR_TRY(ensure(c->minmax, (6 + 2048 * 6) * sizeof(float)));
+  p.gen.gain_log2 = (float*)c->scratch[7].p;
+  p.gen.minmax = (float*)c->minmax.p;
+  int grid = 0;
+  {
+    ProfScope ps(c, "encode_api0_fused");
+    HIP_TRY(launch_encode_api0_p010_fused(p, true, &grid, c->stream));
+  }
+  UHDR_TRY(two_pass_tail(c, p.gen, grid, cfg, gm));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  float mm[6];
+  memcpy(mm, c->h_mm, sizeof mm);
+  note_table_stats(c, cfg);
+  return generate_gainmap_finalize_md(cfg, hdr->ct, use_base_cg, mm, md);
+}
+
+// -------------------------------------------------------------------------------------------------
 // API-1 encode chain fused (encode_api1_fused.hip): pass 1 -> range + tables -> map blocks; base blocks
 // -------------------------------------------------------------------------------------------------
 // With a communicator on the context (uhdr_hip_comm_init / _init_custom) the images are this rank's ROW STRIPE and the extrema
@@ -629,6 +713,106 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans(uhdr_hip_ctx_t* c, const uhdr_raw_i
   if (base_capacity > 0xFFFFFFF0u) base_capacity = 0xFFFFFFF0u;
   if (map_capacity > 0xFFFFFFF0u) map_capacity = 0xFFFFFFF0u;
   // the scans' device buffers: the image planes are free again once the FDCTs have run -- but those are only enqueued, so separate ones
+  UHDR_TRY(ensure(c->jpg[0], base_capacity + 64));
+  UHDR_TRY(ensure(c->jpg[4], map_capacity + 64));
+  size_t nbs = 0, nms = 0;
+  const uhdr_error_info_t e2 = uhdr_hip_huffman_encode2_dev(c, &sb, (uint8_t*)c->jpg[0].p, base_capacity, &nbs, &sm, (uint8_t*)c->jpg[4].p, map_capacity, &nms);
+  *base_bytes = nbs;
+  *map_bytes = nms;
+  if (e2.error_code != UHDR_CODEC_OK) return e2;
+  HIP_TRY(hipMemcpyAsync(base_scan, c->jpg[0].p, nbs, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(map_scan, c->jpg[4].p, nms, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ok_status();
+}
+
+// uhdr_hip_encode_api0_scans for every intent a fused front end takes: RGBA1010102 / RGBA half float go to the entry point above unchanged;
+// a P010 intent (what camera and video frames arrive as; jpegr.cpp:179-244 compresses the tone mapper's 4:2:0 planes as they are) goes up once,
+// uhdr_hip_encode_api0_p010_fused_dev leaves the 4:2:0 base image and the one-pass map in HBM, the base image's blocks come from the API-1
+// chain's launch_base_blocks (no conversion matrix), the map's as above, both scans are Huffman-coded concurrently (the base scan is
+// 2x2 / 1x1 / 1x1) and only the bytes come down.  Preset, sdr_is_601 and use_luminance are overridden as above.
+uhdr_error_info_t uhdr_hip_encode_api0_scans_any(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
+                                                 const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                 uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
+                                                 size_t map_capacity, size_t* map_bytes) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  if (!hdr || !cfg_in || !qt_base || !qt_map || !md || !base_scan || !map_scan || !base_bytes || !map_bytes)
+    return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
+  if (hdr->fmt != UHDR_IMG_FMT_24bppYCbCrP010)
+    return uhdr_hip_encode_api0_scans(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes);
+  if (cfg_in->map_dimension_scale_factor != 1)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs a full-resolution gain map (scale factor 1), received %d", cfg_in->map_dimension_scale_factor);
+  if (hdr->w == 0 || hdr->h == 0 || hdr->w % 16 || hdr->h % 16 || hdr->w > 65535 || hdr->h > 65535)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs P010 dimensions that are multiples of 16 (received %ux%u); use the operators", hdr->w, hdr->h);
+  if (c->comm != nullptr || c->comm_custom) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes");
+  UHDR_TRY(validate_image(hdr, "hdr intent"));
+  for (int t = 0; t < 2; t++)
+    for (int i = 0; i < 64; i++)
+      if (qt_base[t][i] == 0 || qt_base[t][i] > 255 || qt_map[t][i] == 0 || qt_map[t][i] > 255)
+        return err_status(UHDR_CODEC_INVALID_PARAM, "quantization table entry %d out of baseline range", i);
+  HIP_TRY(hipSetDevice(c->device));
+  uhdr_hip_encode_cfg_t cfg = *cfg_in;
+  cfg.preset = UHDR_USAGE_REALTIME;  // jpegr.cpp:207
+  cfg.sdr_is_601 = 0;                // jpegr.cpp:213-214
+  cfg.use_luminance = 0;
+  const unsigned w = hdr->w, h = hdr->h;
+  const int nch = cfg.use_multi_channel_gainmap ? 3 : 1;
+  uhdr_raw_image_t dh;
+  if (c->resident_on) UHDR_TRY(resident_write_back_all(c));
+  UHDR_TRY(stage_in(c, 1, hdr, &dh, true));
+  // device images: the base image's 4:2:0 planes and the map (rows padded to 64 samples), then the coefficient arrays
+  const size_t pitch = ((size_t)w + 63) & ~(size_t)63, cpitch = ((size_t)(w / 2) + 63) & ~(size_t)63;
+  const size_t plane_y = pitch * h, plane_c = cpitch * (h / 2);
+  UHDR_TRY(ensure(c->enc[1], plane_y + 2 * plane_c + 256));
+  UHDR_TRY(ensure(c->enc[2], pitch * (size_t)nch * h + 256));
+  const size_t nb[3] = {(size_t)(w / 8) * (h / 8), (size_t)(w / 16) * (h / 16), (size_t)(w / 16) * (h / 16)};
+  size_t off = 0, o_coef[6];
+  for (int i = 0; i < 3 + nch; i++) { o_coef[i] = off; off += ((i < 3 ? nb[i] : nb[0]) * 128 + 255) & ~(size_t)255; }
+  UHDR_TRY(ensure(c->enc[0], off));
+  uhdr_raw_image_t ycc, gm;
+  memset(&ycc, 0, sizeof ycc);
+  memset(&gm, 0, sizeof gm);
+  ycc.planes[0] = c->enc[1].p;
+  ycc.planes[1] = (uint8_t*)c->enc[1].p + plane_y;
+  ycc.planes[2] = (uint8_t*)c->enc[1].p + plane_y + plane_c;
+  ycc.stride[0] = (unsigned int)pitch;
+  ycc.stride[1] = ycc.stride[2] = (unsigned int)cpitch;
+  gm.planes[0] = c->enc[2].p;
+  gm.stride[0] = (unsigned int)pitch;
+  UHDR_TRY(uhdr_hip_encode_api0_p010_fused_dev(c, &dh, &cfg, &ycc, md, &gm));
+  if (sdr_cg) *sdr_cg = ycc.cg;  // what toneMap gives its SDR rendition (jpegr.cpp:2024-2030)
+  if (gainmap_desc) {
+    *gainmap_desc = gm;
+    gainmap_desc->planes[0] = gainmap_desc->planes[1] = gainmap_desc->planes[2] = nullptr;
+  }
+  int16_t* coef[6];
+  for (int i = 0; i < 3 + nch; i++) coef[i] = (int16_t*)((uint8_t*)c->enc[0].p + o_coef[i]);
+  {
+    ProfScope ps(c, "fdct_quant");
+    HIP_TRY(launch_base_blocks(view_of(&ycc), nullptr, qt_base[0], qt_base[1], coef, c->stream));
+  }
+  if (nch == 3) UHDR_TRY(uhdr_hip_fdct_quant_rgb_dev(c, &gm, qt_map[0], qt_map[1], coef[3], coef[4], coef[5]));
+  else UHDR_TRY(uhdr_hip_fdct_quant_dev(c, (const uint8_t*)gm.planes[0], (size_t)gm.stride[0], (int)(w / 8), (int)(h / 8), qt_map[0], coef[3]));
+  uhdr_hip_jpeg_scan_t sb, sm;
+  memset(&sb, 0, sizeof sb);
+  memset(&sm, 0, sizeof sm);
+  sb.num_components = 3;
+  sm.num_components = nch;
+  sb.w = sm.w = w;
+  sb.h = sm.h = h;
+  for (int i = 0; i < 3; i++) {
+    sb.coef[i] = coef[i];
+    sb.blocks_w[i] = (int)(i ? w / 16 : w / 8);
+    sb.blocks_h[i] = (int)(i ? h / 16 : h / 8);
+    sb.h_samp[i] = sb.v_samp[i] = i ? 1 : 2;
+  }
+  for (int i = 0; i < nch; i++) {
+    sm.coef[i] = coef[3 + i];
+    sm.blocks_w[i] = (int)(w / 8); sm.blocks_h[i] = (int)(h / 8);
+    sm.h_samp[i] = sm.v_samp[i] = 1;
+  }
+  if (base_capacity > 0xFFFFFFF0u) base_capacity = 0xFFFFFFF0u;
+  if (map_capacity > 0xFFFFFFF0u) map_capacity = 0xFFFFFFF0u;
   UHDR_TRY(ensure(c->jpg[0], base_capacity + 64));
   UHDR_TRY(ensure(c->jpg[4], map_capacity + 64));
   size_t nbs = 0, nms = 0;

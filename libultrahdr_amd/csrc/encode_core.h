@@ -61,6 +61,15 @@ __device__ __forceinline__ int lut_index_rpi(float x) {  // x already clamped to
   return rpi(x * (float)(N - 1));
 }
 
+// ScaleTo8Bit (jpegr.cpp:1979-1983): clamp((int)std::round(v * 255), 0, 255).  std::round is half away from zero, floor(t + 0.5)
+// (v_cvt_rpi_i32_f32, exact) is half up: they differ for negative t only, where both land at or below 0 and clamp to 0
+// (t in (-0.5, 0): both 0 / -0; t <= -0.5: both negative).
+__device__ __forceinline__ uint32_t scale_to_8bit(float v) {
+  int i = rpi(v * 255.0f), o;
+  asm("v_med3_i32 %0, %1, 0, %2" : "=v"(o) : "v"(i), "v"(255));
+  return (uint32_t)o;
+}
+
 // HDR inverse OETF through the LDS copy of the linearisation table (for HLG the host folded
 // hlgOotfApprox into it); has_lut == false: linear input, identityConversion.  The arguments are clamped to [0, 1]
 // by every caller (yuv_to_rgb / the 10-bit unpack), so the index needs no clip.

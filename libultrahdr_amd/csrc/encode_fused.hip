@@ -241,6 +241,130 @@ bool fused4_ok(const FusedParams& p, bool two_pass) {
   return ((size_t)p.gen.out_stride * nch) % 4 == 0 && al(p.gen.out, 4);
 }
 
+// ---- P010 intents: one lane per 2x2 quad ---------------------------------------------------------------------------------------------
+// JpegR::encodeJPEGR API-0 on a P010 intent (jpegr.cpp:179-244) is toneMap (P010 -> YCbCr 4:2:0) and generateGainMap; the 4:2:0
+// planes are compressed as they are.  Staged that is tonemap_p010_kernel + generate_quad_kernel: 3 + 1.5 bytes per pixel, then
+// 1.5 + 3 + 3 again (12 in all for a three-channel map), and every HDR pixel is fetched, converted and linearised twice.  Here a
+// lane carries its quad through both: one fetch_quad_p010, yuv_to_rgb + linearisation once per pixel (the gain side's hl IS the
+// tone mapper's l, as in the kernels above), tone curve, the four luma bytes and the two mean-chroma bytes of the base image, and
+// the gain of each pixel from those QUANTISED bytes with the arithmetic generate_quad_kernel applies to what fetch_quad_420
+// returns -- 3 bytes per pixel in, 1.5 + 3 out (7.5 in all), bit for bit the staged route's planes and map
+// (tests/test_gpu_api0_p010.py).  A wave walks tiles of 64 consecutive quads of one quad row, like the two staged kernels.
+// GAMUT is the HDR intent's gamut as the host's two parameter blocks see it (the SDR rendition is always Display-P3):
+//   0 Display-P3: no conversion anywhere; 1 BT.2100: the tone mapper converts to P3 and the gain side converts the SDR pixel
+//   to BT.2100; 2 BT.709: the tone mapper converts to P3 and the gain side converts the HDR pixel to P3.
+// LDS: HDR linearisation table 16 KB + direct pow table 18 KB + sample normalisation 5 KB + sRGB table 4 KB = 43.2 KB
+// (two pass), and one pass adds the gain step table's 16 KB: 59.0 KB.  The staged kernels run four (tone map, 39 KB, 64 VGPRs)
+// and three (generate, 25-41 KB, 80 VGPRs) 512-thread workgroups per CU, 32 and 24 waves.  A quad keeps its twelve linear HDR
+// values alive across the tone curve, so this kernel needs 69-75 VGPRs: six waves per SIMD, 24 per CU, generate_quad_kernel's
+// occupancy, is what the registers allow.  The tables fit that without any of them staying in global memory: two pass,
+// three 512-thread workgroups (130 of 160 KB); one pass, two 768-thread workgroups (118 KB) -- twelve waves share a table
+// set instead of eight.  (Every table is read several times per pixel, the step and pow tables through address forms that
+// exist for LDS only: encode_core.h step_code, srgb_oetf_lds.)  No scratch.
+struct alignas(16) FusedQuadLds {  // (16-byte table reads and copies)
+  float hdr[kInvOetfN];
+  double powt[kPowDirDoubles];
+  float srgb[kSrgbN];
+  UnormTables unorm;
+};
+constexpr int quad_block(bool two_pass) { return two_pass ? 512 : 768; }
+template <bool TWO_PASS, int GAMUT, int MC, bool LUT>
+__global__ __launch_bounds__(quad_block(TWO_PASS)) void encode_api0_p010_fused_kernel(const FusedParams p, float* partials) {
+  constexpr int kQuadBlock = quad_block(TWO_PASS);
+  __shared__ FusedQuadLds L;
+  __shared__ alignas(16) uint2 s_gain8[TWO_PASS ? 1 : kStepTabMax];
+  const uint32_t tid = threadIdx.x;
+  if constexpr (!TWO_PASS) stage_step_tab(s_gain8, p.gen.gain8, tid, kQuadBlock);
+  if (LUT) copy_to_lds(L.hdr, p.tm.hdr_inv_lut, (uint32_t)p.tm.hdr_inv_n, tid, kQuadBlock);
+  stage_pow_tab(L.powt, p.tm.math_tab, tid, kQuadBlock);
+  copy_to_lds(L.srgb, p.gen.srgb_lut, (uint32_t)kSrgbN, tid, kQuadBlock);
+  fill_unorm_tables(L.unorm, tid, kQuadBlock);
+  __syncthreads();
+  float mn[3] = {UHDR_RATIO_MIN_INIT, UHDR_RATIO_MIN_INIT, UHDR_RATIO_MIN_INIT}, mx[3] = {UHDR_RATIO_MAX_INIT, UHDR_RATIO_MAX_INIT, UHDR_RATIO_MAX_INIT};
+  const uint32_t qw = p.tm.hdr.w / 2, qh = p.tm.hdr.h / 2;
+  const uint32_t tiles_x = (qw + 63) / 64, tiles = tiles_x * qh;
+  const float inv_tx = 1.0f / (float)tiles_x;
+  const uint32_t lane = tid & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (kQuadBlock / 64) + (tid >> 6));
+  const uint32_t nwaves = gridDim.x * (kQuadBlock / 64);
+  const float lut_scale = (float)(p.tm.hdr_inv_n - 1);  // lut_index: x * (N - 1), round half up (encode_core.h: rpi)
+  uint8_t* yp = (uint8_t*)p.tm.sdr.p[0];
+  uint8_t* up = (uint8_t*)p.tm.sdr.p[1];
+  uint8_t* vp = (uint8_t*)p.tm.sdr.p[2];
+  for (uint32_t t = wave; t < tiles; t += nwaves) {
+    uint32_t qy = (uint32_t)((float)t * inv_tx);  // t / tiles_x for t < 2^24: the float estimate is off by at most one
+    if (qy * tiles_x > t) qy--;
+    if ((qy + 1) * tiles_x <= t) qy++;
+    const uint32_t qx = (t - qy * tiles_x) * 64 + lane;
+    if (qx >= qw) continue;
+    const QuadYuv hq = fetch_quad_p010(p.tm.hdr, qx, qy, &L.unorm);
+    Color3 l[4];  // linear HDR rgb: the tone mapper's input AND the gain side's HDR pixel
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const Color3 g = yuv_to_rgb(hq.px[k].r, hq.px[k].g, hq.px[k].b, p.tm.hdr_yuv);  // in [0, 1]
+      l[k] = g;
+      if (LUT) l[k] = Color3{L.hdr[rpi(g.r * lut_scale)], L.hdr[rpi(g.g * lut_scale)], L.hdr[rpi(g.b * lut_scale)]};
+    }
+    // ---- toneMap (jpegr.cpp:2147-2203), as tonemap_p010_kernel -----------------------------------------------------------------
+    float su = 0.0f, sv = 0.0f;
+    uint32_t yb[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {  // (row, column) order: the chroma sums accumulate like the reference's
+      const Color3 og = tone_curve<(GAMUT != 0) ? 1 : 0>(l[k], p.tm, L.powt);
+      Color3 yuv = rgb_to_yuv(og, p.tm.p3);
+      yuv.g += 0.5f;
+      yuv.b += 0.5f;
+      yb[k] = scale_to_8bit(yuv.r);
+      su += yuv.g;
+      sv += yuv.b;
+    }
+    su *= 0.25f;  // x / 4.0f == x * 0.25f exactly
+    sv *= 0.25f;
+    const uint32_t ub = scale_to_8bit(su), vb = scale_to_8bit(sv);
+    const size_t sy = p.tm.sdr.stride[0];
+    uint8_t* y0 = yp + (size_t)(qy * 2) * sy + qx * 2;  // (the host checked quad_layout_ok: 16-bit stores stay aligned)
+    *(uint16_t*)y0 = (uint16_t)(yb[0] | (yb[1] << 8));
+    *(uint16_t*)(y0 + sy) = (uint16_t)(yb[2] | (yb[3] << 8));
+    up[(size_t)qy * p.tm.sdr.stride[1] + qx] = (uint8_t)ub;
+    vp[(size_t)qy * p.tm.sdr.stride[2] + qx] = (uint8_t)vb;
+    // ---- generateGainMap on the quantised bytes (jpegr.cpp:753-818 / 866-931), as generate_quad_kernel reads them back ---------
+    const float cu = (float)((int)ub - 128) * (1 / 255.0f), cv = (float)((int)vb - 128) * (1 / 255.0f);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const Color3 s = yuv_to_rgb((float)(int)yb[k] * (1 / 255.0f), cu, cv, p.gen.sdr_yuv);  // in [0, 1]
+      Color3 sl = lut3_unit<kSrgbN>(s, L.srgb);
+      Color3 hl = l[k];
+      if (GAMUT == 1) {  // clipNegatives (jpegr.cpp:783-784) can only bite behind a matrix: table outputs are never negative
+        sl = mat3_apply(sl, p.gen.sdr_gamut);
+        sl.r = clip_neg(sl.r); sl.g = clip_neg(sl.g); sl.b = clip_neg(sl.b);
+      }
+      if (GAMUT == 2) {
+        hl = mat3_apply(hl, p.gen.hdr_gamut);
+        hl.r = clip_neg(hl.r); hl.g = clip_neg(hl.g); hl.b = clip_neg(hl.b);
+      }
+      gain_of_pixel<TWO_PASS, MC>(sl, hl, p.gen, p.gen.math_tab, 2 * qx + (k & 1), 2 * qy + (k >> 1), mn, mx, TWO_PASS ? nullptr : s_gain8);
+    }
+  }
+  if constexpr (TWO_PASS) reduce_block_minmax<kQuadBlock>(mn, mx, partials);
+}
+
+template <bool TWO_PASS, int GAMUT, int MC>
+void launch_p010_l(const FusedParams& p, int grid, float* partials, hipStream_t s) {
+  if (p.tm.hdr_inv_lut) hipLaunchKernelGGL((encode_api0_p010_fused_kernel<TWO_PASS, GAMUT, MC, true>), dim3(grid), dim3(quad_block(TWO_PASS)), 0, s, p, partials);
+  else hipLaunchKernelGGL((encode_api0_p010_fused_kernel<TWO_PASS, GAMUT, MC, false>), dim3(grid), dim3(quad_block(TWO_PASS)), 0, s, p, partials);
+}
+template <bool TWO_PASS, int GAMUT>
+void launch_p010_m(const FusedParams& p, int grid, float* partials, hipStream_t s) {
+  if (p.gen.multichannel) launch_p010_l<TWO_PASS, GAMUT, 1>(p, grid, partials, s);
+  else launch_p010_l<TWO_PASS, GAMUT, 0>(p, grid, partials, s);
+}
+template <bool TWO_PASS>
+void launch_p010(const FusedParams& p, int grid, float* partials, hipStream_t s) {
+  if (p.gen.sdr_gamut_on) launch_p010_m<TWO_PASS, 1>(p, grid, partials, s);
+  else if (p.gen.hdr_gamut_on) launch_p010_m<TWO_PASS, 2>(p, grid, partials, s);
+  else launch_p010_m<TWO_PASS, 0>(p, grid, partials, s);
+}
+
 }  // namespace
 
 int fused_grid(uint32_t tiles, int per_cu) {
@@ -281,6 +405,27 @@ hipError_t launch_encode_api0_fused(const FusedParams& p, bool two_pass, int* gr
     if (two_pass) hipLaunchKernelGGL((encode_api0_fused_kernel<UHDR_IMG_FMT_32bppRGBA1010102, true>), dim3(grid), dim3(kBlock), 0, s, p, partials);
     else hipLaunchKernelGGL((encode_api0_fused_kernel<UHDR_IMG_FMT_32bppRGBA1010102, false>), dim3(grid), dim3(kBlock), 0, s, p, partials);
   }
+  return hipGetLastError();
+}
+
+bool encode_api0_p010_layout_ok(const ImageView& hdr, const ImageView& base420) { return quad_layout_ok(hdr) && quad_layout_ok(base420); }
+
+// P010 intent -> p.tm.sdr (YCbCr 4:2:0 planes) + the map; p.ycc / p.base_k are unused.  The caller has checked quad_layout_ok for
+// p.tm.hdr and the base planes, scale factor 1 and the tables; two_pass / grid_out as for launch_encode_api0_fused.
+hipError_t launch_encode_api0_p010_fused(const FusedParams& p, bool two_pass, int* grid_out, hipStream_t s) {
+  if (p.tm.hdr.fmt != UHDR_IMG_FMT_24bppYCbCrP010 || p.tm.sdr.fmt != UHDR_IMG_FMT_12bppYCbCr420 || !quad_layout_ok(p.tm.hdr) || p.tm.sdr.w != p.tm.hdr.w ||
+      p.tm.sdr.h != p.tm.hdr.h || p.tm.sdr.stride[0] % 2 || ((uintptr_t)p.tm.sdr.p[0] % 2) || p.gen.scale != 1 || p.gen.map_w != p.tm.hdr.w ||
+      p.gen.map_h != p.tm.hdr.h || !p.gen.srgb_lut || !p.tm.math_tab)
+    return hipErrorInvalidValue;
+  // the three gamut modes: the SDR rendition is Display-P3, so the tone mapper converts exactly when the gain side does
+  if ((p.tm.gamut_on != 0) != (p.gen.sdr_gamut_on || p.gen.hdr_gamut_on) || (p.gen.sdr_gamut_on && p.gen.hdr_gamut_on)) return hipErrorInvalidValue;
+  const uint32_t wave_tiles = ((p.tm.hdr.w / 2 + 63) / 64) * (p.tm.hdr.h / 2);
+  const uint32_t wg_waves = (uint32_t)quad_block(two_pass) / 64;
+  const int grid = fused_grid((wave_tiles + wg_waves - 1) / wg_waves, two_pass ? 3 : 2);  // 43 / 59 KB of LDS tables per workgroup: 24 waves per CU either way
+  if (grid_out) *grid_out = grid;
+  float* partials = two_pass ? p.gen.minmax + 6 : nullptr;
+  if (two_pass) launch_p010<true>(p, grid, partials, s);
+  else launch_p010<false>(p, grid, partials, s);
   return hipGetLastError();
 }
 

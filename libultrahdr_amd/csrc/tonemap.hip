@@ -18,14 +18,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-// jpegr.cpp:1979-1983: clamp((int)std::round(v * 255), 0, 255).  std::round is half away from zero, floor(t + 0.5)
-// (v_cvt_rpi_i32_f32, exact) is half up: they differ for negative t only, where both land at or below 0 and clamp to 0
-// (t in (-0.5, 0): both 0 / -0; t <= -0.5: both negative).
-__device__ __forceinline__ uint32_t scale_to_8bit(float v) {
-  int i = rpi(v * 255.0f), o;
-  asm("v_med3_i32 %0, %1, 0, %2" : "=v"(o) : "v"(i), "v"(255));
-  return (uint32_t)o;
-}
 struct ToneLds {
   float hdr[kInvOetfN];  // RGBA1010102 input with p.lin10: the first 1024 entries hold code -> linear value
   double powt[kPowDirDoubles];  // exact_math.h: pow_direct_f32

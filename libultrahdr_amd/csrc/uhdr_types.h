@@ -261,6 +261,8 @@ hipError_t launch_selftest(int which, unsigned long long* out, uint32_t arg0, ui
                            hipStream_t s);  // selftest.hip
 int gen_partials_count(const GenParams& p);  // workgroups (= partials) launch_generate_gainmap(p, two_pass = true) writes
 hipError_t launch_encode_api0_fused(const FusedParams& p, bool two_pass, int* grid_out, hipStream_t s);
+bool encode_api0_p010_layout_ok(const ImageView& hdr, const ImageView& base420);  // quad_layout_ok (pixel_io.h) of both images
+hipError_t launch_encode_api0_p010_fused(const FusedParams& p, bool two_pass, int* grid_out, hipStream_t s);
 hipError_t launch_tone_map(const ToneMapParams& p, hipStream_t s);
 hipError_t launch_transform_yuv(const YuvXformParams& p, hipStream_t s);
 hipError_t launch_rgb_to_ycbcr(const RgbToYcbcrParams& p, hipStream_t s);

@@ -198,6 +198,46 @@ class UltraHdr:
         gm.sync_meta_from_raw()
         return sdr, ycc, md, gm
 
+    def encodeApi0FusedP010(self, hdr_intent: Image, base: Image = None, gm: Image = None, use_luminance=False):
+        """MI355X extension: toneMap (P010 -> YCbCr 4:2:0) + generateGainMap of an API-0 encode (jpegr.cpp:206-220) in one pass
+        over a device-resident P010 image (scale factor 1).  base / gm: the device images to fill (fresh 64-aligned ones when None).
+        Returns (base_ycc420, metadata, gainmap), bit-identical to the two separate calls."""
+        assert _is_dev(hdr_intent)
+        w, h, dev = hdr_intent.w, hdr_intent.h, hdr_intent.device
+        if base is None:
+            base = Image(A.UHDR_IMG_FMT_12bppYCbCr420, w, h, align=64, device=dev)
+        if gm is None:
+            fmt = A.UHDR_IMG_FMT_24bppRGB888 if self.mUseMultiChannelGainMap else A.UHDR_IMG_FMT_8bppYCbCr400
+            gm = Image(fmt, w, h, align=64, device=dev)
+        md = A.GainmapMetadata()
+        cfg = self.encode_cfg(False, use_luminance)
+        self._call(True, self.lib.uhdr_hip_encode_api0_p010_fused_dev, self.ctx.handle, C.byref(hdr_intent.raw), C.byref(cfg),
+                   C.byref(base.raw), C.byref(md), C.byref(gm.raw))
+        base.sync_meta_from_raw()
+        gm.sync_meta_from_raw()
+        return base, md, gm
+
+    def encodeApi0ScansAny(self, hdr_intent: Image, qt_base, qt_map, base_capacity: int, map_capacity: int, any_format=True):
+        """JpegR::encodeJPEGR API-0 (jpegr.cpp:179-244) without the container in ONE C call on a HOST intent: RGBA1010102, RGBA half
+        float or P010 (uhdr_hip_encode_api0_scans_any; any_format=False: uhdr_hip_encode_api0_scans, which declines P010).
+        Returns (base scan bytes, map scan bytes, metadata, gainmap descriptor, gamut of the SDR rendition); raises UhdrError --
+        UHDR_CODEC_MEM_ERROR carries the needed sizes in e.needed = (base, map)."""
+        assert not _is_dev(hdr_intent)
+        qb, qm = self._qt_pair(qt_base), self._qt_pair(qt_map)
+        md, desc, cg = A.GainmapMetadata(), A.RawImage(), C.c_int(0)
+        cfg = self.encode_cfg(False, False)
+        ob, om = np.empty(max(1, base_capacity), np.uint8), np.empty(max(1, map_capacity), np.uint8)
+        nb, nm = C.c_size_t(0), C.c_size_t(0)
+        fn = self.lib.uhdr_hip_encode_api0_scans_any if any_format else self.lib.uhdr_hip_encode_api0_scans
+        try:
+            self._call(False, fn, self.ctx.handle, C.byref(hdr_intent.raw), C.byref(cfg), C.c_void_p(qb.ctypes.data), C.c_void_p(qm.ctypes.data),
+                       C.byref(md), C.byref(desc), C.byref(cg), C.c_void_p(ob.ctypes.data), int(base_capacity), C.byref(nb),
+                       C.c_void_p(om.ctypes.data), int(map_capacity), C.byref(nm))
+        except A.UhdrError as e:
+            e.needed = (int(nb.value), int(nm.value))
+            raise
+        return ob[:nb.value].tobytes(), om[:nm.value].tobytes(), md, desc, int(cg.value)
+
     def encodeApi1Fused(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, want_map=True,
                         sdr_is_601=False, use_luminance=True):
         """MI355X extension: the sample -> coefficient part of an API-1 encode (jpegr.cpp:253-316) in four launches on
