@@ -269,10 +269,14 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
   if (getenv("UHDR_HIP_SEAM_NO_FUSED_ENCODE") || getenv("UHDR_HIP_SEAM_CPU_ENTROPY") || getenv("UHDR_HIP_SEAM_RESTART_INTERVAL") ||
       getenv("UHDR_HIP_SEAM_DEVICE_ENTROPY") || getenv("UHDR_HIP_SEAM_EAGER_DOWNLOADS"))
     return false;
-  if (sdr_intent->fmt != UHDR_IMG_FMT_12bppYCbCr420 || *scale_factor < 1) return false;
+  // an RGBA8888 SDR intent (its base image is YCbCr 4:4:4: convert_raw_input_to_ycbcr + convertYuv, jpegr.cpp:264-277) takes the fused route only
+  // when asked to: UHDR_HIP_SEAM_FUSED_RGBA_SDR; without it the per-stage seams run as before
+  const bool rgba = sdr_intent->fmt == UHDR_IMG_FMT_32bppRGBA8888 && getenv("UHDR_HIP_SEAM_FUSED_RGBA_SDR") != nullptr;
+  if ((!rgba && sdr_intent->fmt != UHDR_IMG_FMT_12bppYCbCr420) || *scale_factor < 1) return false;
   const unsigned w = sdr_intent->w, h = sdr_intent->h;
   const int s = *scale_factor;
-  if (w == 0 || h == 0 || w % 16 || h % 16 || w > 65535 || h > 65535) return false;
+  const unsigned grid = rgba ? 8 : 16;  // whole MCUs: 1x1 / 1x1 / 1x1 sampling for RGBA8888, 2x2 / 1x1 / 1x1 otherwise
+  if (w == 0 || h == 0 || w % grid || h % grid || w > 65535 || h > 65535) return false;
   const unsigned mw = w / (unsigned)s, mh = h / (unsigned)s;
   if (mw == 0 || mh == 0 || mw % 8 || mh % 8) return false;  // (the tiny-image fallback of jpegr.cpp:690-706 stays with generate_gainmap)
   if (base_icc_size > 65533 || map_icc_size > 65533 || (map_comment && strlen(map_comment) > 65533)) return false;
@@ -301,9 +305,9 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
   sb.num_components = 3;
   sb.w = w; sb.h = h;
   for (int i = 0; i < 3; i++) {
-    sb.blocks_w[i] = (int)(i ? w / 16 : w / 8);
-    sb.blocks_h[i] = (int)(i ? h / 16 : h / 8);
-    sb.h_samp[i] = sb.v_samp[i] = i ? 1 : 2;
+    sb.blocks_w[i] = (int)(i ? w / grid : w / 8);
+    sb.blocks_h[i] = (int)(i ? h / grid : h / 8);
+    sb.h_samp[i] = sb.v_samp[i] = (i || rgba) ? 1 : 2;
   }
   sm.num_components = nch;
   sm.w = mw; sm.h = mh;
@@ -316,7 +320,7 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
   // file = SOI + JFIF APP0 (20 bytes) | APP2 ICC | COM | DQT .. SOS | data | EOI  (jcmarker.c's order around the helper's markers)
   auto lead = [](size_t nh, size_t icc, const char* com) { return 20 + (icc ? 4 + icc : 0) + (com ? 4 + strlen(com) : 0) + (nh - 22); };
   const size_t lead_b = lead(nhb, base_icc ? base_icc_size : 0, nullptr), lead_m = lead(nhm, map_icc ? map_icc_size : 0, map_comment);
-  size_t cap_b = (size_t)w * h * 3 / 2 + (1u << 16), cap_m = (size_t)mw * mh * nch + (1u << 16);  // one byte per coefficient: never seen exceeded
+  size_t cap_b = (rgba ? (size_t)w * h * 3 : (size_t)w * h * 3 / 2) + (1u << 16), cap_m = (size_t)mw * mh * nch + (1u << 16);  // one byte per coefficient: never seen exceeded
   if (const char* e = getenv("UHDR_HIP_SEAM_TEST_SMALL_CAP")) {  // (tests: the second attempt below)
     const size_t div = (size_t)(atoi(e) > 1 ? atoi(e) : 16);
     cap_b /= div;
@@ -332,8 +336,8 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
     out->gainmap_data.reset(new (std::nothrow) unsigned char[lead_m + cap_m + 2]);
     if (!out->base_data || !out->gainmap_data) return false;
     nb = nm = 0;
-    *st = uhdr_hip_encode_api1_scans(cur(), sdr_intent, hdr_intent, &cfg, UHDR_CG_DISPLAY_P3, qt_base, qt_map, &md, &gm_desc, out->base_data.get() + lead_b,
-                                     cap_b, &nb, out->gainmap_data.get() + lead_m, cap_m, &nm);
+    *st = (rgba ? uhdr_hip_encode_api1_scans_any : uhdr_hip_encode_api1_scans)(cur(), sdr_intent, hdr_intent, &cfg, UHDR_CG_DISPLAY_P3, qt_base, qt_map, &md, &gm_desc,
+                                                                               out->base_data.get() + lead_b, cap_b, &nb, out->gainmap_data.get() + lead_m, cap_m, &nm);
     // a stream busier than the first guess: the encoder reports the size it needs -- once more with room for that (the device chain is ~1 ms at 4K;
     // the per-stage seams this used to fall to carry every intermediate over PCIe).  Any other MEM_ERROR (a device allocation) has no such sizes.
     if (st->error_code == UHDR_CODEC_MEM_ERROR && attempt == 0 && (nb > cap_b || nm > cap_m)) {

@@ -777,6 +777,38 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans(uhdr_hip_ctx_t* ctx, const uhdr_raw
                                              uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
                                              uint8_t* map_scan, size_t map_capacity, size_t* map_bytes);
 
+/* ---- The fused API-1 encode for both SDR intents API-1 takes (lib/src/jpegr.cpp:247-291): YCbCr 4:2:0 and RGBA8888 -----------------
+ * Three entry points with the parameter lists of uhdr_hip_encode_api1_fused_dev, uhdr_hip_encode_api1_scans and
+ * uhdr_hip_encode_api1_scans_dev (below).  A UHDR_IMG_FMT_12bppYCbCr420 SDR intent runs exactly what those run.  A
+ * UHDR_IMG_FMT_32bppRGBA8888 SDR intent -- what editors and render pipelines hand over, and the only SDR form that goes with a
+ * half-float HDR intent -- has a YCbCr 4:4:4 base image: the gain-map launches are the same (pass 1 reads RGBA8888), and ONE launch
+ * does convert_raw_input_to_ycbcr (gainmapmath.cpp:1447-1474, the coefficients of sdr->cg) + convertYuv to base_encoding on those
+ * bytes (both roundings to 8 bits kept) + FDCT / quantize of Y, Cb and Cr; the YCbCr planes never exist.  Coefficient blocks and
+ * metadata are bit-identical to uhdr_hip_generate_gainmap_dev + uhdr_hip_convert_raw_input_to_ycbcr_dev + uhdr_hip_convert_yuv_dev +
+ * uhdr_hip_fdct_quant_dev x 3 (+ the map's FDCT).
+ * RGBA8888: w and h multiples of 8; blocks->base_coef[0..2] are three (w/8)*(h/8) arrays; the base scan of the one-call forms is
+ * 1x1 / 1x1 / 1x1 (size the base buffer for three full-resolution components).  Rows of any pitch are taken: 16-byte aligned rows
+ * (base address, and a stride that is a multiple of 4 pixels) are read with 16-byte loads, others pixel by pixel; the base address
+ * is a multiple of 4.  UHDR_CODEC_UNSUPPORTED_FEATURE before anything is launched or uploaded: dimensions or map dimensions not
+ * multiples of 8, the one-pass preset, gamma != 1, any other SDR format (RGB888, YCbCr 4:4:4 ...), a context with a communicator
+ * (row stripes are 4:2:0 only).  The entry points without _any keep refusing RGBA8888. */
+uhdr_error_info_t uhdr_hip_encode_api1_fused_any_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                     const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                     const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                     const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm);
+uhdr_error_info_t uhdr_hip_encode_api1_scans_any(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                 const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                 const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                 uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                 uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
+                                                 uint8_t* map_scan, size_t map_capacity, size_t* map_bytes);
+uhdr_error_info_t uhdr_hip_encode_api1_scans_any_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                     const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                     const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                     uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                     uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
+                                                     uint8_t* map_scan, size_t map_capacity, size_t* map_bytes);
+
 /* JpegR::encodeJPEGR API-0 (lib/src/jpegr.cpp:179-244) for the HDR intents whose tone-mapped rendition is RGBA8888 -- RGBA1010102 and RGBA
  * half float -- in ONE call (round 6): host intent in, the two entropy-coded scans out (host buffers).  uhdr_hip_encode_api0_fused_dev (tone
  * map + one-pass gain map + RGB -> YCbCr 4:4:4) + FDCT / quantize + both scans Huffman-coded; what the facade binds at encodeJPEGR API-0.

@@ -167,6 +167,35 @@ class UltraHdr {
                                           base_bytes, map_scan, map_capacity, map_bytes);
   }
 
+  // The sample -> coefficient part of an API-1 encode on device-resident intents (uhdr_hip_encode_api1_fused_any_dev): the SDR intent is
+  // YCbCr 4:2:0 (multiples of 16) or RGBA8888 (multiples of 8; its base image is 4:4:4, three (w/8)*(h/8) coefficient arrays).
+  // blocks: device buffers; gainmap_img may be null.
+  uhdr_error_info_t encodeApi1FusedAny(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* hdr_intent, uhdr_color_gamut_t base_encoding,
+                                       const uint16_t qt_base[2][64], const uint16_t qt_map[2][64], const uhdr_hip_api1_blocks_t* blocks,
+                                       uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_raw_image_t* gainmap_img, bool sdr_is_601 = false,
+                                       bool use_luminance = true) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, sdr_is_601 ? 1 : 0, use_luminance ? 1 : 0};
+    return uhdr_hip_encode_api1_fused_any_dev(mCtx, sdr_intent, hdr_intent, &cfg, base_encoding, qt_base, qt_map, blocks, gainmap_metadata, gainmap_img);
+  }
+
+  // JpegR::encodeJPEGR API-1 without the container in one call, for a YCbCr 4:2:0 or an RGBA8888 SDR intent (base scan 1x1 / 1x1 / 1x1):
+  // dev == false: host intents and host scan buffers (uhdr_hip_encode_api1_scans_any); dev == true: device intents and device buffers
+  // (uhdr_hip_encode_api1_scans_any_dev).  qt_base / qt_map: {luma, chroma} tables.
+  uhdr_error_info_t encodeApi1ScansAny(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* hdr_intent, uhdr_color_gamut_t base_encoding,
+                                       const uint16_t qt_base[2][64], const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* gainmap_metadata,
+                                       uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
+                                       uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, bool dev = false, bool sdr_is_601 = false,
+                                       bool use_luminance = true) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, sdr_is_601 ? 1 : 0, use_luminance ? 1 : 0};
+    return (dev ? uhdr_hip_encode_api1_scans_any_dev : uhdr_hip_encode_api1_scans_any)(mCtx, sdr_intent, hdr_intent, &cfg, base_encoding, qt_base, qt_map,
+                                                                                       gainmap_metadata, gainmap_desc, base_scan, base_capacity,
+                                                                                       base_bytes, map_scan, map_capacity, map_bytes);
+  }
+
   uhdr_error_info_t convertYuv(uhdr_raw_image_t* image, uhdr_color_gamut_t src_encoding, uhdr_color_gamut_t dst_encoding) {
     if (!mCtx) return mCreateStatus;
     return uhdr_hip_convert_yuv(mCtx, image, src_encoding, dst_encoding);

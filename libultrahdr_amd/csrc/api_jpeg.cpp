@@ -285,13 +285,20 @@ uhdr_error_info_t uhdr_hip_encode_api0_p010_fused_dev(uhdr_hip_ctx_t* c, const u
 // are merged across ranks between the passes, exactly as in uhdr_hip_generate_gainmap_striped_dev: reduce -> ONE all-reduce(min)
 // over {min, -max} -> finalize + tables.  Every rank takes part in that exchange whatever happens locally (a rank that
 // failed validation, or whose stripe is empty -- h == 0 --, contributes the identity), and reports its error afterwards.
-uhdr_error_info_t uhdr_hip_encode_api1_fused_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
-                                                 const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
-                                                 const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
-                                                 const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
+//
+// any_sdr (uhdr_hip_encode_api1_fused_any_dev): a packed RGBA8888 SDR intent is taken as well -- the other form API-1 accepts (jpegr.cpp:247-291),
+// whose base image is YCbCr 4:4:4: the gain-map passes read it as they are (pass 1 fetches RGBA8888), launch_base_blocks_rgba is the base
+// launch (three (w / 8) x (h / 8) coefficient arrays), dimensions are multiples of 8, whole images only.
+static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm, bool any_sdr) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   HIP_TRY(hipSetDevice(c->device));
   const bool striped = c->comm != nullptr || c->comm_custom;
+  const bool rgba = any_sdr && sdr && sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888;
+  if (rgba && striped) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes of 4:2:0 base images; an RGBA8888 SDR intent is encoded whole");
+  Rgb2Yuv base_k;
   GenParams p;
   int use_base_cg = 1, nch = 1;
   float hdr_white_nits = 0;
@@ -301,9 +308,17 @@ uhdr_error_info_t uhdr_hip_encode_api1_fused_dev(uhdr_hip_ctx_t* c, const uhdr_r
   bool convert = false, empty = false;
   auto prepare = [&]() -> uhdr_error_info_t {
     if (!sdr || !hdr || !cfg || !qt_base || !qt_map || !blocks || !md) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
-    if (sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420 || sdr->w % 16 || sdr->h % 16 || sdr->w == 0)
+    if (rgba) {
+      if (sdr->w % 8 || sdr->h % 8 || sdr->w == 0)
+        return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_32bppRGBA8888 SDR intent whose dimensions are multiples of 8 "
+                          "(received %ux%u); use the operators", sdr->w, sdr->h);
+    } else if (any_sdr && sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420) {
+      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_12bppYCbCr420 or UHDR_IMG_FMT_32bppRGBA8888 SDR intent "
+                        "(received format %d); use the operators", sdr->fmt);
+    } else if (sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420 || sdr->w % 16 || sdr->h % 16 || sdr->w == 0) {
       return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_12bppYCbCr420 base image whose dimensions are multiples of 16 "
                         "(received format %d, %ux%u); use the operators", sdr->fmt, sdr->w, sdr->h);
+    }
     if (cfg->preset == UHDR_USAGE_REALTIME) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain is the two-pass (best quality) encode; one pass: generate_gainmap + fdct_quant");
     if (cfg->gamma != 1.0f) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs gain-map gamma 1 (received %f); use the operators", cfg->gamma);
     for (int t = 0; t < 2; t++)
@@ -321,7 +336,12 @@ uhdr_error_info_t uhdr_hip_encode_api1_fused_dev(uhdr_hip_ctx_t* c, const uhdr_r
       return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs map dimensions that are multiples of 8 (%ux%u at scale factor %u); use the operators",
                         p.map_w, p.map_h, p.scale);
     nch = p.multichannel ? 3 : 1;
-    if (((uintptr_t)sdr->planes[0] | sdr->stride[0]) & 1) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain reads luma in 16-bit pairs: even base address and stride");
+    if (rgba) {  // any pitch: rows that are not 16-byte aligned are read dword by dword (encode_api1_fused.hip)
+      if ((uintptr_t)sdr->planes[0] & 3) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain reads RGBA8888 pixels as 32-bit words: base address a multiple of 4");
+      base_k = host::rgb2yuv_coeffs(sdr->cg);
+    } else if (((uintptr_t)sdr->planes[0] | sdr->stride[0]) & 1) {
+      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain reads luma in 16-bit pairs: even base address and stride");
+    }
     for (int i = 0; i < 3; i++)
       if (!blocks->base_coef[i] || ((uintptr_t)blocks->base_coef[i] & 15)) return err_status(UHDR_CODEC_INVALID_PARAM, "base coefficient buffer %d is null or not 16-byte aligned", i);
     for (int i = 0; i < nch; i++)
@@ -351,6 +371,10 @@ uhdr_error_info_t uhdr_hip_encode_api1_fused_dev(uhdr_hip_ctx_t* c, const uhdr_r
   if (!c->h_mm) HIP_TRY(hipHostMalloc((void**)&c->h_mm, 9 * sizeof(float), hipHostMallocDefault));
   uhdr_error_info_t local = prepare();
   if (local.error_code != UHDR_CODEC_OK && !striped) return local;
+  auto base_launch = [&](hipStream_t s) -> hipError_t {
+    if (rgba) return launch_base_blocks_rgba(view_of(sdr), base_k, convert ? &conv : nullptr, qt_base[0], qt_base[1], blocks->base_coef, s);
+    return launch_base_blocks(view_of(sdr), convert ? &conv : nullptr, qt_base[0], qt_base[1], blocks->base_coef, s);
+  };
   bool run = local.error_code == UHDR_CODEC_OK && !empty;
   float* merged = (float*)c->exchange.p;
   float* final_mm = (float*)((char*)c->exchange.p + 192);
@@ -376,8 +400,8 @@ uhdr_error_info_t uhdr_hip_encode_api1_fused_dev(uhdr_hip_ctx_t* c, const uhdr_r
       if (e == hipSuccess) e = hipStreamWaitEvent(x->stream, c->aux_ev, 0);
       if (e == hipSuccess) {
         {
-          ProfScope ps(x, "fdct_quant");
-          note_hip(launch_base_blocks(view_of(sdr), convert ? &conv : nullptr, qt_base[0], qt_base[1], blocks->base_coef, x->stream), "base blocks");
+          ProfScope ps(x, rgba ? "base_blocks_rgba" : "fdct_quant");  // (a family of its own: the launch can be read apart from the map's blocks)
+          note_hip(base_launch(x->stream), "base blocks");
         }
         note_hip(hipEventRecord(c->aux_ev2, x->stream), "base blocks event");
         side = x;
@@ -436,7 +460,11 @@ uhdr_error_info_t uhdr_hip_encode_api1_fused_dev(uhdr_hip_ctx_t* c, const uhdr_r
     ProfScope ps(c, "fdct_quant");
     note_hip(launch_map_blocks(p.gain_log2, (const AffineDev*)c->affine.p, c->d_math, nch, (int)(p.map_w / 8), (int)(p.map_h / 8), qt_map[0], qt_map[1],
                                blocks->map_coef, map_out, map_stride, c->stream), "map blocks");
-    if (!side) note_hip(launch_base_blocks(view_of(sdr), convert ? &conv : nullptr, qt_base[0], qt_base[1], blocks->base_coef, c->stream), "base blocks");
+    if (!side && !rgba) note_hip(base_launch(c->stream), "base blocks");
+  }
+  if (run && xchg.error_code == UHDR_CODEC_OK && !side && rgba) {
+    ProfScope ps(c, "base_blocks_rgba");
+    note_hip(base_launch(c->stream), "base blocks");
   }
   if (side) {  // the base image's coefficients belong to this stream's order from here on (whatever happened above)
     note_hip(hipStreamWaitEvent(c->stream, c->aux_ev2, 0), "base blocks wait");
@@ -461,6 +489,18 @@ uhdr_error_info_t uhdr_hip_encode_api1_fused_dev(uhdr_hip_ctx_t* c, const uhdr_r
   if (run) note_table_stats(c, cfg);
   return generate_gainmap_finalize_md(cfg, hdr->ct, use_base_cg, mm, md);
 }
+uhdr_error_info_t uhdr_hip_encode_api1_fused_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                 const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                 const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                 const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
+  return encode_api1_fused_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, blocks, md, gm, false);
+}
+uhdr_error_info_t uhdr_hip_encode_api1_fused_any_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                     const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                     const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                     const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
+  return encode_api1_fused_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, blocks, md, gm, true);
+}
 
 // JpegR::encodeJPEGR API-1 (jpegr.cpp:253-316) from its two raw intents to its two entropy-coded scans in ONE entry point: the
 // intents go up once (fast_h2d), the fused chain leaves coefficient blocks in HBM, the marker-less Huffman coder turns them into
@@ -468,7 +508,7 @@ uhdr_error_info_t uhdr_hip_encode_api1_fused_dev(uhdr_hip_ctx_t* c, const uhdr_r
 static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
                                                 uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
                                                 uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
-                                                size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, bool dev = false);
+                                                size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, bool dev = false, bool any_sdr = false);
 // ... and on DEVICE-resident intents, into DEVICE buffers (round 6): one call per direction of the round trip, so that no binding
 // layer sits between the stages (a Python caller's 30-100 us between two entry points were a third of a 4K round trip)
 uhdr_error_info_t uhdr_hip_encode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
@@ -477,6 +517,23 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_r
                                                  size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
   return encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
                                 map_bytes, true);
+}
+uhdr_error_info_t uhdr_hip_encode_api1_scans_any_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                     uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                     uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                                     size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
+  return encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
+                                map_bytes, true, true);
+}
+uhdr_error_info_t uhdr_hip_encode_api1_scans_any(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                 uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                 uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                                 size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const uhdr_error_info_t r = encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes,
+                                                     map_scan, map_capacity, map_bytes, false, true);
+  if (c) c->stats.last_encode_api1_scans_ns = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+  return r;
 }
 uhdr_error_info_t uhdr_hip_encode_api1_scans(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
                                              uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
@@ -491,12 +548,20 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans(uhdr_hip_ctx_t* c, const uhdr_raw_i
 static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
                                                 uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
                                                 uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
-                                                size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, bool dev) {
+                                                size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, bool dev, bool any_sdr) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!sdr || !hdr || !cfg || !qt_base || !qt_map || !md || !base_scan || !map_scan || !base_bytes || !map_bytes)
     return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
   // what the fused chain would decline is declined before 37 MB go up for nothing (the same conditions, uhdr_hip_encode_api1_fused_dev)
-  if (sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420 || sdr->w % 16 || sdr->h % 16 || sdr->w == 0 || sdr->h == 0)
+  const bool rgba = any_sdr && sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888;  // base image 4:4:4: a 1x1 / 1x1 / 1x1 scan
+  if (rgba) {
+    if (sdr->w % 8 || sdr->h % 8 || sdr->w == 0 || sdr->h == 0)
+      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_32bppRGBA8888 SDR intent whose dimensions are multiples of 8 "
+                        "(received %ux%u); use the operators", sdr->w, sdr->h);
+  } else if (any_sdr && sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420) {
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_12bppYCbCr420 or UHDR_IMG_FMT_32bppRGBA8888 SDR intent "
+                      "(received format %d); use the operators", sdr->fmt);
+  } else if (sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420 || sdr->w % 16 || sdr->h % 16 || sdr->w == 0 || sdr->h == 0)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_12bppYCbCr420 base image whose dimensions are multiples of 16 "
                       "(received format %d, %ux%u); use the operators", sdr->fmt, sdr->w, sdr->h);
   if (cfg->preset == UHDR_USAGE_REALTIME) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain is the two-pass (best quality) encode");
@@ -506,7 +571,9 @@ static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs map dimensions that are multiples of 8 (scale factor %d on %ux%u)", scale, sdr->w, sdr->h);
   if (hdr->w != sdr->w || hdr->h != sdr->h)
     return err_status(UHDR_CODEC_INVALID_PARAM, "sdr intent resolution %ux%u and hdr intent resolution %ux%u do not match", sdr->w, sdr->h, hdr->w, hdr->h);
-  if (c->comm != nullptr || c->comm_custom) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes (uhdr_hip_encode_api1_fused_dev)");
+  if (c->comm != nullptr || c->comm_custom)
+    return rgba ? err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes of 4:2:0 base images; an RGBA8888 SDR intent is encoded whole")
+                : err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes (uhdr_hip_encode_api1_fused_dev)");
   UHDR_TRY(validate_image(sdr, "sdr intent"));
   UHDR_TRY(validate_image(hdr, "hdr intent"));
   HIP_TRY(hipSetDevice(c->device));
@@ -522,7 +589,8 @@ static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
     UHDR_TRY(stage_in(c, 1, hdr, &dh, true));
   }
   // coefficient arrays: base Y, Cb, Cr, then the map's 1 or 3 components; 256-byte aligned
-  const size_t nb[3] = {(size_t)(w / 8) * (h / 8), (size_t)(w / 16) * (h / 16), (size_t)(w / 16) * (h / 16)};
+  const unsigned cdiv = rgba ? 8 : 16;  // a chroma block's width in luma samples
+  const size_t nb[3] = {(size_t)(w / 8) * (h / 8), (size_t)(w / cdiv) * (h / cdiv), (size_t)(w / cdiv) * (h / cdiv)};
   const size_t nm = (size_t)(mw / 8) * (mh / 8);
   size_t off = 0, o_base[3], o_map[3] = {0, 0, 0};
   for (int i = 0; i < 3; i++) { o_base[i] = off; off += (nb[i] * 128 + 255) & ~(size_t)255; }
@@ -542,9 +610,9 @@ static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   sb.w = w; sb.h = h;
   for (int i = 0; i < 3; i++) {
     sb.coef[i] = blocks.base_coef[i];
-    sb.blocks_w[i] = (int)(i ? w / 16 : w / 8);
-    sb.blocks_h[i] = (int)(i ? h / 16 : h / 8);
-    sb.h_samp[i] = sb.v_samp[i] = i ? 1 : 2;
+    sb.blocks_w[i] = (int)(i ? w / cdiv : w / 8);
+    sb.blocks_h[i] = (int)(i ? h / cdiv : h / 8);
+    sb.h_samp[i] = sb.v_samp[i] = (i || rgba) ? 1 : 2;
   }
   sm.num_components = nch;
   sm.w = mw; sm.h = mh;
@@ -576,7 +644,7 @@ static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   c->side_job_posted = false;
   c->defer_md = dev;  // device-resident callers: no host synchronisation between the chain and the entropy stage
   c->deferred_md.valid = false;
-  const uhdr_error_info_t fs = uhdr_hip_encode_api1_fused_dev(c, &ds, &dh, cfg, base_encoding, qt_base, qt_map, &blocks, md, nullptr);
+  const uhdr_error_info_t fs = encode_api1_fused_impl(c, &ds, &dh, cfg, base_encoding, qt_base, qt_map, &blocks, md, nullptr, any_sdr);
   c->defer_md = false;
   c->on_side_launched = nullptr;
   const bool base_posted = c->side_job_posted;

@@ -12,6 +12,8 @@
 //   base_blocks_kernel  convertYuv + FDCT / quantize of Y, Cb, Cr in ONE launch: a wave takes two 16 x 16 MCUs, converts their
 //                       128 quads (transformYuv420's arithmetic, gainmapmath.cpp:686-748) into an LDS tile and transforms
 //                       the 8 luma + 4 chroma blocks from there; the converted planes never exist in HBM
+//   base_blocks_rgba_kernel  the same for a packed RGBA8888 intent, whose base image is 4:4:4: convert_raw_input_to_ycbcr + convertYuv +
+//                       FDCT / quantize from registers (below; tests/test_gpu_api1_rgba.py)
 //
 // Coefficients are bit-identical to the unfused chain (tests/test_gpu_parity.py::test_api1_fused_chain_equals_the_operators).
 #include <string.h>
@@ -363,6 +365,92 @@ __global__ __launch_bounds__(kBlock) void base_blocks_kernel(const BaseBlocksPar
   }
 }
 
+// ---- the base image from a packed RGBA8888 intent: convert_raw_input_to_ycbcr + convertYuv + FDCT of Y, Cb, Cr in one launch ----------
+// API-1 with an RGBA8888 SDR intent (jpegr.cpp:247-291) compresses a YCbCr 4:4:4 rendition of it: convert_raw_input_to_ycbcr
+// (gainmapmath.cpp:1447-1474) writes full-range bytes in the intent's own gamut, convertYuv (transformYuv444) rewrites them in the base
+// encoding -- a second rounding to bytes -- and the three planes go to the FDCT.  Staged, that is three launches and 22 B/px; here a wave
+// owns a strip of eight horizontally adjacent 8 x 8 blocks, lane (row rr, block rb) loads the eight pixels of row rr of block rb, converts
+// them in registers with the staged kernels' arithmetic (convert.hip: rgb_to_ycbcr444_wide_kernel<false>, transform_yuv444_kernel; both
+// roundings kept) and is the lane that runs the row pass of that block row: the samples never touch LDS or HBM, only the transposes of
+// column_pass_and_quantize use the wave's workspace, three times per strip.  4 B/px in, 6 B/px out.
+// Rows whose base address and pitch are multiples of 16 bytes are read with two 16-byte loads per lane (VEC); any other pitch takes the
+// same kernel with eight dword loads (pixels are 32-bit words: the base address is a multiple of 4, the launcher's caller checks).
+struct BaseBlocksRgbaParams {
+  const uint32_t* src;     // packed RGBA8888
+  uint32_t stride;         // pixels
+  int bw, bh;              // blocks (w / 8, h / 8)
+  int convert;             // 0: convert_raw_input_to_ycbcr's bytes go to the FDCT as they are
+  Rgb2Yuv k;               // the intent's gamut (host_tables.cpp: rgb2yuv_coeffs)
+  Mat3 c;                  // convertYuv's coefficients (host_tables.cpp: yuv_encoding_matrix)
+  int16_t* coef[3];
+  QuantPair q;
+};
+
+__device__ __forceinline__ float clipf255(float v) { return (v < 0.0f) ? 0.0f : ((v > 255.0f) ? 255.0f : v); }  // convert.hip: clipf
+
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void base_blocks_rgba_kernel(const BaseBlocksRgbaParams p) {
+  __shared__ int s_ws[kBlock / 64][8 * 8 * 9];
+  __shared__ uint2 s_q[2][64];
+  __shared__ float s_u8[256];  // i / 255.0f, the device's correctly rounded division (pixel_io.h: UnormTables)
+  if (threadIdx.x < 128) s_q[threadIdx.x >> 6][threadIdx.x & 63] = uint2{p.q.qv[threadIdx.x >> 6][threadIdx.x & 63], p.q.qm[threadIdx.x >> 6][threadIdx.x & 63]};
+  for (uint32_t i = threadIdx.x; i < 256; i += kBlock) s_u8[i] = (float)i / 255.0f;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int* ws = s_ws[wv];
+  const int groups_x = (p.bw + 7) >> 3, total = groups_x * p.bh;
+  const int gwave = blockIdx.x * (kBlock / 64) + wv, nwaves = gridDim.x * (kBlock / 64);
+  const int rr = lane >> 3, rb = lane & 7;
+  const Rgb2Yuv k = p.k;
+  const float k255 = 1 / 255.0f;
+  for (int t = gwave; t < total; t += nwaves) {
+    const int by = t / groups_x, gx = t - by * groups_x;
+    const int bx = gx * 8 + rb;
+    const bool active = bx < p.bw;
+    int comp[3][8];
+    if (active) {
+      const uint32_t* s0 = p.src + ((size_t)(by * 8 + rr) * p.stride + (size_t)bx * 8);
+      uint32_t px[8];
+      if (VEC) {
+        const uint4 a = *(const uint4*)s0, b = *(const uint4*)(s0 + 4);
+        px[0] = a.x; px[1] = a.y; px[2] = a.z; px[3] = a.w; px[4] = b.x; px[5] = b.y; px[6] = b.z; px[7] = b.w;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; j++) px[j] = s0[j];
+      }
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const Color3 e = {s_u8[px[j] & 0xff], s_u8[(px[j] >> 8) & 0xff], s_u8[(px[j] >> 16) & 0xff]};
+        const Color3 q = rgb_to_yuv(e, k);
+        int yy = (int)(uint32_t)clipf255(q.r * 255.0f + 0.5f);
+        int uu = (int)(uint32_t)clipf255(q.g * 255.0f + 0.5f + 128.0f);
+        int vv = (int)(uint32_t)clipf255(q.b * 255.0f + 0.5f + 128.0f);
+        if (p.convert) {  // transformYuv444 on those bytes
+          const Color3 o = mat3_apply({(float)yy * k255, (float)(uu - 128) * k255, (float)(vv - 128) * k255}, p.c);
+          yy = (int)st8(o.r * 255.0f + 0.5f);
+          uu = (int)st8(o.g * 255.0f + 128.0f + 0.5f);
+          vv = (int)st8(o.b * 255.0f + 128.0f + 0.5f);
+        }
+        comp[0][j] = yy - 128;
+        comp[1][j] = uu - 128;
+        comp[2][j] = vv - 128;
+      }
+    }
+#pragma unroll
+    for (int ci = 0; ci < 3; ci++) {
+      int out[8], v[8];
+      if (active) {
+        fdct_1d<0>(comp[ci], out);
+      } else {
+#pragma unroll
+        for (int c = 0; c < 8; c++) out[c] = 0;
+      }
+      column_pass_and_quantize(ws, lane, out, s_q[ci == 0 ? 0 : 1], v);
+      if (active) store_coef_row(p.coef[ci] + ((size_t)by * p.bw + bx) * 64 + rr * 8, v);
+    }
+  }
+}
+
 int resident_grid(int total_wave_items, int per_cu) {
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
@@ -404,6 +492,27 @@ hipError_t launch_base_blocks(const ImageView& yuv420, const Mat3* c, const uint
   fill_quant(qt_luma, qt_chroma, &p.q);
   const int grid = resident_grid(((p.mcus_x + 1) / 2) * p.mcus_y, 8);
   hipLaunchKernelGGL(base_blocks_kernel, dim3(grid), dim3(kBlock), 0, s, p);
+  return hipGetLastError();
+}
+
+// packed RGBA8888 (w, h multiples of 8; stride in pixels; base address a multiple of 4) -> convert_raw_input_to_ycbcr with the coefficients k
+// of the image's gamut -> [convertYuv with matrix c ->] quantized coefficients of Y, Cb, Cr, each on a (w / 8) x (h / 8) grid
+hipError_t launch_base_blocks_rgba(const ImageView& rgba, const Rgb2Yuv& k, const Mat3* c, const uint16_t* qt_luma, const uint16_t* qt_chroma,
+                                   int16_t* const coef[3], hipStream_t s) {
+  BaseBlocksRgbaParams p;
+  memset(&p, 0, sizeof p);
+  p.src = (const uint32_t*)rgba.p[0];
+  p.stride = rgba.stride[0];
+  p.bw = (int)(rgba.w / 8); p.bh = (int)(rgba.h / 8);
+  p.k = k;
+  p.convert = c ? 1 : 0;
+  if (c) p.c = *c;
+  for (int i = 0; i < 3; i++) p.coef[i] = coef[i];
+  fill_quant(qt_luma, qt_chroma, &p.q);
+  const int grid = resident_grid(((p.bw + 7) / 8) * p.bh, 7);  // 66 VGPRs: seven waves per SIMD, i.e. seven 4-wave workgroups per CU are resident
+  const bool vec = ((uintptr_t)rgba.p[0] % 16) == 0 && rgba.stride[0] % 4 == 0;
+  if (vec) hipLaunchKernelGGL((base_blocks_rgba_kernel<true>), dim3(grid), dim3(kBlock), 0, s, p);
+  else hipLaunchKernelGGL((base_blocks_rgba_kernel<false>), dim3(grid), dim3(kBlock), 0, s, p);
   return hipGetLastError();
 }
 

@@ -257,6 +257,8 @@ hipError_t launch_map_blocks(const float* ratio, const AffineDev* dev, const dou
                              const uint16_t* qt_chroma, int16_t* const coef[3], uint8_t* map_out, uint32_t out_stride, hipStream_t s);
 hipError_t launch_base_blocks(const ImageView& yuv420, const Mat3* c, const uint16_t* qt_luma, const uint16_t* qt_chroma, int16_t* const coef[3],
                               hipStream_t s);
+hipError_t launch_base_blocks_rgba(const ImageView& rgba, const Rgb2Yuv& k, const Mat3* c, const uint16_t* qt_luma, const uint16_t* qt_chroma,
+                                   int16_t* const coef[3], hipStream_t s);
 hipError_t launch_selftest(int which, unsigned long long* out, uint32_t arg0, uint32_t arg1, uint32_t seed, const double* math_tab, const AffineDev* dev,
                            hipStream_t s);  // selftest.hip
 int gen_partials_count(const GenParams& p);  // workgroups (= partials) launch_generate_gainmap(p, two_pass = true) writes

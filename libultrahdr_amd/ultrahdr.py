@@ -239,7 +239,7 @@ class UltraHdr:
         return ob[:nb.value].tobytes(), om[:nm.value].tobytes(), md, desc, int(cg.value)
 
     def encodeApi1Fused(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, want_map=True,
-                        sdr_is_601=False, use_luminance=True):
+                        sdr_is_601=False, use_luminance=True, _any=False):
         """MI355X extension: the sample -> coefficient part of an API-1 encode (jpegr.cpp:253-316) in four launches on
         device-resident images -- two-pass generateGainMap fused with the map's rgb->ycc + FDCT, convertYuv fused with the base
         image's three FDCTs.  qt_base / qt_map: (luma, chroma) quantization tables.  Returns (base coefficient tensors [3],
@@ -250,7 +250,8 @@ class UltraHdr:
         w, h, dev = sdr_intent.w, sdr_intent.h, sdr_intent.buf.device
         mw, mh = self.gainmap_dims(w, h)
         nch = 3 if self.mUseMultiChannelGainMap else 1
-        base = [torch.empty((h // 8, w // 8, 64), dtype=torch.int16, device=dev)] + [torch.empty((h // 16, w // 16, 64), dtype=torch.int16, device=dev) for _ in range(2)]
+        cdiv = 8 if _any and sdr_intent.fmt == A.UHDR_IMG_FMT_32bppRGBA8888 else 16  # an RGBA8888 intent's base image is 4:4:4
+        base = [torch.empty((h // 8, w // 8, 64), dtype=torch.int16, device=dev)] + [torch.empty((h // cdiv, w // cdiv, 64), dtype=torch.int16, device=dev) for _ in range(2)]
         mapc = [torch.empty((mh // 8, mw // 8, 64), dtype=torch.int16, device=dev) for _ in range(nch)]
         blocks = A.Api1Blocks()
         for i in range(3):
@@ -263,12 +264,20 @@ class UltraHdr:
             gm = Image(A.UHDR_IMG_FMT_24bppRGB888 if nch == 3 else A.UHDR_IMG_FMT_8bppYCbCr400, mw, mh, align=64, device=sdr_intent.device)
         md = A.GainmapMetadata()
         cfg = self.encode_cfg(sdr_is_601, use_luminance)
-        self._call(True, self.lib.uhdr_hip_encode_api1_fused_dev, self.ctx.handle, C.byref(sdr_intent.raw), C.byref(hdr_intent.raw), C.byref(cfg),
+        fn = self.lib.uhdr_hip_encode_api1_fused_any_dev if _any else self.lib.uhdr_hip_encode_api1_fused_dev
+        self._call(True, fn, self.ctx.handle, C.byref(sdr_intent.raw), C.byref(hdr_intent.raw), C.byref(cfg),
                    base_encoding, C.c_void_p(qb.ctypes.data), C.c_void_p(qm.ctypes.data), C.byref(blocks), C.byref(md),
                    C.byref(gm.raw) if gm is not None else None)
         if gm is not None:
             gm.sync_meta_from_raw()
         return base, mapc, md, gm
+
+    def encodeApi1FusedAny(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, want_map=True,
+                           sdr_is_601=False, use_luminance=True):
+        """encodeApi1Fused for both SDR intents API-1 takes (uhdr_hip_encode_api1_fused_any_dev): a YCbCr 4:2:0 intent runs exactly what
+        encodeApi1Fused runs; an RGBA8888 intent (dimensions multiples of 8) has a 4:4:4 base image -- three (h/8, w/8, 64) base
+        coefficient tensors, bit-identical to convert_raw_input_to_ycbcr + convertYuv + fdct_quant x 3.  encodeApi1Fused keeps refusing RGBA8888."""
+        return self.encodeApi1Fused(sdr_intent, hdr_intent, base_encoding, qt_base, qt_map, want_map, sdr_is_601, use_luminance, _any=True)
 
     # ---- one entry point per direction of the API-1 round trip, device resident (round 6) -----------------
     def encodeApi1Scans(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, out_base, out_map,
@@ -285,6 +294,35 @@ class UltraHdr:
                    C.c_void_p(qb.ctypes.data), C.c_void_p(qm.ctypes.data), C.byref(md), None, C.c_void_p(out_base.data_ptr()), int(out_base.numel()), C.byref(nb),
                    C.c_void_p(out_map.data_ptr()), int(out_map.numel()), C.byref(nm))
         return int(nb.value), int(nm.value), md
+
+    def encodeApi1ScansAny(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, out_base, out_map,
+                           sdr_is_601=False, use_luminance=True):
+        """encodeApi1Scans for both SDR intents API-1 takes, YCbCr 4:2:0 and RGBA8888 (base scan 1x1 / 1x1 / 1x1), in ONE C call.
+        Device images (uhdr_hip_encode_api1_scans_any_dev): out_base / out_map are uint8 CUDA tensors; returns (bytes of the base scan,
+        bytes of the map scan, metadata).  Host images (uhdr_hip_encode_api1_scans_any): out_base / out_map are the two capacities in
+        bytes; returns (base scan, map scan, metadata, gain-map description); a UhdrError for a capacity that is too small carries the
+        needed sizes in .needed."""
+        qb, qm = self._qt_pair(qt_base), self._qt_pair(qt_map)
+        md = A.GainmapMetadata()
+        cfg = self.encode_cfg(sdr_is_601, use_luminance)
+        nb, nm = C.c_size_t(0), C.c_size_t(0)
+        if _is_dev(sdr_intent, hdr_intent):
+            assert out_base.is_cuda and out_map.is_cuda
+            self._call(True, self.lib.uhdr_hip_encode_api1_scans_any_dev, self.ctx.handle, C.byref(sdr_intent.raw), C.byref(hdr_intent.raw), C.byref(cfg),
+                       base_encoding, C.c_void_p(qb.ctypes.data), C.c_void_p(qm.ctypes.data), C.byref(md), None, C.c_void_p(out_base.data_ptr()),
+                       int(out_base.numel()), C.byref(nb), C.c_void_p(out_map.data_ptr()), int(out_map.numel()), C.byref(nm))
+            return int(nb.value), int(nm.value), md
+        assert not _is_dev(sdr_intent) and not _is_dev(hdr_intent)
+        desc = A.RawImage()
+        ob, om = np.empty(max(1, int(out_base)), np.uint8), np.empty(max(1, int(out_map)), np.uint8)
+        try:
+            self._call(False, self.lib.uhdr_hip_encode_api1_scans_any, self.ctx.handle, C.byref(sdr_intent.raw), C.byref(hdr_intent.raw), C.byref(cfg),
+                       base_encoding, C.c_void_p(qb.ctypes.data), C.c_void_p(qm.ctypes.data), C.byref(md), C.byref(desc), C.c_void_p(ob.ctypes.data),
+                       int(out_base), C.byref(nb), C.c_void_p(om.ctypes.data), int(out_map), C.byref(nm))
+        except A.UhdrError as e:
+            e.needed = (int(nb.value), int(nm.value))
+            raise
+        return ob[:nb.value].tobytes(), om[:nm.value].tobytes(), md, desc
 
     def bindEncodeApi1Scans(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, out_base, out_map,
                             sdr_is_601=False, use_luminance=True):
