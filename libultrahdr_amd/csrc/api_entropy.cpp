@@ -498,8 +498,18 @@ uhdr_error_info_t uhdr_hip_huffman_decode_dev(uhdr_hip_ctx_t* c, const uhdr_hip_
   const bool rst_sync = a.nseg > 1 && data_bytes / (size_t)a.nseg >= 320 && !getenv("UHDR_HIP_HUFF_RST_INTERVALS");
   const bool try_sync = (a.nseg == 1 || rst_sync) && data_bytes >= 4096 && data_bytes < ((size_t)1 << 29) && fast_ok && !getenv("UHDR_HIP_HUFF_SERIAL") && bpm <= 16;
   // write pass, form 2 (marker-less scans): a scan-order scratch takes the zero fill, the JBLOCK arrays are written whole
-  const int write_form = [] { const char* e = getenv("UHDR_HIP_HUFF_WRITE"); return e ? atoi(e) : 2; }();  // (read per call: tools/huff_exp.py sweeps it)
+  const int write_form = [] { const char* e = getenv("UHDR_HIP_HUFF_WRITE"); return e ? atoi(e) : 3; }();  // 3: form 3 where a scan qualifies, else 2 (read per call: tools/huff_exp.py sweeps it)
   const bool form2 = try_sync && !rst_sync && write_form != 1;
+  // write pass, form 3: every component sampled 1x1 (block t of the scan is JBLOCK t / ncomp of component t % ncomp) -- the hypothesis attempts store
+  // straight into the component arrays, which pass 0 zero-fills; no scratch, no placing pass.  UHDR_HIP_HUFF_WRITE=2 keeps form 2 (A/B).
+  const bool jblock_ok = [&] {
+    if (!form2 || write_form == 2 || bpm != a.ncomp || (a.ncomp != 1 && a.ncomp != 3)) return false;
+    for (int i = 0; i < a.ncomp; i++)
+      if (a.hs[i] != 1 || a.vs[i] != 1 || (size_t)a.bw[i] * a.bh[i] != (size_t)a.total_mcus || ((uintptr_t)a.coef[i] & 15u) != 0 ||
+          zero_bytes[i] / 16 >= 0xFFFFFFFFull)
+        return false;
+    return true;
+  }();
   bool coef_zeroed = !form2;  // the interval / single-lane decoder below stores into zero-initialised arrays
   if (!form2)
     for (int i = 0; i < a.ncomp; i++) HIP_TRY(hipMemsetAsync(a.coef[i], 0, zero_bytes[i], c->stream));
@@ -591,8 +601,10 @@ uhdr_error_info_t uhdr_hip_huffman_decode_dev(uhdr_hip_ctx_t* c, const uhdr_hip_
     const size_t o_pe = max_pieces > 1 ? take((size_t)nsub * (size_t)max_pieces * 8 + 64) : 0;
     const size_t o_pc = max_pieces > 1 ? take(((size_t)nsub * (size_t)max_pieces + 4) * 4) : 0;
     const size_t o_st2 = max_pieces > 1 ? take(((size_t)nsub * (size_t)max_pieces / 2048 + 4) * 4) : 0;
-    const size_t scan_bytes = form2 ? (size_t)total_blocks * 64 * sizeof(int16_t) : 0;
-    const size_t o_cs = form2 ? take(scan_bytes + 256) : 0;
+    const bool form3 = jblock_ok && attempts[0].levels > 0;  // (the rounds behind these attempts take form 1: they find the arrays zeroed)
+    const bool scratch2 = form2 && !form3;
+    const size_t scan_bytes = scratch2 ? (size_t)total_blocks * 64 * sizeof(int16_t) : 0;
+    const size_t o_cs = scratch2 ? take(scan_bytes + 256) : 0;
     UHDR_TRY(ensure(c->scratch[6], off));
     uint8_t* sb = (uint8_t*)c->scratch[6].p;
     HuffSyncArgs y;
@@ -635,7 +647,8 @@ uhdr_error_info_t uhdr_hip_huffman_decode_dev(uhdr_hip_ctx_t* c, const uhdr_hip_
       y.strag_list = (uint32_t*)(sb + o_sl);
       y.strag_cap = nsub * (uint32_t)bpm;
     }
-    if (form2) y.coef_scan = (int16_t*)(sb + o_cs);
+    if (scratch2) y.coef_scan = (int16_t*)(sb + o_cs);
+    y.total_mcus = (uint32_t)a.total_mcus;
     // lockstep levels of pass 1 before the stragglers get a wave each (0: all levels in lockstep, the round-4 form); restart files keep the lockstep form
     // (a lane walks a 1024-bit subsequence in ~33 us, a straggler's wave in ~10: 4K three-channel gain map 634 us with all 15
     // levels in lockstep, 517 with two, 491 with one; the 4:2:0 base image's 512-bit levels are cheap in lockstep once compacted)
@@ -657,8 +670,9 @@ uhdr_error_info_t uhdr_hip_huffman_decode_dev(uhdr_hip_ctx_t* c, const uhdr_hip_
       }
       // form 2's scratch: zero-filled by pass 0 of a hypothesis attempt itself (round 6: a 25-50 MB fill was a launch of its own at the head of
       // the decode); the rounds scheme gets a fill
-      auto pass0_zeroes = [&](const Attempt& t) { return form2 && t.levels > 0 && scan_bytes % 16 == 0 && scan_bytes / 16 < 0xFFFFFFFFull; };
-      if (form2 && !pass0_zeroes(attempts[0])) HIP_TRY(hipMemsetAsync(y.coef_scan, 0, scan_bytes, c->stream));
+      // form 3: the same for the component arrays (up to three regions)
+      auto pass0_zeroes = [&](const Attempt& t) { return form2 && t.levels > 0 && (form3 || (scan_bytes % 16 == 0 && scan_bytes / 16 < 0xFFFFFFFFull)); };
+      if (scratch2 && !pass0_zeroes(attempts[0])) HIP_TRY(hipMemsetAsync(y.coef_scan, 0, scan_bytes, c->stream));
       dbg.mark("huffman_decode_dev: fills enqueued");
       int final_buf = 0;
       uint32_t* fl = c->h_flags;  // pinned; [9]: restart markers the unstuff pass dropped, [16] [17] / [0] [7]: their sequence sums as found / as due
@@ -668,8 +682,10 @@ uhdr_error_info_t uhdr_hip_huffman_decode_dev(uhdr_hip_ctx_t* c, const uhdr_hip_
         HIP_TRY(hipMemsetAsync(y.flags, 0, 32, c->stream));  // not [8]: the stuffed-byte count stays
         HIP_TRY(hipMemsetAsync(y.flags + kHuffFlagStragglers, 0, 4, c->stream));  // (hyp_pass01_kernel appends to the list it finds)
         HIP_TRY(hipMemsetAsync(y.nblk, 0, (size_t)nsub * 4 + 4, c->stream));
-        if (form2) {
+        if (scratch2) {
           if (!pass0_zeroes(next)) HIP_TRY(hipMemsetAsync(y.coef_scan, 0, scan_bytes, c->stream));
+        } else if (form3 && pass0_zeroes(next)) {
+          // (pass 0 of the next attempt fills the arrays again: what the lost attempt stored is gone before its write pass)
         } else {
           HIP_TRY(hipMemsetAsync(y.dcd, 0, (size_t)total_blocks * 4, c->stream));
           for (int i = 0; i < a.ncomp; i++) HIP_TRY(hipMemsetAsync(a.coef[i], 0, zero_bytes[i], c->stream));
@@ -680,8 +696,14 @@ uhdr_error_info_t uhdr_hip_huffman_decode_dev(uhdr_hip_ctx_t* c, const uhdr_hip_
         const Attempt& t = attempts[ti];
         if (ti > 0) UHDR_TRY(start_over(t));
         y.sub_bits = t.sub_bits;
-        y.zero_ptr = pass0_zeroes(t) ? (uint4*)y.coef_scan : nullptr;
-        y.zero_vec = pass0_zeroes(t) ? (uint32_t)(scan_bytes / 16) : 0u;
+        y.write_form = form3 && t.levels > 0 ? 3 : 0;
+        for (int i = 0; i < 3; i++) { y.zero_ptr[i] = nullptr; y.zero_vec[i] = 0u; }
+        if (pass0_zeroes(t) && form3) {
+          for (int i = 0; i < a.ncomp; i++) { y.zero_ptr[i] = (uint4*)a.coef[i]; y.zero_vec[i] = (uint32_t)(zero_bytes[i] / 16); }
+        } else if (pass0_zeroes(t)) {
+          y.zero_ptr[0] = (uint4*)y.coef_scan;
+          y.zero_vec[0] = (uint32_t)(scan_bytes / 16);
+        }
         const uint32_t nsub_t = huff_sync_max_subsequences(data_bytes, t.sub_bits);
         if (t.levels > 0) {
           y.hyp_h = bpm;
@@ -753,6 +775,9 @@ uhdr_error_info_t uhdr_hip_huffman_decode_dev(uhdr_hip_ctx_t* c, const uhdr_hip_
           HIP_TRY(hipMemcpyAsync(fl, y.flags, 24 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
           HIP_TRY(wait_stream(c));
           rounds_ran = true;
+          if (getenv("UHDR_HIP_HUFF_DEBUG"))
+            fprintf(stderr, "uhdr_hip: rounds decode of %zu bytes, %u subsequences of %u bits (write form %d): %s\n", data_bytes, nsub_t, t.sub_bits,
+                    y.coef_scan && !rst_sync ? 2 : 1, fl[4 + max_rounds % 3] == 0 ? "settled" : "NOT settled");
         }
       }
       const bool settled = hyp_done || fl[4 + max_rounds % 3] == 0;

@@ -784,8 +784,17 @@ struct __attribute__((aligned(16))) Write2Lds {  // == the layout of HuffSyncArg
   uint16_t l2[kHuffL2Total * 128];        // 8 KB: the sub-tables of the value form, packed (codes longer than the index): bits | advance << 5 |
                                           // magnitude bits << 12; 0 = a malformed code (16 bits, to the end of the block / one DC step)
 };
+// JB: write form 3 (HuffSyncArgs::write_form) -- every component sampled 1x1, so block t of the scan is JBLOCK t / ncomp of component t % ncomp and
+// the stores go straight to the component arrays: no edge MCUs, no address arithmetic beyond "next component, after the last one the next JBLOCK"
+// (blk counts JBLOCKs per component here, the state's b is the component).  What form 2 leaves to the placing pass is the zig-zag -> natural index,
+// one LDS byte per stored value.  That read must not put a wait of its own in front of the next step's table read (this loop runs at one lane's
+// latency): a step only ISSUES the two index reads and carries its stores -- destination block, values, predicates -- into the next step, which
+// makes them behind its own table read; LDS returns in order, so the wait for the table entry covers the indices.  The last step's pair is
+// stored behind the loop.  Every store lies inside [coef[b] + 64 m, + 64) with b < ncomp and m < total_mcus, whatever the start state: a lost
+// attempt's garbage stays inside the arrays.
+template <bool JB>
 __device__ __forceinline__ void write_span2(const HuffSyncArgs& a, const Staged& st, uint32_t region_bit, const Write2Lds& L, uint32_t p, uint32_t b, uint32_t k,
-                                            uint32_t end_bit, uint32_t& nblk, uint32_t blk) {
+                                            uint32_t end_bit, uint32_t& nblk, uint32_t blk, const uint32_t* __restrict__ nat = nullptr) {
   Bits r;
   r.st = st;
   r.region_bit = region_bit;
@@ -797,15 +806,38 @@ __device__ __forceinline__ void write_span2(const HuffSyncArgs& a, const Staged&
   for (int j = 0; j < 16; j++) cpack |= ((uint32_t)a.comp_of[j] & 3u) << (2 * j);
   const uint2* P = &L.p[0][0];
   const uint16_t* S = &L.l2[0];
-  uint32_t cls = ((cpack >> (2u * b)) & 3u) ? 2u : 0u;
-  int16_t* dst = a.coef_scan + (size_t)blk * 64;
+  const uint32_t limit = JB ? a.total_mcus : a.total_blocks;
+  // JB: the element distances from this block to the next one of the scan, to the one after it, ... -- one or three components, so the
+  // three rotate at every block end (per lane, in registers: selecting among wave-uniform values costs the block end twice the instructions)
+  ptrdiff_t dA = 64, dB = 64, dC = 64;
+  if (JB) {
+    if (b >= bpm) b = 0;  // (no walk leaves such a state)
+    blk /= bpm;
+    if (bpm == 3u) {
+      const ptrdiff_t d0 = a.coef[1] - a.coef[0], d1 = a.coef[2] - a.coef[1], dl = a.coef[0] - a.coef[2] + 64;
+      dA = b == 0 ? d0 : (b == 1 ? d1 : dl);
+      dB = b == 0 ? d1 : (b == 1 ? dl : d0);
+      dC = b == 0 ? dl : (b == 1 ? d0 : d1);
+    }
+  }
+  uint32_t cls = JB ? (b ? 2u : 0u) : (((cpack >> (2u * b)) & 3u) ? 2u : 0u);
+  int16_t* dst = JB ? a.coef[b] + (size_t)min(blk, limit) * 64 : a.coef_scan + (size_t)blk * 64;
+  // JB: the stores of the step before
+  int16_t* pdst = dst;
+  uint32_t pn1 = 0, pn2 = 0;
+  int pv1 = 0, pv2 = 0;
+  bool ps1 = false, ps2 = false;
   int left = (int)(end_bit - p);
-  while (left > 0 && blk < a.total_blocks) {
+  while (left > 0 && blk < limit) {
     r.fill();
     const uint32_t w16 = r.peek(16);
     const uint32_t ti = cls + (k ? 1u : 0u);
     const uint2 e = P[ti * (uint32_t)kHuffPairWords + (w16 >> (16 - kHuffPairBits))];
     uint32_t e1 = e.x, e2 = e.y;
+    if (JB) {
+      if (ps1) pdst[pn1] = (int16_t)pv1;
+      if (ps2) pdst[pn2] = (int16_t)pv2;
+    }
     if (__builtin_amdgcn_ballot_w64((e1 >> 31) != 0) != 0) {  // a code longer than the index: its sub-table, one symbol
       uint32_t s2 = S[((e1 >> 31) ? (e1 & 63u) : 0u) * 128u + (w16 & 127u)];
       s2 = s2 ? s2 : (16u | ((k ? 64u : 1u) << 5) | (1u << 16));  // malformed: make_value_table's entry for an undefined code
@@ -824,23 +856,48 @@ __device__ __forceinline__ void write_span2(const HuffSyncArgs& a, const Staged&
     const uint32_t zz1 = k + kinc1 - 1u, zz2 = zz1 + kinc2;  // DC: 0; AC symbol with a value: k + run
     const bool over1 = sz1 != 0 && zz1 > 63u, over2 = sz2 != 0 && zz2 > 63u;  // (a DC symbol has zzpos 0)
     bad = bad || ((e1 >> 16) & 1u) != 0 || over1 || over2;
-    if (sz1 != 0 && !over1) dst[zz1] = (int16_t)v1;
-    if (sz2 != 0 && !over2) dst[zz2] = (int16_t)v2;
+    if (JB) {
+      pn1 = nat[zz1 & 63u];
+      pn2 = nat[zz2 & 63u];
+      pdst = dst;
+      pv1 = v1; pv2 = v2;
+      ps1 = sz1 != 0 && !over1;
+      ps2 = sz2 != 0 && !over2;
+    } else {
+      if (sz1 != 0 && !over1) dst[zz1] = (int16_t)v1;
+      if (sz2 != 0 && !over2) dst[zz2] = (int16_t)v2;
+    }
     r.skip((int)adv);
     left -= (int)adv;
     k += kinc1 + kinc2;
     if (k >= 64u) {
       k = 0;
-      b++;
-      nblk++;
-      blk++;
-      dst += 64;
-      if (b == bpm) b = 0;
-      cls = ((cpack >> (2u * b)) & 3u) ? 2u : 0u;
+      if constexpr (JB) {
+        const bool last = b + 1u == bpm;
+        dst += dA;
+        const ptrdiff_t t = dA;
+        dA = dB; dB = dC; dC = t;
+        b = last ? 0u : b + 1u;
+        nblk++;
+        blk += last ? 1u : 0u;
+        cls = b ? 2u : 0u;
+      } else {
+        b++;
+        nblk++;
+        blk++;
+        dst += 64;
+        if (b == bpm) b = 0;
+        cls = ((cpack >> (2u * b)) & 3u) ? 2u : 0u;
+      }
     }
+  }
+  if (JB) {
+    if (ps1) pdst[pn1] = (int16_t)pv1;
+    if (ps2) pdst[pn2] = (int16_t)pv2;
   }
   if (bad) atomicOr(a.flags + 1, 2u);
 }
+template <bool JB>
 __global__ __launch_bounds__(256) void sync_write2_kernel(const HuffSyncArgs a, int final_buf) {
   extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
   // the tables sit in the dynamic segment as well (static + dynamic LDS beyond 64 KB needs the opt-in either way)
@@ -853,9 +910,17 @@ __global__ __launch_bounds__(256) void sync_write2_kernel(const HuffSyncArgs a, 
   const uint32_t nsub = (nbits + a.sub_bits - 1) / a.sub_bits;
   const uint32_t cshift = 31u - (uint32_t)__builtin_clz(a.sub_bits >> 3);
   const uint32_t wv = threadIdx.x >> 6;
-  uint32_t* s_stage = s_stage_all + wv * ((64u * ((a.sub_bits >> 3) + 4u) + 64u) >> 2);
+  const uint32_t wave_words = (64u * ((a.sub_bits >> 3) + 4u) + 64u) >> 2;
+  uint32_t* s_stage = s_stage_all + wv * wave_words;
   const uint32_t first_byte = (blockIdx.x * blockDim.x + wv * 64u) * (a.sub_bits >> 3);
   stage_wave(a.clean, nclean, first_byte, cshift, s_stage, threadIdx.x & 63u);
+  const uint32_t* nat = nullptr;
+  if constexpr (JB) {  // zig-zag position -> natural index (a word each: a byte would be widened on its way round the loop), behind the last wave's
+                       // staged bytes (launch_write2 sizes the segment)
+    uint32_t* zz = s_stage_all + (blockDim.x >> 6) * wave_words;
+    if (threadIdx.x < 64) zz[threadIdx.x] = a.zigzag[threadIdx.x];
+    nat = zz;
+  }
   __syncthreads();
   if (i >= nsub) return;
   uint32_t p = 0, b = 0, k = 0;
@@ -867,7 +932,7 @@ __global__ __launch_bounds__(256) void sync_write2_kernel(const HuffSyncArgs a, 
   uint32_t nblk = 0;
   const Staged st = {s_stage, cshift};
   const uint32_t blk0 = a.nblk[i] + tile_offset(a);  // nblk[] holds the per-tile exclusive scan by now
-  if (p < end_bit) write_span2(a, st, first_byte * 8u, L, p, b, k, end_bit, nblk, blk0);
+  if (p < end_bit) write_span2<JB>(a, st, first_byte * 8u, L, p, b, k, end_bit, nblk, blk0, nat);
   if (i == nsub - 1) {
     if (blk0 + nblk < a.total_blocks) atomicOr(a.flags + 1, 8u);  // truncated data
   }
@@ -889,6 +954,13 @@ __global__ __launch_bounds__(256) void sync_write2_kernel(const HuffSyncArgs a, 
 // A path that does not merge within `levels` subsequences leaves map = 0xff; if the true path hits one, flags[2] is set
 // and the caller runs the rounds instead.
 
+// pass 0's fill on the side (HuffSyncArgs::zero_ptr): up to three regions of 16-byte pieces, grid-stride
+__device__ __forceinline__ void zero_fill_regions(const HuffSyncArgs& a, uint32_t t, uint32_t nt) {
+  const uint4 z = make_uint4(0, 0, 0, 0);
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+    for (uint32_t v = t; v < a.zero_vec[r]; v += nt) a.zero_ptr[r][v] = z;
+}
 __global__ __launch_bounds__(1024) void hyp_pass0_kernel(const HuffSyncArgs a) {
   extern __shared__ uint32_t s_stage[];
   __shared__ PairLds L;
@@ -900,13 +972,10 @@ __global__ __launch_bounds__(1024) void hyp_pass0_kernel(const HuffSyncArgs a) {
   const uint32_t cshift = 31u - (uint32_t)__builtin_clz(a.sub_bits >> 3);
   const uint32_t first_byte = blockIdx.x * 64u * (a.sub_bits >> 3);
   stage_wave(a.clean, nclean, first_byte, cshift, s_stage, threadIdx.x, 64u, blockDim.x);
-  if (a.zero_vec) {
-    // the write pass's scan-order scratch: zeros (25-50 MB at 4K).  BEHIND the last global load of this kernel: the walk below reads LDS only, so
-    // the stores drain while it runs.  In front of the staging loads (where this loop stood until round 6) every wave waited for its 56 KB of
-    // stores before its first symbol -- memory operations of a wave complete in order.
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < a.zero_vec; v += gridDim.x * blockDim.x) a.zero_ptr[v] = z;
-  }
+  // what the write pass stores into (form 2's scan-order scratch, form 3's component arrays): zeros (25-50 MB at 4K).  BEHIND the last global load
+  // of this kernel: the walk below reads LDS only, so the stores drain while it runs.  In front of the staging loads (where this loop stood until
+  // round 6) every wave waited for its 56 KB of stores before its first symbol -- memory operations of a wave complete in order.
+  zero_fill_regions(a, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
   __syncthreads();
   if (i >= nsub) return;
   uint32_t p = i * a.sub_bits, b = h, k = 0, nblk = 0;
@@ -1146,10 +1215,7 @@ __global__ __launch_bounds__(1024) void hyp_pass01_kernel(const HuffSyncArgs a) 
   uint16_t* s_id = (uint16_t*)(s_fresh_hi + 64u * H);
   if (tid == 0) s_n = 0;
   stage_wave(a.clean, nclean, first_byte, cshift, s_stage, tid, 64u, blockDim.x);
-  if (a.zero_vec) {  // (behind the last global load, as in hyp_pass0_kernel)
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    for (uint32_t v = blockIdx.x * blockDim.x + tid; v < a.zero_vec; v += gridDim.x * blockDim.x) a.zero_ptr[v] = z;
-  }
+  zero_fill_regions(a, blockIdx.x * blockDim.x + tid, gridDim.x * blockDim.x);  // (behind the last global load, as in hyp_pass0_kernel)
   __syncthreads();
   const Staged st = {s_stage, cshift};
   const bool have = i < nsub;
@@ -1669,6 +1735,56 @@ __global__ __launch_bounds__(kPlaceChunk) void coef_place_kernel(const HuffSyncA
     dst[lane & 31u] = lo | (hi << 16);
   }
 }
+// form 3 of the write pass: the DC differences sit at [0] of every JBLOCK of the component arrays, and scan position t is JBLOCK t / ncomp of
+// component t % ncomp.  The prediction happens in place, on term 0 alone: per-chunk sums per component, then carry-in + in-chunk scan + store
+// (same chunks, same int sums and the same final cast as coef_place_kernel; partial / self_prefix as there).
+__device__ __forceinline__ int16_t* dc_term3(const HuffSyncArgs& a, uint32_t t, int& c) {
+  const uint32_t n = (uint32_t)a.ncomp, m = t / n;
+  c = (int)(t - m * n);
+  int16_t* base = c == 0 ? a.coef[0] : (c == 1 ? a.coef[1] : a.coef[2]);
+  return base + (size_t)m * 64;
+}
+__global__ __launch_bounds__(kPlaceChunk) void dc_partial3_kernel(const HuffSyncArgs a, int* __restrict__ partial) {
+  __shared__ int s_sum[3 * (kPlaceChunk / 64)];
+  const int tid = (int)threadIdx.x;
+  const uint32_t t = blockIdx.x * (uint32_t)kPlaceChunk + (uint32_t)tid;
+  int v[3] = {0, 0, 0};
+  if (t < a.total_blocks) {
+    int c;
+    const int16_t* d = dc_term3(a, t, c);
+    v[c] = *d;
+  }
+  dc_chunk_scan(v, s_sum, tid);
+  if (tid == kPlaceChunk - 1) { partial[blockIdx.x * 3] = v[0]; partial[blockIdx.x * 3 + 1] = v[1]; partial[blockIdx.x * 3 + 2] = v[2]; }
+}
+__global__ __launch_bounds__(kPlaceChunk) void dc_apply3_kernel(const HuffSyncArgs a, const int* __restrict__ partial, int self_prefix) {
+  __shared__ int s_sum[3 * (kPlaceChunk / 64)];
+  const int tid = (int)threadIdx.x;
+  const uint32_t t = blockIdx.x * (uint32_t)kPlaceChunk + (uint32_t)tid;
+  int v[3] = {0, 0, 0};
+  int c = 0;
+  int16_t* d = nullptr;
+  if (t < a.total_blocks) {
+    d = dc_term3(a, t, c);
+    v[c] = *d;
+  }
+  int carry[3];
+  if (self_prefix) {
+    int part[3] = {0, 0, 0};
+    for (uint32_t i = (uint32_t)tid; i < blockIdx.x; i += (uint32_t)kPlaceChunk) {
+      part[0] += partial[i * 3];
+      part[1] += partial[i * 3 + 1];
+      part[2] += partial[i * 3 + 2];
+    }
+    wg_incl_scan<kPlaceChunk, 3>(part, s_sum, carry);
+  } else {
+    carry[0] = partial[blockIdx.x * 3];
+    carry[1] = partial[blockIdx.x * 3 + 1];
+    carry[2] = partial[blockIdx.x * 3 + 2];
+  }
+  dc_chunk_scan(v, s_sum, tid);
+  if (d) *d = (int16_t)((c == 0 ? carry[0] : (c == 1 ? carry[1] : carry[2])) + v[c]);
+}
 __global__ __launch_bounds__(1024) void dc_scan_partials_kernel(int* __restrict__ partial, int nchunks) {  // exclusive, in place
   __shared__ int s_sum[3 * 16];
   const int tid = (int)threadIdx.x;
@@ -1814,12 +1930,29 @@ static void launch_write2(const HuffSyncArgs& a, uint32_t nsub, int final_buf, h
   const size_t lds = sizeof(Write2Lds) + per_wave * waves;  // 48 KB of pair tables + the staged bytes: beyond the 64 KB default, opt in
   const int threads = 64 * waves;
   const int grid = (int)((nsub + threads - 1) / threads);
+  if (a.write_form == 3) {  // + the zig-zag -> natural words behind the staged bytes
+    static size_t opted3 = 0;
+    if (lds + 256 > opted3) {
+      (void)hipFuncSetAttribute((const void*)sync_write2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + 256));
+      opted3 = lds + 256;
+    }
+    hipLaunchKernelGGL(sync_write2_kernel<true>, dim3(grid), dim3(threads), lds + 256, s, a, final_buf);
+    return;
+  }
   static size_t opted = 0;
   if (lds > opted) {
-    (void)hipFuncSetAttribute((const void*)sync_write2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)sync_write2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     opted = lds;
   }
-  hipLaunchKernelGGL(sync_write2_kernel, dim3(grid), dim3(threads), lds, s, a, final_buf);
+  hipLaunchKernelGGL(sync_write2_kernel<false>, dim3(grid), dim3(threads), lds, s, a, final_buf);
+}
+// form 3: the DC prediction in place (dc_partial3_kernel, dc_apply3_kernel)
+static void launch_dc3(const HuffSyncArgs& a, int* dc_partial, hipStream_t s) {
+  const int nch = (int)((a.total_blocks + kPlaceChunk - 1) / kPlaceChunk);
+  hipLaunchKernelGGL(dc_partial3_kernel, dim3(nch), dim3(kPlaceChunk), 0, s, a, dc_partial);
+  const int self_prefix = nch <= kPlaceSelfPrefix ? 1 : 0;
+  if (!self_prefix) hipLaunchKernelGGL(dc_scan_partials_kernel, dim3(1), dim3(1024), 0, s, dc_partial, nch);
+  hipLaunchKernelGGL(dc_apply3_kernel, dim3(nch), dim3(kPlaceChunk), 0, s, a, (const int*)dc_partial, self_prefix);
 }
 static void launch_place(const HuffSyncArgs& a, int* dc_partial, hipStream_t s) {
   const int nch = (int)((a.total_blocks + kPlaceChunk - 1) / kPlaceChunk);
@@ -1940,7 +2073,8 @@ hipError_t launch_huffman_decode_hyp(const HuffSyncArgs& a, int* dc_partial, uin
   // the write pass: on pieces of a subsequence when the tracking passes noted them (HuffSyncArgs::pieces), else on whole subsequences
   HuffSyncArgs w = a;
   uint32_t nw = nsub;
-  if (a.pieces > 1 && a.coef_scan && !a.rst_map) {
+  const bool form3 = a.write_form == 3 && !a.rst_map;
+  if (a.pieces > 1 && (a.coef_scan || form3) && !a.rst_map) {
     w.sub_bits = a.sub_bits / (uint32_t)a.pieces;
     w.state[0] = a.pend;
     w.nblk = a.pcnt;
@@ -1951,7 +2085,11 @@ hipError_t launch_huffman_decode_hyp(const HuffSyncArgs& a, int* dc_partial, uin
     hipLaunchKernelGGL(scan_tiles_kernel, dim3(nt), dim3(kScanThreads), 0, s, w.nblk, (int)nw, w.scan_tmp);  // (the write pass adds the tile sums: tile_offset)
   }
   mark();
-  if (a.coef_scan && !a.rst_map) {
+  if (form3) {
+    launch_write2(w, nw, 0, s);
+    mark();
+    launch_dc3(a, dc_partial, s);
+  } else if (a.coef_scan && !a.rst_map) {
     launch_write2(w, nw, 0, s);
     mark();
     launch_place(a, dc_partial, s);
@@ -1964,7 +2102,7 @@ hipError_t launch_huffman_decode_hyp(const HuffSyncArgs& a, int* dc_partial, uin
   if (dbg) {
     (void)hipStreamSynchronize(s);
     static const char* names[] = {"pass0", "pass1 (+ stragglers)", "chain x3", "nblk scan", "write", "dc x3 / place", "-"};
-    fprintf(stderr, "uhdr_hip: hypothesis decode kernels:");
+    fprintf(stderr, "uhdr_hip: hypothesis decode kernels (write form %d):", form3 ? 3 : (a.coef_scan && !a.rst_map ? 2 : 1));
     for (int i = 0; i + 1 < nev; i++) {
       float ms = 0;
       (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);

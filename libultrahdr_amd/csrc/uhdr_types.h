@@ -410,10 +410,16 @@ struct HuffSyncArgs {
   // order, the DC DIFFERENCE at [0]; zero-initialised) and coef_place_kernel moves them to the component arrays in natural
   // order with the DC prediction applied; nullptr: form 1 (stores into zero-initialised JBLOCK arrays + dcd[])
   int16_t* coef_scan;
-  // round 6: pass 0 zero-fills that scratch on the side (its lanes wait on table lookups, the memory system is idle): zero_vec 16-byte
-  // pieces from zero_ptr, grid-stride; 0: the host has enqueued a fill instead (the rounds scheme)
-  uint4* zero_ptr;
-  uint32_t zero_vec;
+  // write pass, form 3 (marker-less scans whose components are all sampled 1x1, hypothesis attempts): block t of the scan IS JBLOCK
+  // t / ncomp of component t % ncomp, so the write pass stores straight into the (zero-initialised) component arrays -- natural order, the
+  // DC DIFFERENCE at [0] -- and two small kernels turn the differences into predictions in place.  No scan-order scratch, no placing pass.
+  int write_form;        // 3: that form; else coef_scan decides between 2 and 1
+  uint32_t total_mcus;   // form 3: JBLOCKs per component
+  // round 6: pass 0 zero-fills what the write pass stores into on the side (its lanes wait on table lookups, the memory system is idle):
+  // zero_vec[r] 16-byte pieces from zero_ptr[r], grid-stride -- form 2's scratch is one region, form 3's component arrays up to three
+  // (a caller's arrays need not be contiguous); all 0: the host has enqueued fills instead (the rounds scheme)
+  uint4* zero_ptr[3];
+  uint32_t zero_vec[3];
   // round 6: the write pass runs on PIECES of a subsequence.  It has one lane per subsequence -- 290 waves for a 4K gain map -- and therefore
   // runs at one lane's latency; the tracking passes (pass 1's lockstep levels, the stragglers, pass 0's very first lane) already walk every
   // subsequence along what may be the true path, so they also note the state at the first symbol boundary at or beyond each interior cut
