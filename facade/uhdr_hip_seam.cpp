@@ -194,7 +194,11 @@ bool apply_gainmap(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* gainmap_img,
     // the version check is the one thing uhdr_gainmap_metadata_ext_t adds (jpegr.cpp:1546-1555)
     if (gainmap_metadata->version.compare(ultrahdr::kJpegrVersion)) return false;  // the reference words that error
     const uhdr_gainmap_metadata_t md = *gainmap_metadata;  // slice off the version string
-    *st = uhdr_hip_apply_gainmap(cur(), sdr_intent, gainmap_img, &md, output_ct, output_format, max_display_boost, dest);
+    // UHDR_HIP_SEAM_RESIZED_MAP: a gain map of another aspect ratio than the base image (jpegr.cpp:1651-1671) stays on the device
+    // (uhdr_hip_apply_gainmap_any); without it the library refuses such a map and the reference's resize + loop run on the host
+    *st = getenv("UHDR_HIP_SEAM_RESIZED_MAP")
+              ? uhdr_hip_apply_gainmap_any(cur(), sdr_intent, gainmap_img, &md, output_ct, output_format, max_display_boost, dest)
+              : uhdr_hip_apply_gainmap(cur(), sdr_intent, gainmap_img, &md, output_ct, output_format, max_display_boost, dest);
     return handled(*st, "apply_gainmap");
   }();
   if (!on_device_) drop_resident();

@@ -17,6 +17,9 @@
  *                                       JpegEncoderHelper::compressImage  lib/include/ultrahdr/jpegencoderhelper.h:57-58
  *                                                                     (call sites lib/src/jpegencoderhelper.cpp:187-198,297)
  *   uhdr_hip_copy_raw_image_dev         copy_raw_image                lib/src/gainmapmath.cpp:1492-1613
+ *   uhdr_hip_resize_image               resize_image                  lib/src/editorhelper.cpp:88-146
+ *   uhdr_hip_apply_gainmap_any          UltraHdr::applyGainMap with its resize step for a gain map of another aspect ratio
+ *                                                                     (lib/src/jpegr.cpp:1651-1671)
  *   uhdr_hip_jpeg_rgb_to_ycc            libjpeg's JCS_RGB -> YCbCr for 3-channel gain maps  lib/src/jpegencoderhelper.cpp:165-167, 212-225
  *   uhdr_hip_idct_dequant,
  *   uhdr_hip_jpeg_ycc_to_rgb            the dequantize + IDCT (+ colour conversion) stage libjpeg runs inside
@@ -198,6 +201,36 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_batch_dev(uhdr_hip_ctx_t* ctx, unsigned
                                                    uhdr_color_transfer_t output_ct,
                                                    uhdr_img_fmt_t output_format, float max_display_boost,
                                                    uhdr_raw_image_t* dests);
+/* applyGainMap for a gain map of ANY aspect ratio: UltraHdr::applyGainMap including its resize step, lib/src/jpegr.cpp:1651-1671.
+ * Where the map's aspect ratio differs from the base image's by more than 1 % (the reference's float expression, on the whole
+ * image's height) the reference first resizes the map to the base image's size (resize_image, lib/src/editorhelper.cpp:88-146) and
+ * then runs its loop at map scale 1.  uhdr_hip_apply_gainmap / _dev refuse such a pair with UHDR_CODEC_UNSUPPORTED_FEATURE; these two
+ * take it, with the reference's bytes, by one of two routes: staged (uhdr_hip_resize_image_dev into scratch of the context, then the
+ * usual launch at scale 1) or fused (the resized byte is computed per output pixel inside the applyGainMap kernel and the map of the
+ * base image's size never exists in memory).  The route is the measured default; UHDR_HIP_APPLY_RESIZE=staged|fused in the
+ * environment forces one.  Within 1 % they are uhdr_hip_apply_gainmap / _dev.  Parameters as theirs. */
+uhdr_error_info_t uhdr_hip_apply_gainmap_any(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr_intent,
+                                             const uhdr_raw_image_t* gainmap_img,
+                                             const uhdr_gainmap_metadata_t* gainmap_metadata,
+                                             uhdr_color_transfer_t output_ct,
+                                             uhdr_img_fmt_t output_format, float max_display_boost,
+                                             uhdr_raw_image_t* dest);
+uhdr_error_info_t uhdr_hip_apply_gainmap_any_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr_intent,
+                                                 const uhdr_raw_image_t* gainmap_img,
+                                                 const uhdr_gainmap_metadata_t* gainmap_metadata,
+                                                 uhdr_color_transfer_t output_ct,
+                                                 uhdr_img_fmt_t output_format, float max_display_boost,
+                                                 uhdr_raw_image_t* dest, unsigned int y0,
+                                                 unsigned int full_height);
+/* resize_image, lib/src/editorhelper.cpp:88-146 (declared lib/include/ultrahdr/editorhelper.h): the interpolating resize
+ * applyGainMap runs on a gain map of another aspect ratio, for UHDR_IMG_FMT_8bppYCbCr400, UHDR_IMG_FMT_24bppRGB888 and
+ * UHDR_IMG_FMT_32bppRGBA8888 (alpha 255), with the reference's bytes.  dst: caller provides planes[0], stride[0], w, h and
+ * fmt == src->fmt; colour aspects are copied from src.  Any other format: UHDR_CODEC_UNSUPPORTED_FEATURE (the reference
+ * returns nullptr for most of them).  _dev: dst may be a row stripe of a taller destination, y0 = its first row there,
+ * full_height = the whole destination's height (whole image: 0, 0), as for uhdr_hip_apply_gainmap_dev. */
+uhdr_error_info_t uhdr_hip_resize_image(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* src, uhdr_raw_image_t* dst);
+uhdr_error_info_t uhdr_hip_resize_image_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* src, uhdr_raw_image_t* dst,
+                                            unsigned int y0, unsigned int full_height);
 /* one-pass (REALTIME) generation, or the whole two-pass sequence on one device */
 uhdr_error_info_t uhdr_hip_generate_gainmap_dev(uhdr_hip_ctx_t* ctx,
                                                 const uhdr_raw_image_t* sdr_intent,

@@ -108,6 +108,21 @@ class UltraHdr {
     return uhdr_hip_apply_gainmap(mCtx, sdr_intent, gainmap_img, gainmap_metadata, output_ct, output_format, max_display_boost, dest);
   }
 
+  // applyGainMap including the reference's resize step for a gain map of another aspect ratio (jpegr.cpp:1651-1671,
+  // uhdr_hip_apply_gainmap_any); applyGainMap above keeps refusing such a map.
+  uhdr_error_info_t applyGainMapAny(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* gainmap_img,
+                                    uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_color_transfer_t output_ct,
+                                    uhdr_img_fmt_t output_format, float max_display_boost, uhdr_raw_image_t* dest) {
+    if (!mCtx) return mCreateStatus;
+    return uhdr_hip_apply_gainmap_any(mCtx, sdr_intent, gainmap_img, gainmap_metadata, output_ct, output_format, max_display_boost, dest);
+  }
+
+  // resize_image (editorhelper.cpp:88-146) for Y400 / RGB888 / RGBA8888 into a caller-provided image of the wanted size
+  uhdr_error_info_t resizeImage(uhdr_raw_image_t* src, uhdr_raw_image_t* dst) {
+    if (!mCtx) return mCreateStatus;
+    return uhdr_hip_resize_image(mCtx, src, dst);
+  }
+
   // applyGainMap on a base image still in coefficient form (device pointers; gainmap_img and dest are device images): the
   // dequantize + IDCT stage runs inside the kernel.  sampling422: the coefficients are a 4:2:2 frame's, not a 4:2:0 one's.
   uhdr_error_info_t applyGainMapFromCoefficients(const uhdr_hip_jpeg_coefficients_t* base, unsigned int w, unsigned int h,

@@ -7,7 +7,9 @@
 static uhdr_error_info_t build_apply_params(uhdr_hip_ctx* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
                                             const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct,
                                             float max_display_boost, uhdr_raw_image_t* dest, unsigned int y0,
-                                            unsigned int full_height, ApplyParams* out) {
+                                            unsigned int full_height, ApplyParams* out, bool resize_in_kernel = false) {
+  // resize_in_kernel: the _any entry points' fused route -- a map of another aspect ratio is resized by the sampler
+  // (ApplyParams::resize_on) instead of being refused
   UHDR_TRY(validate_apply(sdr, gm, md, out_ct, dest));
   // colour-space bookkeeping (jpegr.cpp:1616-1631)
   const int sdr_cg = sdr->cg == UHDR_CG_UNSPECIFIED ? UHDR_CG_BT_709 : sdr->cg;
@@ -29,15 +31,18 @@ static uhdr_error_info_t build_apply_params(uhdr_hip_ctx* c, const uhdr_raw_imag
     return err_status(UHDR_CODEC_INVALID_PARAM, "stripe offset y0=%u given without the full image height", y0);
   if ((uint64_t)y0 + sdr->h > whole_h)
     return err_status(UHDR_CODEC_INVALID_PARAM, "stripe rows [%u, %u) exceed the full image height %u", y0, y0 + sdr->h, whole_h);
+  bool resized = false;
   {
     const float pa = (float)sdr->w / whole_h, ga = (float)gm->w / gm->h;
-    if (fabsf(pa - ga) / pa > 0.01f)
+    if (fabsf(pa - ga) / pa > 0.01f) resized = true;
+    if (resized && !resize_in_kernel)
       return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE,
                         "gain map aspect ratio differs from the base image (%ux%u vs %ux%u): the reference's "
                         "resize_image fallback (jpegr.cpp:1659) is outside the HIP hot path",
                         gm->w, gm->h, sdr->w, whole_h);
   }
-  const float msf = (float)sdr->w / gm->w;
+  // the resized map has the base image's width (jpegr.cpp:1659, 1673)
+  const float msf = resized ? 1.0f : (float)sdr->w / gm->w;
   int msf_rnd = (int)roundf(msf);
   if (msf_rnd < 1) msf_rnd = 1;
   const bool use_table = (msf == floorf(msf));
@@ -79,6 +84,11 @@ static uhdr_error_info_t build_apply_params(uhdr_hip_ctx* c, const uhdr_raw_imag
   p.gm = view_of(gm);
   p.dst = view_mut_of(dest);
   p.y0 = y0;
+  if (resized) {
+    p.resize_on = 1;
+    p.resize_sx = (double)gm->w / sdr->w;
+    p.resize_sy = (double)gm->h / whole_h;
+  }
   p.map_ch = gm->fmt == UHDR_IMG_FMT_8bppYCbCr400 ? 1 : 3;
   p.map_bpp = gm->fmt == UHDR_IMG_FMT_8bppYCbCr400 ? 1 : (gm->fmt == UHDR_IMG_FMT_32bppRGBA8888 ? 4 : 3);
   p.out_ct = out_ct;
@@ -97,6 +107,11 @@ static uhdr_error_info_t build_apply_params(uhdr_hip_ctx* c, const uhdr_raw_imag
 
 namespace {
 constexpr uint64_t kMallHotBytes = 160ull << 20;
+// uhdr_hip_apply_gainmap_any: the route a map of another aspect ratio takes when UHDR_HIP_APPLY_RESIZE does not say.  Measured at
+// 3840 x 2160 (tools/resized_map_time.py, profiles/resized_map_time.json): the staged route's two launches -- the resize kernel and
+// the quad kernel at scale 1 -- take less time than the generic kernel with the resizing sampler, for Y400 and RGBA8888 maps and for
+// linear and PQ output alike, by more than the two spreads added.
+constexpr bool kResizeDefaultStaged = true;
 size_t input_bytes(const uhdr_raw_image_t* im) {
   size_t n = 0;
   const ImageView v = view_of(im);
@@ -139,6 +154,144 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_dev(uhdr_hip_ctx_t* c, const uhdr_raw_i
     HIP_TRY(launch_apply_gainmap(p, c->stream));
   }
   return ok_status();
+}
+
+// -------------------------------------------------------------------------------------------------
+// resize_image (editorhelper.cpp:100-146) on Y400 / RGB888 / RGBA8888
+// -------------------------------------------------------------------------------------------------
+static int resize_bpp(int fmt) {
+  return fmt == UHDR_IMG_FMT_8bppYCbCr400 ? 1 : (fmt == UHDR_IMG_FMT_24bppRGB888 ? 3 : (fmt == UHDR_IMG_FMT_32bppRGBA8888 ? 4 : 0));
+}
+
+uhdr_error_info_t uhdr_hip_resize_image_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* src, uhdr_raw_image_t* dst, unsigned int y0,
+                                            unsigned int full_height) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  if (!src || !dst) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
+  const int bpp = resize_bpp(src->fmt);
+  if (!bpp)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "resize_image is implemented for color formats {UHDR_IMG_FMT_8bppYCbCr400, "
+                      "UHDR_IMG_FMT_24bppRGB888, UHDR_IMG_FMT_32bppRGBA8888}. Received %d", src->fmt);
+  if (dst->fmt != src->fmt)
+    return err_status(UHDR_CODEC_INVALID_PARAM, "resize_image keeps the color format: source %d, destination %d", src->fmt, dst->fmt);
+  UHDR_TRY(validate_image(src, "source"));
+  UHDR_TRY(validate_image(dst, "destination"));
+  const unsigned int whole_h = full_height ? full_height : dst->h;
+  if (full_height == 0 && y0 != 0)
+    return err_status(UHDR_CODEC_INVALID_PARAM, "stripe offset y0=%u given without the full image height", y0);
+  if ((uint64_t)y0 + dst->h > whole_h)
+    return err_status(UHDR_CODEC_INVALID_PARAM, "stripe rows [%u, %u) exceed the full image height %u", y0, y0 + dst->h, whole_h);
+  if (src->w > 0x7fffffffu || src->h > 0x7fffffffu || dst->w > 0x7fffffffu || whole_h > 0x7fffffffu)
+    return err_status(UHDR_CODEC_INVALID_PARAM, "image dimensions beyond 2^31 - 1 are not supported");
+  HIP_TRY(hipSetDevice(c->device));
+  dst->cg = src->cg; dst->ct = src->ct; dst->range = src->range;
+  ResizePlane r;
+  r.src = src->planes[0];
+  r.dst = dst->planes[0];
+  r.src_w = src->w; r.src_h = src->h; r.dst_w = dst->w;
+  r.rows = dst->h; r.y0 = y0;
+  r.src_pitch = (size_t)src->stride[0] * bpp;
+  r.dst_pitch = (size_t)dst->stride[0] * bpp;
+  r.scale_x = (double)src->w / dst->w;
+  r.scale_y = (double)src->h / whole_h;
+  ProfScope ps(c, "resize_image");
+  HIP_TRY(launch_resize_image(r, bpp, c->stream));
+  return ok_status();
+}
+
+uhdr_error_info_t uhdr_hip_resize_image(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* src, uhdr_raw_image_t* dst) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  if (!src || !dst) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
+  if (!resize_bpp(src->fmt) || dst->fmt != src->fmt) {  // the device form's refusals, before anything is staged
+    uhdr_raw_image_t d = *dst;
+    return uhdr_hip_resize_image_dev(c, src, &d, 0, 0);
+  }
+  UHDR_TRY(validate_image(src, "source"));
+  UHDR_TRY(validate_image(dst, "destination"));
+  HIP_TRY(hipSetDevice(c->device));
+  uhdr_raw_image_t dsrc, ddst;
+  UHDR_TRY(stage_in(c, 0, src, &dsrc, true));
+  UHDR_TRY(stage_in(c, 1, dst, &ddst, false));
+  UHDR_TRY(uhdr_hip_resize_image_dev(c, &dsrc, &ddst, 0, 0));
+  dst->cg = ddst.cg; dst->ct = ddst.ct; dst->range = ddst.range;
+  return stage_out(c, &ddst, dst);
+}
+
+// -------------------------------------------------------------------------------------------------
+// applyGainMap for a gain map of any aspect ratio (jpegr.cpp:1651-1671 included)
+// -------------------------------------------------------------------------------------------------
+namespace {
+// The reference's decision (jpegr.cpp:1653-1658) on the whole image's height.  Arguments the old entry point refuses
+// (null images, empty images, a bad stripe) answer false: the old entry point then words the refusal.
+bool map_needs_resize(const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm, unsigned int y0, unsigned int full_height) {
+  if (!sdr || !gm || gm->w == 0 || gm->h == 0 || sdr->w == 0 || sdr->h == 0) return false;
+  const unsigned int whole_h = full_height ? full_height : sdr->h;
+  if ((full_height == 0 && y0 != 0) || (uint64_t)y0 + sdr->h > whole_h) return false;
+  const float pa = (float)sdr->w / whole_h, ga = (float)gm->w / gm->h;
+  return fabsf(pa - ga) / pa > 0.01f;
+}
+// UHDR_HIP_APPLY_RESIZE=staged|fused forces a route; otherwise the measured default
+bool resize_route_staged() {
+  if (const char* e = getenv("UHDR_HIP_APPLY_RESIZE")) {
+    if (!strcmp(e, "staged")) return true;
+    if (!strcmp(e, "fused")) return false;
+  }
+  return kResizeDefaultStaged;
+}
+}  // namespace
+
+uhdr_error_info_t uhdr_hip_apply_gainmap_any_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
+                                                 const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct, uhdr_img_fmt_t out_fmt,
+                                                 float max_display_boost, uhdr_raw_image_t* dest, unsigned int y0, unsigned int full_height) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  if (!map_needs_resize(sdr, gm, y0, full_height))
+    return uhdr_hip_apply_gainmap_dev(c, sdr, gm, md, out_ct, out_fmt, max_display_boost, dest, y0, full_height);
+  UHDR_TRY(validate_apply(sdr, gm, md, out_ct, dest));
+  HIP_TRY(hipSetDevice(c->device));
+  const DbgClock clk;
+  const bool staged = resize_route_staged();
+  ApplyParams p;
+  if (staged) {
+    // the map at the base image's size in scratch of the context (rows [y0, y0 + h) of it for a stripe, at their place in
+    // the whole map), then the usual launch at scale 1
+    const unsigned int whole_h = full_height ? full_height : sdr->h;
+    const int bpp = resize_bpp(gm->fmt);
+    uhdr_raw_image_t whole = *gm;
+    whole.w = sdr->w; whole.h = whole_h;
+    whole.stride[0] = (sdr->w + 63u) & ~63u;
+    UHDR_TRY(ensure(c->scratch[3], (size_t)whole.stride[0] * whole_h * bpp));
+    whole.planes[0] = c->scratch[3].p;
+    uhdr_raw_image_t stripe = whole;
+    stripe.h = sdr->h;
+    stripe.planes[0] = (uint8_t*)c->scratch[3].p + (size_t)y0 * whole.stride[0] * bpp;
+    UHDR_TRY(uhdr_hip_resize_image_dev(c, gm, &stripe, y0, whole_h));
+    UHDR_TRY(build_apply_params(c, sdr, &whole, md, out_ct, max_display_boost, dest, y0, full_height, &p));
+  } else {
+    UHDR_TRY(build_apply_params(c, sdr, gm, md, out_ct, max_display_boost, dest, y0, full_height, &p, true));
+  }
+  p.inputs_hot = mall_touch(c, sdr->planes[0], input_bytes(sdr) + input_bytes(gm)) ? 1u : 0u;
+  {
+    ProfScope ps(c, "apply_gainmap");
+    HIP_TRY(launch_apply_gainmap(p, c->stream));
+  }
+  clk.mark(staged ? "apply_gainmap_any: map of another aspect ratio, staged route (resize_image, then applyGainMap at scale 1)"
+                  : "apply_gainmap_any: map of another aspect ratio, fused route (resize inside the applyGainMap kernel)");
+  return ok_status();
+}
+
+uhdr_error_info_t uhdr_hip_apply_gainmap_any(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
+                                             const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct, uhdr_img_fmt_t out_fmt,
+                                             float max_display_boost, uhdr_raw_image_t* dest) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  UHDR_TRY(validate_apply(sdr, gm, md, out_ct, dest));
+  HIP_TRY(hipSetDevice(c->device));
+  uhdr_raw_image_t dsdr, dgm, ddst;
+  UHDR_TRY(stage_in(c, 0, sdr, &dsdr, true));
+  UHDR_TRY(stage_in(c, 1, gm, &dgm, true));
+  UHDR_TRY(stage_in(c, 2, dest, &ddst, false));
+  uhdr_error_info_t st = uhdr_hip_apply_gainmap_any_dev(c, &dsdr, &dgm, md, out_ct, out_fmt, max_display_boost, &ddst, 0, 0);
+  if (st.error_code != UHDR_CODEC_OK) return st;
+  dest->cg = ddst.cg;
+  return stage_out(c, &ddst, dest);
 }
 
 // Batch of n frames with identical geometry, formats, colour aspects and metadata (burst / video

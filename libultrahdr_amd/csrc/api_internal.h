@@ -110,7 +110,8 @@ struct uhdr_hip_ctx {
   hipEvent_t tab_ev[kTableSlots] = {};
   std::string tab_key[kTableSlots];
   int tab_next = 0;
-  // scratch for host-buffer entry points and two-pass generation
+  // scratch for host-buffer entry points and two-pass generation; [3]: the gain map at the base image's size
+  // (uhdr_hip_apply_gainmap_any, staged route)
   DeviceBuf scratch[8];
   uhdr_hip_stats_t stats = {};    // uhdr_hip_get_stats: which route the entropy stage took, call by call
   bool huff_serial_ok = true;  // uhdr_hip_jpeg_decode_scan clears it: a large marker-less scan that the parallel decoder cannot settle goes back to the caller

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "idct_core.h"
+#include "resize_core.h"
 #include "uhdr_types.h"
 
 namespace uhdr {
@@ -229,6 +230,33 @@ __device__ void sample_map_float(const ApplyParams& p, const float* u8f, uint32_
   }
 }
 
+// gain map of another aspect ratio than the base image (jpegr.cpp:1651-1671): the reference first makes a map of the base
+// image's size with resize_image (editorhelper.cpp:100-146) and then samples it at scale 1, where the Shepard weights are
+// (1, 0, 0, 0) and the sample is exactly resized_byte / 255.0f.  Here the resized byte is computed per output pixel from the
+// ORIGINAL map (resize_core.h), so the full-resolution map never exists in memory.  yg: row of the whole image.
+template <int NCH>
+__device__ __forceinline__ void sample_map_resized(const ApplyParams& p, const float* u8f, uint32_t x, uint32_t yg, float out[3]) {
+  double frac, unused;
+  const ResizeAxis rx = resize_axis(x, p.resize_sx, p.gm.w, &frac);
+  const ResizeAxis ry = resize_axis(yg, p.resize_sy, p.gm.h, &unused);
+  const ResizeWeights w = resize_weights(frac);
+  const uint8_t* d = (const uint8_t*)p.gm.p[0];
+  const size_t st = p.gm.stride[0];
+  const int bpp = p.map_bpp;
+  const uint8_t* a0 = d + (rx.lo + ry.lo * st) * bpp;
+  const uint8_t* a1 = d + (rx.hi + ry.lo * st) * bpp;
+  const uint8_t* a2 = d + (rx.lo + ry.hi * st) * bpp;
+  const uint8_t* a3 = d + (rx.hi + ry.hi * st) * bpp;
+#pragma unroll
+  for (int c = 0; c < NCH; c++) {
+    uint32_t b;
+    // getYuv400Pixel multiplies by (1 / 255.0f); the RGB readers divide by 255.0f, which is the u8f table (gainmapmath.cpp:389-470)
+    if (NCH == 1) b = resize_byte(w, (float)a0[c] * (1 / 255.0f), (float)a1[c] * (1 / 255.0f), (float)a2[c] * (1 / 255.0f), (float)a3[c] * (1 / 255.0f));
+    else b = resize_byte(w, u8f[a0[c]], u8f[a1[c]], u8f[a2[c]], u8f[a3[c]]);
+    out[c] = u8f[b];
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // generic kernel: one thread per pixel, every base format / scale; the sRGB, gain and byte -> float tables
 // live in LDS (the IDW weights, whose size depends on the scale, stay in global memory), a workgroup
@@ -282,11 +310,13 @@ __global__ __launch_bounds__(kBlock) void apply_generic_kernel(const ApplyParams
     float gn[3];
     const uint32_t yg = y + p.y0;
     if (p.map_ch == 1) {
-      if (p.scale) sample_map_table<1>(p, u8f, idw, x, yg, gn);
+      if (p.resize_on) sample_map_resized<1>(p, u8f, x, yg, gn);
+      else if (p.scale) sample_map_table<1>(p, u8f, idw, x, yg, gn);
       else sample_map_float<1>(p, u8f, x, yg, gn);
       gn[1] = gn[2] = gn[0];
     } else {
-      if (p.scale) sample_map_table<3>(p, u8f, idw, x, yg, gn);
+      if (p.resize_on) sample_map_resized<3>(p, u8f, x, yg, gn);
+      else if (p.scale) sample_map_table<3>(p, u8f, idw, x, yg, gn);
       else sample_map_float<3>(p, u8f, x, yg, gn);
     }
     float f0 = gain_factor(gn[0], gain_tab, 0, p), f1 = f0, f2 = f0;
@@ -1269,6 +1299,7 @@ inline bool aligned_to(const void* ptr, size_t a) { return ((uintptr_t)ptr % a) 
 
 // Does the quad kernel's layout contract hold?  Returns its SMODE (0 / 1) or -1.
 int apply_quad_mode(const ApplyParams& p) {
+  if (p.resize_on) return -1;  // the resizing sampler exists in the generic kernel only
   const int out = p.out_ct == UHDR_CT_LINEAR ? 0 : (p.out_ct == UHDR_CT_HLG ? 1 : 2);
   const int mapfmt = p.gm.fmt == UHDR_IMG_FMT_8bppYCbCr400 ? 0 : (p.gm.fmt == UHDR_IMG_FMT_24bppRGB888 ? 1 : 2);
   const size_t out_bytes = out == 0 ? 8 : 4;

@@ -121,6 +121,11 @@ struct ApplyParams {
   Mat3 gamut;               // hdr_cg <- sdr_cg
   Yuv2Rgb yuv;              // always the BT.601 set (jpegr.cpp:1723)
   const CoefSrc* coef_src;  // quad kernel, SRC 1 only: the base image in coefficient form (p.sdr then carries geometry only)
+  // generic kernel only: `gm` has another aspect ratio than the base image and every sample is the byte resize_image
+  // (editorhelper.cpp:100-146) would have stored at this pixel of a map of the base image's size (sample_map_resized);
+  // scale is 1 then.  resize_sx / resize_sy: (double)gm.w / base width, (double)gm.h / the WHOLE base image's height.
+  int resize_on;
+  double resize_sx, resize_sy;
   FramePtrs frame_tab[kMaxBatchFrames];  // batch: plane pointers of the launch's frames, read with scalar loads from the kernel arguments
 };
 
@@ -295,6 +300,16 @@ struct EffectPlane {
   uint32_t a0, a1;                     // crop: left, top; resize: src_w / dst_w, src_h / dst_h
 };
 hipError_t launch_effect_plane(const EffectPlane& p, hipStream_t s);
+// ---- resize_image (resize_image.hip) -------------------------------------------------------------------
+struct ResizePlane {
+  const void* src;
+  void* dst;                     // row 0 of the destination STRIPE
+  uint32_t src_w, src_h, dst_w;  // pixels
+  uint32_t rows, y0;             // stripe: `rows` destination rows starting at row y0 of the whole destination
+  size_t src_pitch, dst_pitch;   // bytes
+  double scale_x, scale_y;       // (double)src_w / dst_w, (double)src_h / the whole destination's height
+};
+hipError_t launch_resize_image(const ResizePlane& p, int bpp, hipStream_t s);  // bpp: 1 Y400, 3 RGB888, 4 RGBA8888
 
 // ---- baseline Huffman entropy coding (huffman_encode.hip) -------------------------------------------
 struct HuffArgs {

@@ -434,6 +434,36 @@ class UltraHdr:
                 self.ctx.handle, C.byref(sdr_intent.raw), C.byref(gainmap_img.raw), C.byref(gainmap_metadata),
                 output_ct, output_format, max_display_boost, C.byref(dest.raw)))
 
+    def applyGainMapAny(self, sdr_intent: Image, gainmap_img: Image, gainmap_metadata: A.GainmapMetadata,
+                        output_ct: int, output_format: int, max_display_boost: float, dest: Image,
+                        y0: int = 0, full_height: int = 0):
+        """applyGainMap including the reference's resize step (jpegr.cpp:1651-1671): a gain map whose aspect ratio differs from
+        the base image's by more than 1 % is resized to the base image's size as resize_image does (uhdr_hip_apply_gainmap_any /
+        _any_dev); applyGainMap keeps refusing it.  UHDR_HIP_APPLY_RESIZE=staged|fused forces one of the two routes."""
+        if _is_dev(sdr_intent, gainmap_img, dest):
+            self._call(True, self.lib.uhdr_hip_apply_gainmap_any_dev,
+                       self.ctx.handle, C.byref(sdr_intent.raw), C.byref(gainmap_img.raw), C.byref(gainmap_metadata),
+                       output_ct, output_format, max_display_boost, C.byref(dest.raw), y0, full_height)
+        else:
+            if y0 or full_height:
+                raise ValueError("stripes are a device-buffer feature")
+            A.check(self.lib.uhdr_hip_apply_gainmap_any(
+                self.ctx.handle, C.byref(sdr_intent.raw), C.byref(gainmap_img.raw), C.byref(gainmap_metadata),
+                output_ct, output_format, max_display_boost, C.byref(dest.raw)))
+
+    def resizeImage(self, src: Image, dst_w: int, dst_h: int, dst: Image = None, y0: int = 0, full_height: int = 0) -> Image:
+        """resize_image (editorhelper.cpp:88-146) of a Y400 / RGB888 / RGBA8888 image to dst_w x dst_h.  dst: a caller-made
+        image (device images: possibly a row stripe, y0 / full_height as for applyGainMap); by default one is allocated."""
+        if dst is None:
+            dst = Image(src.fmt, dst_w, dst_h, align=64, device=src.device)
+        if _is_dev(src, dst):
+            self._call(True, self.lib.uhdr_hip_resize_image_dev, self.ctx.handle, C.byref(src.raw), C.byref(dst.raw), y0, full_height)
+        else:
+            if y0 or full_height:
+                raise ValueError("stripes are a device-buffer feature")
+            A.check(self.lib.uhdr_hip_resize_image(self.ctx.handle, C.byref(src.raw), C.byref(dst.raw)))
+        return dst
+
     def applyGainMapFromCoefficients(self, coefs, qtables, w: int, h: int, base_cg: int, gainmap_img: Image,
                                      gainmap_metadata: A.GainmapMetadata, output_ct: int, output_format: int,
                                      max_display_boost: float, dest: Image, sampling: str = "420"):
