@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import code_lattice as CL
 from libultrahdr_amd import capi as A
 from libultrahdr_amd import synth
 from libultrahdr_amd.images import Image
@@ -15,8 +16,10 @@ from oracle import loader as L
 pytestmark = pytest.mark.gpu
 
 FULL, LIMITED = A.UHDR_CR_FULL_RANGE, A.UHDR_CR_LIMITED_RANGE
-# one transfer / gamut pair per gamut mode of the kernel: SDR-side conversion, none, HDR-side conversion
-PAIRS = [(A.UHDR_CT_HLG, A.UHDR_CG_BT_2100, LIMITED), (A.UHDR_CT_PQ, A.UHDR_CG_DISPLAY_P3, FULL), (A.UHDR_CT_HLG, A.UHDR_CG_BT_709, LIMITED)]
+# one transfer / gamut pair per gamut mode of the kernel: SDR-side conversion, none, HDR-side conversion; then a linear intent, which
+# has no linearisation table (the kernel's LUT = false instantiations)
+PAIRS = [(A.UHDR_CT_HLG, A.UHDR_CG_BT_2100, LIMITED), (A.UHDR_CT_PQ, A.UHDR_CG_DISPLAY_P3, FULL), (A.UHDR_CT_HLG, A.UHDR_CG_BT_709, LIMITED),
+         (A.UHDR_CT_LINEAR, A.UHDR_CG_BT_2100, FULL)]
 CONFIGS = [dict(preset=A.UHDR_USAGE_REALTIME), dict(preset=A.UHDR_USAGE_BEST_QUALITY),
            dict(preset=A.UHDR_USAGE_REALTIME, use_multi_channel_gainmap=0),
            dict(preset=A.UHDR_USAGE_BEST_QUALITY, use_multi_channel_gainmap=0),
@@ -80,6 +83,34 @@ def test_fused_p010_front_end_equals_tone_map_then_generate_gainmap(hip_ctx, w, 
     assert md_f.as_dict() == md_s.as_dict()
     assert _desc(base_f) == _desc(base_s) and _desc(gm_f) == _desc(gm_s)
     assert base_f.raw.fmt == A.UHDR_IMG_FMT_12bppYCbCr420 and base_f.raw.cg == A.UHDR_CG_DISPLAY_P3 and base_f.raw.range == FULL
+
+
+LATTICE_IMAGES = [(rng, ct, cg) for rng in (LIMITED, FULL) for ct in (CL.HLG, CL.PQ, CL.LINEAR) for cg in (CL.BT2100, CL.P3, CL.BT709)]
+
+
+@pytest.mark.parametrize("rng,ct,cg", LATTICE_IMAGES)
+def test_fused_p010_front_end_on_the_code_lattice(hip_ctx, rng, ct, cg):
+    """The P010 lattice image of tests/code_lattice.py -- every luma code, both chroma ramps against zero, draws from the ends of
+    the code range, the limited-range bounds and their outsides, YCbCr triples outside the RGB cube -- in both ranges, under every
+    transfer (LINEAR: no linearisation table) and in the kernel's three gamut modes, through every configuration: the fused front
+    end equals the staged route bit for bit.  (The staged operators are held to the oracle on these images in
+    test_gpu_code_lattice.py.)"""
+    w, h = CL.SIZE_MAIN
+    hdr = CL.hdr(CL.HP010, w, h, ct=ct, cg=cg, rng_range=rng)
+    dh = hdr.to("cuda:0")
+    y, cb, cr = CL.channels(dh.to_host())
+    assert len(np.unique(y)) == 1024 and len(np.unique(cb)) == 1024 and len(np.unique(cr)) == 1024
+    for cfg_kw in CONFIGS:
+        cfg = A.default_encode_cfg(use_luminance=0, **cfg_kw)
+        u = _uhdr_for(hip_ctx, cfg)
+        base_f, md_f, gm_f = u.encodeApi0FusedP010(dh)
+        hip_ctx.synchronize()
+        base_s, md_s, gm_s = _staged(u, dh)
+        hip_ctx.synchronize()
+        assert planes_equal(base_f, base_s), f"base image planes, {cfg_kw}"
+        assert planes_equal(gm_f, gm_s), f"gain map, {cfg_kw}"
+        assert md_f.as_dict() == md_s.as_dict(), cfg_kw
+        assert _desc(base_f) == _desc(base_s) and _desc(gm_f) == _desc(gm_s), cfg_kw
 
 
 @pytest.mark.parametrize("ct,cg,rng", PAIRS)

@@ -34,7 +34,7 @@ def _remap(a: np.ndarray, effect, p0, p1, dw, dh) -> np.ndarray:
         return a[::-1] if p0 == 0 else a[:, ::-1]
     if effect == 2:
         return a[p1: p1 + dh, p0: p0 + dw]
-    fy, fx = a.shape[0] // dh, a.shape[1] // dw
+    fy, fx = a.shape[0] // dh, a.shape[1] // dw  # 0 along an axis that grows: resize_buffer then repeats row / column 0
     return a[np.arange(dh) * fy][:, np.arange(dw) * fx]
 
 
