@@ -419,15 +419,24 @@ bool encode_api0(uhdr_raw_image_t* hdr_intent, int base_quality, int map_quality
   // UHDR_HIP_SEAM_FUSED_P010; without it the per-stage seams run as before
   const bool p010 = hdr_intent->fmt == UHDR_IMG_FMT_24bppYCbCrP010 && getenv("UHDR_HIP_SEAM_FUSED_P010") != nullptr;
   if (!p010 && hdr_intent->fmt != UHDR_IMG_FMT_32bppRGBA1010102 && hdr_intent->fmt != UHDR_IMG_FMT_64bppRGBAHalfFloat) return false;
-  if (*scale_factor != 1) return false;
+  // a sub-sampled map (scale factor 2 or 4) takes the fused route only when asked to: UHDR_HIP_SEAM_FUSED_SCALED_MAP; what
+  // uhdr_hip_encode_api0_scans_scaled would decline is declined here, before anything goes up
+  const unsigned scale = (unsigned)*scale_factor;
+  const bool sub = (*scale_factor == 2 || *scale_factor == 4) && getenv("UHDR_HIP_SEAM_FUSED_SCALED_MAP") != nullptr;
+  if (*scale_factor != 1 && !sub) return false;
   const unsigned w = hdr_intent->w, h = hdr_intent->h;
   const unsigned grid = p010 ? 16 : 8;  // whole MCUs: 2x2 / 1x1 / 1x1 sampling for P010, 1x1 otherwise
   if (w == 0 || h == 0 || w % grid || h % grid || w > 65535 || h > 65535) return false;
+  if (sub) {  // no half float, a map of whole blocks, pitches the vector loads can read
+    if (hdr_intent->fmt == UHDR_IMG_FMT_64bppRGBAHalfFloat || (w / scale) % 8 || (h / scale) % 8) return false;
+    if (p010 ? (hdr_intent->stride[0] % 2 || hdr_intent->stride[1] % 2) : (hdr_intent->stride[0] % 4 != 0)) return false;
+  }
+  const unsigned mw = w / scale, mh = h / scale;  // the map's own dimensions
   if (map_icc_size > 65533 || (map_comment && strlen(map_comment) > 65533)) return false;
   if (base_quality < 0 || base_quality > 100 || map_quality < 0 || map_quality > 100) return false;
   enter();
   uhdr_hip_encode_cfg_t cfg;
-  cfg.map_dimension_scale_factor = 1;
+  cfg.map_dimension_scale_factor = (int)scale;
   cfg.use_multi_channel_gainmap = multi_channel;
   cfg.gamma = gamma;
   cfg.preset = UHDR_USAGE_REALTIME;  // jpegr.cpp:207
@@ -447,14 +456,14 @@ bool encode_api0(uhdr_raw_image_t* hdr_intent, int base_quality, int map_quality
   memset(&sm, 0, sizeof sm);
   sb.num_components = 3;
   sm.num_components = nch;
-  sb.w = sm.w = w;
-  sb.h = sm.h = h;
+  sb.w = w; sm.w = mw;
+  sb.h = h; sm.h = mh;
   for (int i = 0; i < 3; i++) {
-    const unsigned sub = (p010 && i) ? 16 : 8;
-    sb.blocks_w[i] = (int)(w / sub); sb.blocks_h[i] = (int)(h / sub);
+    const unsigned blk = (p010 && i) ? 16 : 8;
+    sb.blocks_w[i] = (int)(w / blk); sb.blocks_h[i] = (int)(h / blk);
     sb.h_samp[i] = sb.v_samp[i] = (p010 && !i) ? 2 : 1;
   }
-  for (int i = 0; i < nch; i++) { sm.blocks_w[i] = (int)(w / 8); sm.blocks_h[i] = (int)(h / 8); sm.h_samp[i] = sm.v_samp[i] = 1; }
+  for (int i = 0; i < nch; i++) { sm.blocks_w[i] = (int)(mw / 8); sm.blocks_h[i] = (int)(mh / 8); sm.h_samp[i] = sm.v_samp[i] = 1; }
   unsigned char hb[2048], hm[2048];
   const unsigned char none = 0;
   const size_t nhb = uhdr_hip_jpeg_assemble(&sb, qt_base[0], qt_base[1], &none, 0, hb, sizeof hb);
@@ -465,7 +474,7 @@ bool encode_api0(uhdr_raw_image_t* hdr_intent, int base_quality, int map_quality
   constexpr size_t kIccRoom = 4096;
   const size_t lead_m = lead_bytes(nhm, map_icc ? map_icc_size : 0, map_comment);
   const size_t lead_b_max = lead_bytes(nhb, kIccRoom, nullptr);
-  size_t cap_b = (size_t)w * h * 3 + (1u << 16), cap_m = (size_t)w * h * nch + (1u << 16);  // one byte per coefficient: never seen exceeded
+  size_t cap_b = (size_t)w * h * 3 + (1u << 16), cap_m = (size_t)mw * mh * nch + (1u << 16);  // one byte per coefficient: never seen exceeded
   if (const char* e = getenv("UHDR_HIP_SEAM_TEST_SMALL_CAP")) {  // (tests: the second attempt below)
     const size_t div = (size_t)(atoi(e) > 1 ? atoi(e) : 16);
     cap_b /= div;
@@ -482,8 +491,9 @@ bool encode_api0(uhdr_raw_image_t* hdr_intent, int base_quality, int map_quality
     out->gainmap_data.reset(new (std::nothrow) unsigned char[lead_m + cap_m + 2]);
     if (!out->base_data || !out->gainmap_data) return false;
     nb = nm = 0;
-    *st = uhdr_hip_encode_api0_scans_any(cur(), hdr_intent, &cfg, qt_base, qt_map, &md, &gm_desc, &cg, out->base_data.get() + lead_b_max, cap_b, &nb,
-                                         out->gainmap_data.get() + lead_m, cap_m, &nm);
+    *st = (sub ? uhdr_hip_encode_api0_scans_scaled : uhdr_hip_encode_api0_scans_any)(cur(), hdr_intent, &cfg, qt_base, qt_map, &md, &gm_desc, &cg,
+                                                                                     out->base_data.get() + lead_b_max, cap_b, &nb,
+                                                                                     out->gainmap_data.get() + lead_m, cap_m, &nm);
     if (st->error_code == UHDR_CODEC_MEM_ERROR && attempt == 0 && (nb > cap_b || nm > cap_m)) {  // (as in encode_api1: once more with the reported sizes)
       note("encode_api0_fused", true, "scan larger than one byte per coefficient: second attempt with the reported sizes");
       if (nb > cap_b) cap_b = nb + nb / 16 + (1u << 16);

@@ -29,6 +29,7 @@
  *   _pass2_dev (two-pass generation split at its only exchange step, for row stripes across GPUs),
  *   uhdr_hip_encode_api0_fused_dev (toneMap + generateGainMap + convert_raw_input_to_ycbcr in one pass),
  *   uhdr_hip_encode_api0_p010_fused_dev (toneMap + generateGainMap of a P010 intent in one pass),
+ *   uhdr_hip_encode_api0_fused_scaled_dev / uhdr_hip_encode_api0_p010_fused_scaled_dev (the same at gain-map scale factor 1, 2 or 4),
  *   uhdr_hip_fdct_quant_rgb_dev (colour conversion + FDCT of a 3-channel map in one pass),
  *   uhdr_hip_idct_dequant_rgb_dev (its decode-side mirror: dequant + IDCT + colour conversion in one pass),
  *   uhdr_hip_apply_gainmap_coef_dev / _coef422_dev / _coef444_dev (applyGainMap on a base image still in coefficient form: IDCT inside the kernel),
@@ -417,6 +418,23 @@ uhdr_error_info_t uhdr_hip_encode_api0_fused_dev(uhdr_hip_ctx_t* ctx, const uhdr
 uhdr_error_info_t uhdr_hip_encode_api0_p010_fused_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* hdr,
                                                       const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* base_ycc420,
                                                       uhdr_gainmap_metadata_t* metadata, uhdr_raw_image_t* gainmap);
+
+/* MI355X extension: the two front ends above for a sub-sampled gain map as well -- JpegR::encodeJPEGR API-0 (lib/src/jpegr.cpp:179-244) with
+ * map_dimension_scale_factor 2 or 4 (kMapDimensionScaleFactorAndroidDefault is 4).  samplePixels (lib/src/gainmapmath.cpp:494-535) averages the
+ * gamma-encoded samples of each S x S box of both images and the mean is linearised; the kernels sum the bytes they have just written and the
+ * codes they have just read in that order, so the outputs are bit-identical to uhdr_hip_tone_map_dev -> uhdr_hip_generate_gainmap_dev
+ * (-> uhdr_hip_convert_raw_input_to_ycbcr_dev) at that scale factor.  Same parameters as the siblings; gainmap is (w / S) x (h / S).
+ * Scale factor 1: exactly what the sibling does.  Scale factor 2 / 4: one pass only.  UHDR_CODEC_UNSUPPORTED_FEATURE, before anything is
+ * launched, for any other scale factor and, at 2 / 4, for a half-float intent, UHDR_USAGE_BEST_QUALITY, a width that is not a multiple of 4,
+ * a height that is not a multiple of S, and layouts the vector accesses cannot take (RGBA1010102: 16-byte aligned intent and rendition, 4-byte
+ * aligned base planes, strides that are multiples of 4; P010: as the sibling).  The map is stored byte by byte: any stride and base. */
+uhdr_error_info_t uhdr_hip_encode_api0_fused_scaled_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* hdr,
+                                                        const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* sdr_rgba,
+                                                        uhdr_raw_image_t* base_ycc, uhdr_gainmap_metadata_t* metadata,
+                                                        uhdr_raw_image_t* gainmap);
+uhdr_error_info_t uhdr_hip_encode_api0_p010_fused_scaled_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* hdr,
+                                                             const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* base_ycc420,
+                                                             uhdr_gainmap_metadata_t* metadata, uhdr_raw_image_t* gainmap);
 
 /* copy_raw_image(src, dst) (lib/src/gainmapmath.cpp:1492-1613) between device images: strided plane copies
  * for equal formats, RGB888 -> RGBA8888 (alpha 0xff), RGBA8888 -> Y400 (R byte); same error codes
@@ -864,6 +882,18 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans_any(uhdr_hip_ctx_t* ctx, const uhdr
                                                  uhdr_raw_image_t* gainmap_desc, uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan,
                                                  size_t base_capacity, size_t* base_bytes, uint8_t* map_scan, size_t map_capacity,
                                                  size_t* map_bytes);
+
+/* uhdr_hip_encode_api0_scans_any for a sub-sampled gain map as well (lib/src/jpegr.cpp:179-244 with map_dimension_scale_factor 2 or 4;
+ * samplePixels, lib/src/gainmapmath.cpp:494-535): everything uhdr_hip_encode_api0_scans_any takes, and RGBA1010102 / P010 intents at scale
+ * factor 2 and 4 through uhdr_hip_encode_api0_fused_scaled_dev / uhdr_hip_encode_api0_p010_fused_scaled_dev; the map's blocks come from the
+ * (w / S) x (h / S) image and gainmap_desc carries those dimensions.  UHDR_CODEC_UNSUPPORTED_FEATURE before anything is uploaded: any other
+ * scale factor, a half-float intent at 2 / 4, dimensions that are not whole MCUs (8; 16 for P010), a map that is not whole blocks (w / S or
+ * h / S not a multiple of 8), strides the vector loads cannot read, a context with a communicator.  The preset is overridden as in the sibling. */
+uhdr_error_info_t uhdr_hip_encode_api0_scans_scaled(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                    const uint16_t qt_base[2][64], const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md,
+                                                    uhdr_raw_image_t* gainmap_desc, uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan,
+                                                    size_t base_capacity, size_t* base_bytes, uint8_t* map_scan, size_t map_capacity,
+                                                    size_t* map_bytes);
 
 /* The same on DEVICE-resident intents into DEVICE buffers, and its inverse (round 6): one entry point per direction of the API-1
  * round trip, for callers whose images live in HBM (a transcoding service; bench.py's headline).

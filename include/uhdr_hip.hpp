@@ -182,6 +182,37 @@ class UltraHdr {
                                           base_bytes, map_scan, map_capacity, map_bytes);
   }
 
+  // The API-0 front ends for a gain map at scale factor 1, 2 or 4 (uhdr_hip_encode_api0_fused_scaled_dev for RGBA1010102 / RGBA half-float
+  // intents, uhdr_hip_encode_api0_p010_fused_scaled_dev for P010): device images the caller allocated, gainmap_img of (w / S) x (h / S) pixels;
+  // sdr_rgba may be null.  Scale factor 2 / 4: one pass (UHDR_USAGE_REALTIME), RGBA1010102 or P010.
+  uhdr_error_info_t encodeApi0FusedScaled(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_rgba, uhdr_raw_image_t* base_ycc,
+                                          uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_raw_image_t* gainmap_img, bool use_luminance = false) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, 0, use_luminance ? 1 : 0};
+    return uhdr_hip_encode_api0_fused_scaled_dev(mCtx, hdr_intent, &cfg, sdr_rgba, base_ycc, gainmap_metadata, gainmap_img);
+  }
+  uhdr_error_info_t encodeApi0FusedP010Scaled(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* base_ycc420, uhdr_gainmap_metadata_t* gainmap_metadata,
+                                              uhdr_raw_image_t* gainmap_img, bool use_luminance = false) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, 0, use_luminance ? 1 : 0};
+    return uhdr_hip_encode_api0_p010_fused_scaled_dev(mCtx, hdr_intent, &cfg, base_ycc420, gainmap_metadata, gainmap_img);
+  }
+
+  // encodeApi0ScansAny for a gain map at scale factor 1, 2 or 4 (uhdr_hip_encode_api0_scans_scaled): 2 and 4 for RGBA1010102 and P010 intents
+  // whose map is whole 8 x 8 blocks; gainmap_desc carries the map's dimensions.
+  uhdr_error_info_t encodeApi0ScansScaled(uhdr_raw_image_t* hdr_intent, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                          uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_raw_image_t* gainmap_desc, uhdr_color_gamut_t* sdr_cg,
+                                          uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan, size_t map_capacity,
+                                          size_t* map_bytes) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, 0, 0};
+    return uhdr_hip_encode_api0_scans_scaled(mCtx, hdr_intent, &cfg, qt_base, qt_map, gainmap_metadata, gainmap_desc, sdr_cg, base_scan, base_capacity,
+                                             base_bytes, map_scan, map_capacity, map_bytes);
+  }
+
   // The sample -> coefficient part of an API-1 encode on device-resident intents (uhdr_hip_encode_api1_fused_any_dev): the SDR intent is
   // YCbCr 4:2:0 (multiples of 16) or RGBA8888 (multiples of 8; its base image is 4:4:4, three (w/8)*(h/8) coefficient arrays).
   // blocks: device buffers; gainmap_img may be null.

@@ -229,6 +229,8 @@ _SIGS = {
                                                C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "uhdr_hip_encode_api0_scans_any": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(EncodeCfg), C.c_void_p, C.c_void_p, _P(GainmapMetadata), _P(RawImage), _P(C.c_int),
                                                C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
+    "uhdr_hip_encode_api0_scans_scaled": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(EncodeCfg), C.c_void_p, C.c_void_p, _P(GainmapMetadata), _P(RawImage), _P(C.c_int),
+                                                      C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "uhdr_hip_encode_api1_scans_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(EncodeCfg), C.c_int, C.c_void_p, C.c_void_p, _P(GainmapMetadata),
                                                    _P(RawImage), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "uhdr_hip_decode_api1_scans_dev": (ErrorInfo, [C.c_void_p, _P(JpegHeader), C.c_void_p, C.c_size_t, C.c_int, _P(JpegHeader), C.c_void_p, C.c_size_t, C.c_int,
@@ -241,6 +243,8 @@ _SIGS = {
     "uhdr_hip_fdct_quant_dev": (ErrorInfo, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, _P(C.c_uint16), C.c_void_p]),
     "uhdr_hip_encode_api0_fused_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(EncodeCfg), _P(RawImage), _P(RawImage), _P(GainmapMetadata), _P(RawImage)]),
     "uhdr_hip_encode_api0_p010_fused_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(EncodeCfg), _P(RawImage), _P(GainmapMetadata), _P(RawImage)]),
+    "uhdr_hip_encode_api0_fused_scaled_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(EncodeCfg), _P(RawImage), _P(RawImage), _P(GainmapMetadata), _P(RawImage)]),
+    "uhdr_hip_encode_api0_p010_fused_scaled_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(EncodeCfg), _P(RawImage), _P(GainmapMetadata), _P(RawImage)]),
     "uhdr_hip_copy_raw_image_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage)]),
     "uhdr_hip_fdct_quant_rgb_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(C.c_uint16), _P(C.c_uint16), C.c_void_p, C.c_void_p, C.c_void_p]),
     "uhdr_hip_idct_dequant": (ErrorInfo, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _P(C.c_uint16), C.c_void_p, C.c_size_t]),

@@ -108,17 +108,37 @@ uhdr_error_info_t uhdr_hip_fdct_quant_rgb_dev(uhdr_hip_ctx_t* c, const uhdr_raw_
 // -------------------------------------------------------------------------------------------------
 // API-0 front end fused: toneMap + generateGainMap + convert_raw_input_to_ycbcr(4:4:4) in one pass
 // -------------------------------------------------------------------------------------------------
-uhdr_error_info_t uhdr_hip_encode_api0_fused_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
-                                                 uhdr_raw_image_t* sdr_rgba, uhdr_raw_image_t* base_ycc, uhdr_gainmap_metadata_t* md,
-                                                 uhdr_raw_image_t* gm) {
+// What the scaled entry points decline at scale factor 2 / 4 whatever the intent format (nothing has been launched): any other factor, the
+// two-pass preset (API-0 is one pass, jpegr.cpp:207), a width that is not whole 4-pixel cells or a height that is not whole strips.
+static uhdr_error_info_t check_scaled_request(const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg, bool any_preset) {
+  const int s = cfg->map_dimension_scale_factor;
+  if (s != 1 && s != 2 && s != 4)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 front end takes gain-map scale factors 1, 2 and 4, received %d; use the operators", s);
+  if (s == 1) return ok_status();
+  if (hdr->fmt == UHDR_IMG_FMT_64bppRGBAHalfFloat)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 front end takes a half-float intent at scale factor 1 only (received %d); use the operators", s);
+  if (!any_preset && cfg->preset != UHDR_USAGE_REALTIME)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 front end at scale factor %d is the one-pass (UHDR_USAGE_REALTIME) encode; use the operators", s);
+  if (hdr->w == 0 || hdr->h == 0 || hdr->w % 4 || hdr->h % (unsigned)s)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 front end at scale factor %d needs a width that is a multiple of 4 and a height that is a "
+                      "multiple of %d (received %ux%u); use the operators", s, s, hdr->w, hdr->h);
+  return ok_status();
+}
+
+// scaled == false: uhdr_hip_encode_api0_fused_dev; true: uhdr_hip_encode_api0_fused_scaled_dev, which also takes scale factors 2 and 4
+static uhdr_error_info_t encode_api0_fused_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                uhdr_raw_image_t* sdr_rgba, uhdr_raw_image_t* base_ycc, uhdr_gainmap_metadata_t* md,
+                                                uhdr_raw_image_t* gm, bool scaled) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!hdr || !cfg || !base_ycc || !md || !gm || !gm->planes[0]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
   if (hdr->fmt != UHDR_IMG_FMT_32bppRGBA1010102 && hdr->fmt != UHDR_IMG_FMT_64bppRGBAHalfFloat)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 front end takes UHDR_IMG_FMT_32bppRGBA1010102 or UHDR_IMG_FMT_64bppRGBAHalfFloat "
                       "(the inputs toneMap renders to RGBA8888). Received %d", hdr->fmt);
-  if (cfg->map_dimension_scale_factor != 1)
+  if (!scaled && cfg->map_dimension_scale_factor != 1)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 front end needs a full-resolution gain map (scale factor 1), received %d; "
                       "use tone_map + generate_gainmap + convert_raw_input_to_ycbcr", cfg->map_dimension_scale_factor);
+  if (scaled) UHDR_TRY(check_scaled_request(hdr, cfg, false));
+  const bool sub = cfg->map_dimension_scale_factor != 1;  // the scaled kernel
   if (hdr->cg < UHDR_CG_BT_709 || hdr->cg > UHDR_CG_BT_2100)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "No implementation available for color gamut %d", hdr->cg);
   if (hdr->ct < UHDR_CT_LINEAR || hdr->ct > UHDR_CT_SRGB)
@@ -152,6 +172,9 @@ uhdr_error_info_t uhdr_hip_encode_api0_fused_dev(uhdr_hip_ctx_t* c, const uhdr_r
   base_ycc->w = hdr->w; base_ycc->h = hdr->h;
   p.ycc = view_mut_of(base_ycc);
   p.base_k = host::rgb2yuv_coeffs(UHDR_CG_DISPLAY_P3);
+  if (sub && !encode_api0_fused_scaled_layout_ok(p))
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 front end at scale factor %d reads and writes vectors: a 16-byte aligned intent and rendition, "
+                      "4-byte aligned base planes, strides that are multiples of 4; use the operators", cfg->map_dimension_scale_factor);
   if (cfg->preset == UHDR_USAGE_REALTIME) {  // one pass: jpegr.cpp:724-737
     for (int i = 0; i < 3; i++) {
       md->max_content_boost[i] = hdr_white_nits / 203.0f;
@@ -173,7 +196,8 @@ uhdr_error_info_t uhdr_hip_encode_api0_fused_dev(uhdr_hip_ctx_t* c, const uhdr_r
     p.gen.out = (uint8_t*)gm->planes[0];
     p.gen.out_stride = gm->stride[0];
     ProfScope ps(c, "encode_api0_fused");
-    HIP_TRY(launch_encode_api0_fused(p, false, nullptr, c->stream));
+    if (sub) HIP_TRY(launch_encode_api0_fused_scaled(p, c->stream));
+    else HIP_TRY(launch_encode_api0_fused(p, false, nullptr, c->stream));
     return ok_status();
   }
   const size_t nfl = (size_t)p.gen.map_w * p.gen.map_h * (p.gen.multichannel ? 3 : 1);
@@ -193,6 +217,16 @@ uhdr_error_info_t uhdr_hip_encode_api0_fused_dev(uhdr_hip_ctx_t* c, const uhdr_r
   note_table_stats(c, cfg);
   return generate_gainmap_finalize_md(cfg, hdr->ct, use_base_cg, mm, md);
 }
+uhdr_error_info_t uhdr_hip_encode_api0_fused_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                 uhdr_raw_image_t* sdr_rgba, uhdr_raw_image_t* base_ycc, uhdr_gainmap_metadata_t* md,
+                                                 uhdr_raw_image_t* gm) {
+  return encode_api0_fused_impl(c, hdr, cfg, sdr_rgba, base_ycc, md, gm, false);
+}
+uhdr_error_info_t uhdr_hip_encode_api0_fused_scaled_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                        uhdr_raw_image_t* sdr_rgba, uhdr_raw_image_t* base_ycc, uhdr_gainmap_metadata_t* md,
+                                                        uhdr_raw_image_t* gm) {
+  return encode_api0_fused_impl(c, hdr, cfg, sdr_rgba, base_ycc, md, gm, true);
+}
 
 // -------------------------------------------------------------------------------------------------
 // API-0 front end fused for P010 intents: toneMap (P010 -> YCbCr 4:2:0) + generateGainMap in one pass
@@ -200,13 +234,16 @@ uhdr_error_info_t uhdr_hip_encode_api0_fused_dev(uhdr_hip_ctx_t* c, const uhdr_r
 // jpegr.cpp:179-244 compresses the tone mapper's 4:2:0 planes as they are, so the base image leaves here in the form the base JPEG's
 // FDCT takes.  Declines (UHDR_CODEC_UNSUPPORTED_FEATURE, before anything is launched) what the quad kernel cannot read with its vector
 // accesses; the caller then runs uhdr_hip_tone_map_dev + uhdr_hip_generate_gainmap_dev.
-uhdr_error_info_t uhdr_hip_encode_api0_p010_fused_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
-                                                      uhdr_raw_image_t* base_ycc420, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
+// scaled == false: uhdr_hip_encode_api0_p010_fused_dev; true: uhdr_hip_encode_api0_p010_fused_scaled_dev, which also takes scale factors 2 and 4
+static uhdr_error_info_t encode_api0_p010_fused_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                     uhdr_raw_image_t* base_ycc420, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm, bool scaled) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!hdr || !cfg || !base_ycc420 || !md || !gm || !gm->planes[0]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
   if (hdr->fmt != UHDR_IMG_FMT_24bppYCbCrP010)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused P010 API-0 front end takes UHDR_IMG_FMT_24bppYCbCrP010. Received %d", hdr->fmt);
-  if (cfg->map_dimension_scale_factor != 1)
+  if (scaled) UHDR_TRY(check_scaled_request(hdr, cfg, false));
+  const bool sub = scaled && cfg->map_dimension_scale_factor != 1;  // the scaled kernel
+  if (!scaled && cfg->map_dimension_scale_factor != 1)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused P010 API-0 front end needs a full-resolution gain map (scale factor 1), received %d; "
                       "use tone_map + generate_gainmap", cfg->map_dimension_scale_factor);
   if (hdr->cg < UHDR_CG_BT_709 || hdr->cg > UHDR_CG_BT_2100)  // (what uhdr_hip_tone_map_dev accepts for P010)
@@ -257,7 +294,8 @@ uhdr_error_info_t uhdr_hip_encode_api0_p010_fused_dev(uhdr_hip_ctx_t* c, const u
     p.gen.out = (uint8_t*)gm->planes[0];
     p.gen.out_stride = gm->stride[0];
     ProfScope ps(c, "encode_api0_fused");
-    HIP_TRY(launch_encode_api0_p010_fused(p, false, nullptr, c->stream));
+    if (sub) HIP_TRY(launch_encode_api0_p010_fused_scaled(p, c->stream));
+    else HIP_TRY(launch_encode_api0_p010_fused(p, false, nullptr, c->stream));
     return ok_status();
   }
   const size_t nfl = (size_t)p.gen.map_w * p.gen.map_h * (p.gen.multichannel ? 3 : 1);
@@ -276,6 +314,14 @@ uhdr_error_info_t uhdr_hip_encode_api0_p010_fused_dev(uhdr_hip_ctx_t* c, const u
   memcpy(mm, c->h_mm, sizeof mm);
   note_table_stats(c, cfg);
   return generate_gainmap_finalize_md(cfg, hdr->ct, use_base_cg, mm, md);
+}
+uhdr_error_info_t uhdr_hip_encode_api0_p010_fused_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                      uhdr_raw_image_t* base_ycc420, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
+  return encode_api0_p010_fused_impl(c, hdr, cfg, base_ycc420, md, gm, false);
+}
+uhdr_error_info_t uhdr_hip_encode_api0_p010_fused_scaled_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                             uhdr_raw_image_t* base_ycc420, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
+  return encode_api0_p010_fused_impl(c, hdr, cfg, base_ycc420, md, gm, true);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -705,19 +751,37 @@ static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
 // API-0 calls): the intent goes up once, uhdr_hip_encode_api0_fused_dev leaves the YCbCr 4:4:4 base image and the one-pass gain map in HBM,
 // FDCT + quantize (rgb -> ycc inside for a three-channel map), both scans Huffman-coded concurrently, and only the bytes come down.
 // The reference overrides the preset to UHDR_USAGE_REALTIME on this path (jpegr.cpp:207) and passes use_luminance = false: so does this.
-uhdr_error_info_t uhdr_hip_encode_api0_scans(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
-                                             const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
-                                             uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
-                                             size_t map_capacity, size_t* map_bytes) {
+// What uhdr_hip_encode_api0_scans_scaled declines at scale factor 2 / 4 before the intent goes up: what the front end would decline
+// (check_scaled_request, a pitch its vector loads cannot read -- the staged copy keeps the host pitch) and a map that is not whole blocks.
+static uhdr_error_info_t check_scaled_scans(const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg) {
+  UHDR_TRY(check_scaled_request(hdr, cfg, true));
+  const unsigned s = (unsigned)cfg->map_dimension_scale_factor;
+  if (s == 1) return ok_status();
+  if ((hdr->w / s) % 8 || (hdr->h / s) % 8)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs map dimensions that are multiples of 8 (scale factor %u on %ux%u); use the operators",
+                      s, hdr->w, hdr->h);
+  const bool p010 = hdr->fmt == UHDR_IMG_FMT_24bppYCbCrP010;
+  if (p010 ? (hdr->stride[0] % 2 || hdr->stride[1] % 2) : (hdr->stride[0] % 4 != 0))
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain at scale factor %u reads the intent with vector loads: strides that are multiples of %d; "
+                      "use the operators", s, p010 ? 2 : 4);
+  return ok_status();
+}
+
+// scaled == false: uhdr_hip_encode_api0_scans; true: the RGB half of uhdr_hip_encode_api0_scans_scaled, which also takes scale factors 2 and 4
+static uhdr_error_info_t encode_api0_scans_rgb_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
+                                                    const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                    uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
+                                                    size_t map_capacity, size_t* map_bytes, bool scaled) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!hdr || !cfg_in || !qt_base || !qt_map || !md || !base_scan || !map_scan || !base_bytes || !map_bytes)
     return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
   if (hdr->fmt != UHDR_IMG_FMT_32bppRGBA1010102 && hdr->fmt != UHDR_IMG_FMT_64bppRGBAHalfFloat)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain takes UHDR_IMG_FMT_32bppRGBA1010102 or UHDR_IMG_FMT_64bppRGBAHalfFloat. Received %d", hdr->fmt);
-  if (cfg_in->map_dimension_scale_factor != 1)
+  if (!scaled && cfg_in->map_dimension_scale_factor != 1)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs a full-resolution gain map (scale factor 1), received %d", cfg_in->map_dimension_scale_factor);
   if (hdr->w == 0 || hdr->h == 0 || hdr->w % 8 || hdr->h % 8 || hdr->w > 65535 || hdr->h > 65535)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs dimensions that are multiples of 8 (received %ux%u); use the operators", hdr->w, hdr->h);
+  if (scaled) UHDR_TRY(check_scaled_scans(hdr, cfg_in));
   if (c->comm != nullptr || c->comm_custom) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes");
   UHDR_TRY(validate_image(hdr, "hdr intent"));
   for (int t = 0; t < 2; t++)
@@ -735,9 +799,10 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans(uhdr_hip_ctx_t* c, const uhdr_raw_i
   if (c->resident_on) UHDR_TRY(resident_write_back_all(c));
   UHDR_TRY(stage_in(c, 1, hdr, &dh, true));
   // device images: the base image's three 4:4:4 planes and the map (rows padded to 64 samples), then the coefficient arrays
-  const size_t pitch = ((size_t)w + 63) & ~(size_t)63, plane = pitch * h, map_pitch_px = pitch;
+  const unsigned scale = (unsigned)cfg.map_dimension_scale_factor, mw = w / scale, mh = h / scale;  // (1 unless scaled)
+  const size_t pitch = ((size_t)w + 63) & ~(size_t)63, plane = pitch * h, map_pitch_px = ((size_t)mw + 63) & ~(size_t)63;
   UHDR_TRY(ensure(c->enc[1], 3 * plane + 256));
-  UHDR_TRY(ensure(c->enc[2], map_pitch_px * (size_t)nch * h + 256));
+  UHDR_TRY(ensure(c->enc[2], map_pitch_px * (size_t)nch * mh + 256));
   const size_t nblk = (size_t)(w / 8) * (h / 8), cbytes = (nblk * 128 + 255) & ~(size_t)255;
   UHDR_TRY(ensure(c->enc[0], cbytes * (size_t)(3 + nch)));
   uhdr_raw_image_t ycc, gm;
@@ -749,7 +814,7 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans(uhdr_hip_ctx_t* c, const uhdr_raw_i
   }
   gm.planes[0] = c->enc[2].p;
   gm.stride[0] = (unsigned int)map_pitch_px;
-  UHDR_TRY(uhdr_hip_encode_api0_fused_dev(c, &dh, &cfg, nullptr, &ycc, md, &gm));
+  UHDR_TRY(encode_api0_fused_impl(c, &dh, &cfg, nullptr, &ycc, md, &gm, scaled));
   if (sdr_cg) *sdr_cg = ycc.cg;  // what toneMap gives its SDR rendition (jpegr.cpp:2024-2030) and convert_raw_input_to_ycbcr keeps
   if (gainmap_desc) {
     *gainmap_desc = gm;
@@ -760,14 +825,14 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans(uhdr_hip_ctx_t* c, const uhdr_raw_i
   for (int i = 0; i < 3; i++)
     UHDR_TRY(uhdr_hip_fdct_quant_dev(c, (const uint8_t*)ycc.planes[i], pitch, (int)(w / 8), (int)(h / 8), qt_base[i ? 1 : 0], coef[i]));
   if (nch == 3) UHDR_TRY(uhdr_hip_fdct_quant_rgb_dev(c, &gm, qt_map[0], qt_map[1], coef[3], coef[4], coef[5]));
-  else UHDR_TRY(uhdr_hip_fdct_quant_dev(c, (const uint8_t*)gm.planes[0], (size_t)gm.stride[0], (int)(w / 8), (int)(h / 8), qt_map[0], coef[3]));
+  else UHDR_TRY(uhdr_hip_fdct_quant_dev(c, (const uint8_t*)gm.planes[0], (size_t)gm.stride[0], (int)(mw / 8), (int)(mh / 8), qt_map[0], coef[3]));
   uhdr_hip_jpeg_scan_t sb, sm;
   memset(&sb, 0, sizeof sb);
   memset(&sm, 0, sizeof sm);
   sb.num_components = 3;
   sm.num_components = nch;
-  sb.w = sm.w = w;
-  sb.h = sm.h = h;
+  sb.w = w; sm.w = mw;
+  sb.h = h; sm.h = mh;
   for (int i = 0; i < 3; i++) {
     sb.coef[i] = coef[i];
     sb.blocks_w[i] = (int)(w / 8); sb.blocks_h[i] = (int)(h / 8);
@@ -775,7 +840,7 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans(uhdr_hip_ctx_t* c, const uhdr_raw_i
   }
   for (int i = 0; i < nch; i++) {
     sm.coef[i] = coef[3 + i];
-    sm.blocks_w[i] = (int)(w / 8); sm.blocks_h[i] = (int)(h / 8);
+    sm.blocks_w[i] = (int)(mw / 8); sm.blocks_h[i] = (int)(mh / 8);
     sm.h_samp[i] = sm.v_samp[i] = 1;
   }
   if (base_capacity > 0xFFFFFFF0u) base_capacity = 0xFFFFFFF0u;
@@ -793,25 +858,34 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans(uhdr_hip_ctx_t* c, const uhdr_raw_i
   HIP_TRY(hipStreamSynchronize(c->stream));
   return ok_status();
 }
+uhdr_error_info_t uhdr_hip_encode_api0_scans(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
+                                             const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                             uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
+                                             size_t map_capacity, size_t* map_bytes) {
+  return encode_api0_scans_rgb_impl(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes, false);
+}
 
 // uhdr_hip_encode_api0_scans for every intent a fused front end takes: RGBA1010102 / RGBA half float go to the entry point above unchanged;
 // a P010 intent (what camera and video frames arrive as; jpegr.cpp:179-244 compresses the tone mapper's 4:2:0 planes as they are) goes up once,
 // uhdr_hip_encode_api0_p010_fused_dev leaves the 4:2:0 base image and the one-pass map in HBM, the base image's blocks come from the API-1
 // chain's launch_base_blocks (no conversion matrix), the map's as above, both scans are Huffman-coded concurrently (the base scan is
 // 2x2 / 1x1 / 1x1) and only the bytes come down.  Preset, sdr_is_601 and use_luminance are overridden as above.
-uhdr_error_info_t uhdr_hip_encode_api0_scans_any(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
-                                                 const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
-                                                 uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
-                                                 size_t map_capacity, size_t* map_bytes) {
+// scaled == false: uhdr_hip_encode_api0_scans_any; true: uhdr_hip_encode_api0_scans_scaled, which also takes scale factors 2 and 4 for RGBA1010102 and
+// P010 intents -- the map is then a (w / S) x (h / S) image of whole blocks.
+static uhdr_error_info_t encode_api0_scans_any_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
+                                                    const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                    uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
+                                                    size_t map_capacity, size_t* map_bytes, bool scaled) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!hdr || !cfg_in || !qt_base || !qt_map || !md || !base_scan || !map_scan || !base_bytes || !map_bytes)
     return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
   if (hdr->fmt != UHDR_IMG_FMT_24bppYCbCrP010)
-    return uhdr_hip_encode_api0_scans(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes);
-  if (cfg_in->map_dimension_scale_factor != 1)
+    return encode_api0_scans_rgb_impl(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes, scaled);
+  if (!scaled && cfg_in->map_dimension_scale_factor != 1)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs a full-resolution gain map (scale factor 1), received %d", cfg_in->map_dimension_scale_factor);
   if (hdr->w == 0 || hdr->h == 0 || hdr->w % 16 || hdr->h % 16 || hdr->w > 65535 || hdr->h > 65535)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs P010 dimensions that are multiples of 16 (received %ux%u); use the operators", hdr->w, hdr->h);
+  if (scaled) UHDR_TRY(check_scaled_scans(hdr, cfg_in));
   if (c->comm != nullptr || c->comm_custom) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes");
   UHDR_TRY(validate_image(hdr, "hdr intent"));
   for (int t = 0; t < 2; t++)
@@ -829,10 +903,11 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans_any(uhdr_hip_ctx_t* c, const uhdr_r
   if (c->resident_on) UHDR_TRY(resident_write_back_all(c));
   UHDR_TRY(stage_in(c, 1, hdr, &dh, true));
   // device images: the base image's 4:2:0 planes and the map (rows padded to 64 samples), then the coefficient arrays
-  const size_t pitch = ((size_t)w + 63) & ~(size_t)63, cpitch = ((size_t)(w / 2) + 63) & ~(size_t)63;
+  const unsigned scale = (unsigned)cfg.map_dimension_scale_factor, mw = w / scale, mh = h / scale;  // (1 unless scaled)
+  const size_t pitch = ((size_t)w + 63) & ~(size_t)63, cpitch = ((size_t)(w / 2) + 63) & ~(size_t)63, map_pitch = ((size_t)mw + 63) & ~(size_t)63;
   const size_t plane_y = pitch * h, plane_c = cpitch * (h / 2);
   UHDR_TRY(ensure(c->enc[1], plane_y + 2 * plane_c + 256));
-  UHDR_TRY(ensure(c->enc[2], pitch * (size_t)nch * h + 256));
+  UHDR_TRY(ensure(c->enc[2], map_pitch * (size_t)nch * mh + 256));
   const size_t nb[3] = {(size_t)(w / 8) * (h / 8), (size_t)(w / 16) * (h / 16), (size_t)(w / 16) * (h / 16)};
   size_t off = 0, o_coef[6];
   for (int i = 0; i < 3 + nch; i++) { o_coef[i] = off; off += ((i < 3 ? nb[i] : nb[0]) * 128 + 255) & ~(size_t)255; }
@@ -846,8 +921,8 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans_any(uhdr_hip_ctx_t* c, const uhdr_r
   ycc.stride[0] = (unsigned int)pitch;
   ycc.stride[1] = ycc.stride[2] = (unsigned int)cpitch;
   gm.planes[0] = c->enc[2].p;
-  gm.stride[0] = (unsigned int)pitch;
-  UHDR_TRY(uhdr_hip_encode_api0_p010_fused_dev(c, &dh, &cfg, &ycc, md, &gm));
+  gm.stride[0] = (unsigned int)map_pitch;
+  UHDR_TRY(encode_api0_p010_fused_impl(c, &dh, &cfg, &ycc, md, &gm, scaled));
   if (sdr_cg) *sdr_cg = ycc.cg;  // what toneMap gives its SDR rendition (jpegr.cpp:2024-2030)
   if (gainmap_desc) {
     *gainmap_desc = gm;
@@ -860,14 +935,14 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans_any(uhdr_hip_ctx_t* c, const uhdr_r
     HIP_TRY(launch_base_blocks(view_of(&ycc), nullptr, qt_base[0], qt_base[1], coef, c->stream));
   }
   if (nch == 3) UHDR_TRY(uhdr_hip_fdct_quant_rgb_dev(c, &gm, qt_map[0], qt_map[1], coef[3], coef[4], coef[5]));
-  else UHDR_TRY(uhdr_hip_fdct_quant_dev(c, (const uint8_t*)gm.planes[0], (size_t)gm.stride[0], (int)(w / 8), (int)(h / 8), qt_map[0], coef[3]));
+  else UHDR_TRY(uhdr_hip_fdct_quant_dev(c, (const uint8_t*)gm.planes[0], (size_t)gm.stride[0], (int)(mw / 8), (int)(mh / 8), qt_map[0], coef[3]));
   uhdr_hip_jpeg_scan_t sb, sm;
   memset(&sb, 0, sizeof sb);
   memset(&sm, 0, sizeof sm);
   sb.num_components = 3;
   sm.num_components = nch;
-  sb.w = sm.w = w;
-  sb.h = sm.h = h;
+  sb.w = w; sm.w = mw;
+  sb.h = h; sm.h = mh;
   for (int i = 0; i < 3; i++) {
     sb.coef[i] = coef[i];
     sb.blocks_w[i] = (int)(i ? w / 16 : w / 8);
@@ -876,7 +951,7 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans_any(uhdr_hip_ctx_t* c, const uhdr_r
   }
   for (int i = 0; i < nch; i++) {
     sm.coef[i] = coef[3 + i];
-    sm.blocks_w[i] = (int)(w / 8); sm.blocks_h[i] = (int)(h / 8);
+    sm.blocks_w[i] = (int)(mw / 8); sm.blocks_h[i] = (int)(mh / 8);
     sm.h_samp[i] = sm.v_samp[i] = 1;
   }
   if (base_capacity > 0xFFFFFFF0u) base_capacity = 0xFFFFFFF0u;
@@ -892,6 +967,18 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans_any(uhdr_hip_ctx_t* c, const uhdr_r
   HIP_TRY(hipMemcpyAsync(map_scan, c->jpg[4].p, nms, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return ok_status();
+}
+uhdr_error_info_t uhdr_hip_encode_api0_scans_any(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
+                                                 const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                 uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
+                                                 size_t map_capacity, size_t* map_bytes) {
+  return encode_api0_scans_any_impl(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes, false);
+}
+uhdr_error_info_t uhdr_hip_encode_api0_scans_scaled(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
+                                                    const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                    uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
+                                                    size_t map_capacity, size_t* map_bytes) {
+  return encode_api0_scans_any_impl(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes, true);
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -227,15 +227,21 @@ void launch_fused4(const FusedParams& p, int grid, float* partials, hipStream_t 
   else if (p.gen.hdr_gamut_on) launch_fused4_m<TWO_PASS, 2>(p, grid, partials, s);
   else launch_fused4_m<TWO_PASS, 0>(p, grid, partials, s);
 }
-bool fused4_ok(const FusedParams& p, bool two_pass) {
-  if (p.tm.hdr.fmt != UHDR_IMG_FMT_32bppRGBA1010102 || !p.tm.lin10 || !p.tm.srgb8.tab || !p.gen.srgb_of_byte) return false;
-  if (!two_pass && !p.gen.gain8.tab) return false;
+// do the 16-byte loads of the intent, the 4-byte stores to the base planes and the 16-byte stores of the rendition stay aligned?
+bool fused4_io_aligned(const FusedParams& p) {
   const uint32_t w = p.tm.hdr.w;
   auto al = [](const void* q, uintptr_t a) { return ((uintptr_t)q & (a - 1)) == 0; };
   if (w % 4 || p.tm.hdr.stride[0] % 4 || !al(p.tm.hdr.p[0], 16)) return false;
   for (int i = 0; i < 3; i++)
     if (p.ycc.stride[i] % 4 || !al(p.ycc.p[i], 4)) return false;
   if (p.tm.sdr.p[0] && (p.tm.sdr.stride[0] % 4 || !al(p.tm.sdr.p[0], 16))) return false;
+  return true;
+}
+bool fused4_ok(const FusedParams& p, bool two_pass) {
+  if (p.tm.hdr.fmt != UHDR_IMG_FMT_32bppRGBA1010102 || !p.tm.lin10 || !p.tm.srgb8.tab || !p.gen.srgb_of_byte) return false;
+  if (!two_pass && !p.gen.gain8.tab) return false;
+  auto al = [](const void* q, uintptr_t a) { return ((uintptr_t)q & (a - 1)) == 0; };
+  if (!fused4_io_aligned(p)) return false;
   const uint32_t nch = p.gen.multichannel ? 3 : 1;
   if (two_pass) return al(p.gen.gain_log2, 16);
   return ((size_t)p.gen.out_stride * nch) % 4 == 0 && al(p.gen.out, 4);
@@ -365,6 +371,254 @@ void launch_p010(const FusedParams& p, int grid, float* partials, hipStream_t s)
   else launch_p010_m<TWO_PASS, 0>(p, grid, partials, s);
 }
 
+// ---- gain maps at scale factor 2 and 4 (one pass) -------------------------------------------------------------------------------------
+// A sub-sampled map (kMapDimensionScaleFactorAndroidDefault = 4, ultrahdrcommon.h:425) used to cost three full-image launches: the tone
+// map, generate_kernel -- one thread per map pixel, fetching its S x S box of BOTH images one pixel at a time, neighbouring lanes S pixels
+// apart -- and, for RGB intents, convert_raw_input_to_ycbcr: about 23 bytes per pixel for RGBA1010102 at S = 4.  The two kernels below are
+// the kernels above with the gain side replaced by generate_kernel's: samplePixels (gainmapmath.cpp:494-503) averages the GAMMA-ENCODED
+// samples of the box and the mean is linearised, so a lane sums what fetch_pixel would return for the bytes it has just written (u8[byte],
+// or y / 255 and (u - 128) / 255) and for the HDR codes it has just read (u10[code], or fetch_quad_p010's values), from 0.0f, dy outer and dx
+// inner, divides by S * S and goes on exactly as generate_kernel does from its two sample_box results.  One pass only (API-0 overrides the
+// preset to UHDR_USAGE_REALTIME, jpegr.cpp:207).  4 + 3 + 3/16 bytes per pixel (RGBA1010102, S = 4, one channel); the SDR bytes never come
+// back from HBM.  GAMUT as in encode_api0_p010_fused_kernel (the SDR rendition is Display-P3, so the tone mapper converts exactly when the
+// gain side does).  A call without a gain step table (gamma != 1) evaluates encode_gain per map pixel, as generate_kernel does.
+// LDS, RGBA1010102: code -> linear 4 KB + HDR inverse OETF 16 KB + sRGB inverse OETF 4 KB + sample normalisation 5 KB + the two step
+// tables 32 KB = 61 KB; P010: FusedQuadLds 43.2 KB + the gain step table 16 KB = 59 KB.  A cell keeps its box sums and S rows of loads alive
+// beside the tone curve: 67-116 VGPRs (RGBA1010102 at S = 4 with two rows in flight: 116; all four: 143), so the one-pass P010 kernel's two
+// 768-thread workgroups (six waves per SIMD, 80 VGPRs) would leave one resident.  Both kernels: two 512-thread workgroups per CU (16 waves,
+// four per SIMD -- __launch_bounds__ holds the allocation to 128 --, 118-122 of 160 KB).  No scratch.
+constexpr int kScaledBlock = 512;
+struct FusedScaledLds {
+  float lin10[1024];     // tone map: 10-bit code -> linear value (unpack + inverse OETF [+ OOTF])
+  float hdr[kInvOetfN];  // gain side: the HDR inverse OETF of the box mean (none for a linear intent)
+  float srgb[kSrgbN];    // gain side: the sRGB inverse OETF of the box mean
+  UnormTables unorm;
+  uint2 srgb8[kStepTabMax];
+};
+
+// RGBA1010102: a lane owns a cell of 4 consecutive pixels x S rows (one map pixel at S = 4, two at S = 2); a wave walks tiles of 64 cells
+// = 256 pixels of one strip of S image rows.
+template <int S, int GAMUT, int MC>
+__global__ __launch_bounds__(kScaledBlock, 4) void encode_api0_fused4_scaled_kernel(const FusedParams p) {
+  __shared__ FusedScaledLds L;
+  __shared__ alignas(16) uint2 s_gain8[kStepTabMax];
+  const uint32_t tid = threadIdx.x;
+  copy_to_lds(L.lin10, p.tm.lin10, 1024u, tid, kScaledBlock);
+  if (p.gen.hdr_inv_lut) copy_to_lds(L.hdr, p.gen.hdr_inv_lut, (uint32_t)p.gen.hdr_inv_n, tid, kScaledBlock);
+  copy_to_lds(L.srgb, p.gen.srgb_lut, (uint32_t)kSrgbN, tid, kScaledBlock);
+  fill_unorm_tables(L.unorm, tid, kScaledBlock);
+  stage_step_tab(L.srgb8, p.tm.srgb8, tid, kScaledBlock);
+  stage_step_tab(s_gain8, p.gen.gain8, tid, kScaledBlock);
+  __syncthreads();
+  const uint32_t w4 = p.tm.hdr.w / 4, strips = p.tm.hdr.h / S;
+  const uint32_t tiles_x = (w4 + 63) / 64, tiles = tiles_x * strips;
+  const float inv_tx = 1.0f / (float)tiles_x;
+  const uint32_t lane = tid & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (kScaledBlock / 64) + (tid >> 6));
+  const uint32_t nwaves = gridDim.x * (kScaledBlock / 64);
+  const bool hdr_lut = p.gen.hdr_inv_lut != nullptr, hdr_lut_4096 = p.gen.hdr_inv_n == kInvOetfN;
+  constexpr int NBOX = 4 / S;  // map pixels per cell
+  for (uint32_t t = wave; t < tiles; t += nwaves) {
+    uint32_t sy = (uint32_t)((float)t * inv_tx);  // t / tiles_x for t < 2^24: the float estimate is off by at most one
+    if (sy * tiles_x > t) sy--;
+    if ((sy + 1) * tiles_x <= t) sy++;
+    const uint32_t x4 = (t - sy * tiles_x) * 64 + lane;
+    if (x4 >= w4) continue;
+    const uint32_t x = x4 * 4;
+    Color3 ss[NBOX], hs[NBOX];  // samplePixels' sums of the two images
+#pragma unroll
+    for (int b = 0; b < NBOX; b++) ss[b] = hs[b] = Color3{0.0f, 0.0f, 0.0f};
+#pragma unroll 2  // two rows' loads in flight per lane; four rows unrolled need 143 VGPRs
+    for (int dy = 0; dy < S; dy++) {
+      const uint32_t y = sy * S + dy;
+      const u4v in = *(const u4v*)((const uint32_t*)p.tm.hdr.p[0] + (size_t)y * p.tm.hdr.stride[0] + x);
+      const uint32_t px[4] = {in.x, in.y, in.z, in.w};
+      uint32_t rgba[4], oy = 0, ocb = 0, ocr = 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        // ---- toneMap (jpegr.cpp:2147-2203): unpack + inverse OETF (+ OOTF) of a 10-bit code is one table entry -----------------
+        const uint32_t v = px[k];
+        const uint32_t c0 = v & 0x3ffu, c1 = (v >> 10) & 0x3ffu, c2 = (v >> 20) & 0x3ffu;
+        const Color3 l = Color3{L.lin10[c0], L.lin10[c1], L.lin10[c2]};
+        const Color3 o = tone_curve_linear<(GAMUT != 0) ? 1 : 0>(l, p.tm);
+        const uint32_t r8 = step_code(o.r, L.srgb8, p.tm.srgb8), g8 = step_code(o.g, L.srgb8, p.tm.srgb8), b8 = step_code(o.b, L.srgb8, p.tm.srgb8);
+        rgba[k] = r8 | (g8 << 8) | (b8 << 16) | (255u << 24);
+        // ---- convert_raw_input_to_ycbcr(sdr, 4:4:4) (gainmapmath.cpp:1446-1472) ------------------------------------------------
+        const Color3 e = {L.unorm.u8[r8], L.unorm.u8[g8], L.unorm.u8[b8]};  // getRgba8888Pixel: byte / 255.0f
+        const Color3 q = rgb_to_yuv(e, p.base_k);
+        oy |= (uint32_t)__builtin_amdgcn_fmed3f(q.r * 255.0f + 0.5f, 0.0f, 255.0f) << (8 * k);
+        ocb |= (uint32_t)__builtin_amdgcn_fmed3f(q.g * 255.0f + 0.5f + 128.0f, 0.0f, 255.0f) << (8 * k);
+        ocr |= (uint32_t)__builtin_amdgcn_fmed3f(q.b * 255.0f + 0.5f + 128.0f, 0.0f, 255.0f) << (8 * k);
+        // ---- samplePixels (gainmapmath.cpp:494-503) of both images: what fetch_pixel returns for these bytes and these codes -----
+        Color3& sb = ss[k / S];  // (a constant index once unrolled)
+        Color3& hb = hs[k / S];
+        sb.r += e.r; sb.g += e.g; sb.b += e.b;
+        hb.r += L.unorm.u10[c0]; hb.g += L.unorm.u10[c1]; hb.b += L.unorm.u10[c2];
+      }
+      if (p.tm.sdr.p[0]) *(u4v*)((uint32_t*)p.tm.sdr.p[0] + (size_t)y * p.tm.sdr.stride[0] + x) = (u4v){rgba[0], rgba[1], rgba[2], rgba[3]};
+      *(uint32_t*)((uint8_t*)p.ycc.p[0] + (size_t)y * p.ycc.stride[0] + x) = oy;
+      *(uint32_t*)((uint8_t*)p.ycc.p[1] + (size_t)y * p.ycc.stride[1] + x) = ocb;
+      *(uint32_t*)((uint8_t*)p.ycc.p[2] + (size_t)y * p.ycc.stride[2] + x) = ocr;
+    }
+    // ---- generateGainMap (jpegr.cpp:753-818) from the two box means, as generate_kernel ----------------------------------------------
+#pragma unroll
+    for (int b = 0; b < NBOX; b++) {
+      const float d = (float)(S * S);
+      const Color3 s = {ss[b].r / d, ss[b].g / d, ss[b].b / d}, h = {hs[b].r / d, hs[b].g / d, hs[b].b / d};
+      Color3 sl = linearise_hdr(s, L.srgb, true, false);  // the 1024-entry sRGB table; box means of RGB samples stay in [0, 1]
+      if (GAMUT == 1) {  // clipNegatives (jpegr.cpp:783-784) can only bite behind a matrix: table outputs are never negative
+        sl = mat3_apply(sl, p.gen.sdr_gamut);
+        sl.r = clip_neg(sl.r); sl.g = clip_neg(sl.g); sl.b = clip_neg(sl.b);
+      }
+      Color3 hl = linearise_hdr(h, L.hdr, hdr_lut, hdr_lut_4096);
+      if (GAMUT == 2) {
+        hl = mat3_apply(hl, p.gen.hdr_gamut);
+        hl.r = clip_neg(hl.r); hl.g = clip_neg(hl.g); hl.b = clip_neg(hl.b);
+      }
+      gain_of_pixel<false, MC>(sl, hl, p.gen, p.gen.math_tab, x4 * NBOX + b, sy, nullptr, nullptr, s_gain8);  // (no extrema in one pass)
+    }
+  }
+}
+
+// P010: a lane owns an S x S box (one quad at S = 2, 2 x 2 quads at S = 4); a wave walks tiles of 64 consecutive boxes of one box row.
+template <int S, int GAMUT, int MC, bool LUT>
+__global__ __launch_bounds__(kScaledBlock, 4) void encode_api0_p010_fused_scaled_kernel(const FusedParams p) {
+  __shared__ FusedQuadLds L;
+  __shared__ alignas(16) uint2 s_gain8[kStepTabMax];
+  const uint32_t tid = threadIdx.x;
+  stage_step_tab(s_gain8, p.gen.gain8, tid, kScaledBlock);
+  if (LUT) copy_to_lds(L.hdr, p.tm.hdr_inv_lut, (uint32_t)p.tm.hdr_inv_n, tid, kScaledBlock);
+  stage_pow_tab(L.powt, p.tm.math_tab, tid, kScaledBlock);
+  copy_to_lds(L.srgb, p.gen.srgb_lut, (uint32_t)kSrgbN, tid, kScaledBlock);
+  fill_unorm_tables(L.unorm, tid, kScaledBlock);
+  __syncthreads();
+  constexpr int Q = S / 2;  // quads per box side
+  const uint32_t bw = p.tm.hdr.w / S, bh = p.tm.hdr.h / S;
+  const uint32_t tiles_x = (bw + 63) / 64, tiles = tiles_x * bh;
+  const float inv_tx = 1.0f / (float)tiles_x;
+  const uint32_t lane = tid & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (kScaledBlock / 64) + (tid >> 6));
+  const uint32_t nwaves = gridDim.x * (kScaledBlock / 64);
+  const float lut_scale = (float)(p.tm.hdr_inv_n - 1);  // lut_index: x * (N - 1), round half up (encode_core.h: rpi)
+  const bool hdr_lut_4096 = p.gen.hdr_inv_n == kInvOetfN;
+  uint8_t* yp = (uint8_t*)p.tm.sdr.p[0];
+  uint8_t* up = (uint8_t*)p.tm.sdr.p[1];
+  uint8_t* vp = (uint8_t*)p.tm.sdr.p[2];
+  for (uint32_t t = wave; t < tiles; t += nwaves) {
+    uint32_t by = (uint32_t)((float)t * inv_tx);  // t / tiles_x for t < 2^24: the float estimate is off by at most one
+    if (by * tiles_x > t) by--;
+    if ((by + 1) * tiles_x <= t) by++;
+    const uint32_t bx = (t - by * tiles_x) * 64 + lane;
+    if (bx >= bw) continue;
+    Color3 ss = {0.0f, 0.0f, 0.0f}, hs = {0.0f, 0.0f, 0.0f};  // samplePixels' sums of the two images (y, u, v)
+#pragma unroll
+    for (int j = 0; j < Q; j++) {  // quad rows of the box
+      float sy_[Q][4], hy_[Q][4], scu[Q], scv[Q], hcu[Q], hcv[Q];
+#pragma unroll
+      for (int i = 0; i < Q; i++) {
+        const uint32_t qx = bx * Q + i, qy = by * Q + j;
+        const QuadYuv hq = fetch_quad_p010(p.tm.hdr, qx, qy, &L.unorm);
+        Color3 l[4];  // linear HDR rgb: the tone mapper's input
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const Color3 g = yuv_to_rgb(hq.px[k].r, hq.px[k].g, hq.px[k].b, p.tm.hdr_yuv);  // in [0, 1]
+          l[k] = g;
+          if (LUT) l[k] = Color3{L.hdr[rpi(g.r * lut_scale)], L.hdr[rpi(g.g * lut_scale)], L.hdr[rpi(g.b * lut_scale)]};
+        }
+        // ---- toneMap (jpegr.cpp:2147-2203), as tonemap_p010_kernel -----------------------------------------------------------------
+        float su = 0.0f, sv = 0.0f;
+        uint32_t yb[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {  // (row, column) order: the chroma sums accumulate like the reference's
+          const Color3 og = tone_curve<(GAMUT != 0) ? 1 : 0>(l[k], p.tm, L.powt);
+          Color3 yuv = rgb_to_yuv(og, p.tm.p3);
+          yuv.g += 0.5f;
+          yuv.b += 0.5f;
+          yb[k] = scale_to_8bit(yuv.r);
+          su += yuv.g;
+          sv += yuv.b;
+        }
+        su *= 0.25f;  // x / 4.0f == x * 0.25f exactly
+        sv *= 0.25f;
+        const uint32_t ub = scale_to_8bit(su), vb = scale_to_8bit(sv);
+        const size_t sy = p.tm.sdr.stride[0];
+        uint8_t* y0 = yp + (size_t)(qy * 2) * sy + qx * 2;  // (the host checked quad_layout_ok: 16-bit stores stay aligned)
+        *(uint16_t*)y0 = (uint16_t)(yb[0] | (yb[1] << 8));
+        *(uint16_t*)(y0 + sy) = (uint16_t)(yb[2] | (yb[3] << 8));
+        up[(size_t)qy * p.tm.sdr.stride[1] + qx] = (uint8_t)ub;
+        vp[(size_t)qy * p.tm.sdr.stride[2] + qx] = (uint8_t)vb;
+        // what fetch_pixel returns for the bytes just written, and what fetch_quad_p010 returned
+        scu[i] = (float)((int)ub - 128) * (1 / 255.0f);
+        scv[i] = (float)((int)vb - 128) * (1 / 255.0f);
+        hcu[i] = hq.px[0].g;
+        hcv[i] = hq.px[0].b;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          sy_[i][k] = (float)(int)yb[k] * (1 / 255.0f);
+          hy_[i][k] = hq.px[k].r;
+        }
+      }
+      // ---- samplePixels (gainmapmath.cpp:494-503): box order is dy outer, dx inner -- row 0 of the left quad, row 0 of the right one, ... ----
+#pragma unroll
+      for (int r = 0; r < 2; r++)
+#pragma unroll
+        for (int i = 0; i < Q; i++)
+#pragma unroll
+          for (int cx = 0; cx < 2; cx++) {
+            ss.r += sy_[i][2 * r + cx]; ss.g += scu[i]; ss.b += scv[i];
+            hs.r += hy_[i][2 * r + cx]; hs.g += hcu[i]; hs.b += hcv[i];
+          }
+    }
+    // ---- generateGainMap (jpegr.cpp:753-818) from the two box means, as generate_kernel for a YCbCr pair ----------------------------------
+    const float d = (float)(S * S);
+    const Color3 s = yuv_to_rgb(ss.r / d, ss.g / d, ss.b / d, p.gen.sdr_yuv);
+    Color3 sl = linearise_hdr(s, L.srgb, true, false);
+    if (GAMUT == 1) {  // clipNegatives (jpegr.cpp:783-784) can only bite behind a matrix: table outputs are never negative
+      sl = mat3_apply(sl, p.gen.sdr_gamut);
+      sl.r = clip_neg(sl.r); sl.g = clip_neg(sl.g); sl.b = clip_neg(sl.b);
+    }
+    const Color3 h = yuv_to_rgb(hs.r / d, hs.g / d, hs.b / d, p.gen.hdr_yuv);
+    Color3 hl = linearise_hdr(h, L.hdr, LUT, hdr_lut_4096);
+    if (GAMUT == 2) {
+      hl = mat3_apply(hl, p.gen.hdr_gamut);
+      hl.r = clip_neg(hl.r); hl.g = clip_neg(hl.g); hl.b = clip_neg(hl.b);
+    }
+    gain_of_pixel<false, MC>(sl, hl, p.gen, p.gen.math_tab, bx, by, nullptr, nullptr, s_gain8);  // (no extrema in one pass)
+  }
+}
+
+template <int S, int GAMUT>
+void launch_fused4_scaled_m(const FusedParams& p, int grid, hipStream_t s) {
+  if (p.gen.multichannel) hipLaunchKernelGGL((encode_api0_fused4_scaled_kernel<S, GAMUT, 1>), dim3(grid), dim3(kScaledBlock), 0, s, p);
+  else hipLaunchKernelGGL((encode_api0_fused4_scaled_kernel<S, GAMUT, 0>), dim3(grid), dim3(kScaledBlock), 0, s, p);
+}
+template <int S>
+void launch_fused4_scaled(const FusedParams& p, int grid, hipStream_t s) {
+  if (p.gen.sdr_gamut_on) launch_fused4_scaled_m<S, 1>(p, grid, s);
+  else if (p.gen.hdr_gamut_on) launch_fused4_scaled_m<S, 2>(p, grid, s);
+  else launch_fused4_scaled_m<S, 0>(p, grid, s);
+}
+template <int S, int GAMUT, int MC>
+void launch_p010_scaled_l(const FusedParams& p, int grid, hipStream_t s) {
+  if (p.tm.hdr_inv_lut) hipLaunchKernelGGL((encode_api0_p010_fused_scaled_kernel<S, GAMUT, MC, true>), dim3(grid), dim3(kScaledBlock), 0, s, p);
+  else hipLaunchKernelGGL((encode_api0_p010_fused_scaled_kernel<S, GAMUT, MC, false>), dim3(grid), dim3(kScaledBlock), 0, s, p);
+}
+template <int S, int GAMUT>
+void launch_p010_scaled_m(const FusedParams& p, int grid, hipStream_t s) {
+  if (p.gen.multichannel) launch_p010_scaled_l<S, GAMUT, 1>(p, grid, s);
+  else launch_p010_scaled_l<S, GAMUT, 0>(p, grid, s);
+}
+template <int S>
+void launch_p010_scaled(const FusedParams& p, int grid, hipStream_t s) {
+  if (p.gen.sdr_gamut_on) launch_p010_scaled_m<S, 1>(p, grid, s);
+  else if (p.gen.hdr_gamut_on) launch_p010_scaled_m<S, 2>(p, grid, s);
+  else launch_p010_scaled_m<S, 0>(p, grid, s);
+}
+// the three gamut modes: the SDR rendition is Display-P3, so the tone mapper converts exactly when the gain side does
+bool scaled_gamut_ok(const FusedParams& p) {
+  return (p.tm.gamut_on != 0) == (p.gen.sdr_gamut_on || p.gen.hdr_gamut_on) && !(p.gen.sdr_gamut_on && p.gen.hdr_gamut_on);
+}
+
 }  // namespace
 
 int fused_grid(uint32_t tiles, int per_cu) {
@@ -426,6 +680,42 @@ hipError_t launch_encode_api0_p010_fused(const FusedParams& p, bool two_pass, in
   float* partials = two_pass ? p.gen.minmax + 6 : nullptr;
   if (two_pass) launch_p010<true>(p, grid, partials, s);
   else launch_p010<false>(p, grid, partials, s);
+  return hipGetLastError();
+}
+
+// ---- scale factor 2 / 4, one pass ---------------------------------------------------------------------------------------------------
+// what the scaled kernels read and write with vector accesses (the map is stored byte by byte: any stride and base)
+bool encode_api0_fused_scaled_layout_ok(const FusedParams& p) { return p.tm.hdr.fmt == UHDR_IMG_FMT_32bppRGBA1010102 && fused4_io_aligned(p); }
+
+static int scaled_grid(uint32_t wave_tiles) {
+  const uint32_t wg_waves = (uint32_t)kScaledBlock / 64;
+  return fused_grid((wave_tiles + wg_waves - 1) / wg_waves, 2);  // 59-61 KB of LDS tables per 512-thread workgroup: 16 waves per CU
+}
+
+// RGBA1010102 intent -> p.ycc (4:4:4 planes), the optional p.tm.sdr rendition and the one-pass map of (w / S) x (h / S) pixels, S = p.gen.scale
+// (2 or 4).  The caller has checked encode_api0_fused_scaled_layout_ok, w % 4 == 0 and h % S == 0.
+hipError_t launch_encode_api0_fused_scaled(const FusedParams& p, hipStream_t s) {
+  const uint32_t S = p.gen.scale, w = p.tm.hdr.w, h = p.tm.hdr.h;
+  if ((S != 2 && S != 4) || !encode_api0_fused_scaled_layout_ok(p) || w == 0 || h == 0 || h % S || p.gen.map_w != w / S || p.gen.map_h != h / S ||
+      !p.tm.lin10 || !p.tm.srgb8.tab || !p.gen.srgb_lut || !p.gen.out || p.gen.out_stride < p.gen.map_w || !scaled_gamut_ok(p))
+    return hipErrorInvalidValue;
+  const int grid = scaled_grid(((w / 4 + 63) / 64) * (h / S));
+  if (S == 2) launch_fused4_scaled<2>(p, grid, s);
+  else launch_fused4_scaled<4>(p, grid, s);
+  return hipGetLastError();
+}
+
+// P010 intent -> p.tm.sdr (YCbCr 4:2:0 planes) + the one-pass map, S = p.gen.scale (2 or 4).  The caller has checked quad_layout_ok for
+// p.tm.hdr and the base planes, w % 4 == 0 and h % S == 0.
+hipError_t launch_encode_api0_p010_fused_scaled(const FusedParams& p, hipStream_t s) {
+  const uint32_t S = p.gen.scale, w = p.tm.hdr.w, h = p.tm.hdr.h;
+  if ((S != 2 && S != 4) || p.tm.hdr.fmt != UHDR_IMG_FMT_24bppYCbCrP010 || p.tm.sdr.fmt != UHDR_IMG_FMT_12bppYCbCr420 || !quad_layout_ok(p.tm.hdr) ||
+      p.tm.sdr.w != w || p.tm.sdr.h != h || p.tm.sdr.stride[0] % 2 || ((uintptr_t)p.tm.sdr.p[0] % 2) || w == 0 || h == 0 || w % S || h % S ||
+      p.gen.map_w != w / S || p.gen.map_h != h / S || !p.gen.srgb_lut || !p.tm.math_tab || !p.gen.out || p.gen.out_stride < p.gen.map_w || !scaled_gamut_ok(p))
+    return hipErrorInvalidValue;
+  const int grid = scaled_grid(((w / S + 63) / 64) * (h / S));
+  if (S == 2) launch_p010_scaled<2>(p, grid, s);
+  else launch_p010_scaled<4>(p, grid, s);
   return hipGetLastError();
 }
 

@@ -270,6 +270,10 @@ int gen_partials_count(const GenParams& p);  // workgroups (= partials) launch_g
 hipError_t launch_encode_api0_fused(const FusedParams& p, bool two_pass, int* grid_out, hipStream_t s);
 bool encode_api0_p010_layout_ok(const ImageView& hdr, const ImageView& base420);  // quad_layout_ok (pixel_io.h) of both images
 hipError_t launch_encode_api0_p010_fused(const FusedParams& p, bool two_pass, int* grid_out, hipStream_t s);
+// gain maps at scale factor 2 / 4 (p.gen.scale), one pass
+bool encode_api0_fused_scaled_layout_ok(const FusedParams& p);  // RGBA1010102 and the alignments of the vector accesses
+hipError_t launch_encode_api0_fused_scaled(const FusedParams& p, hipStream_t s);
+hipError_t launch_encode_api0_p010_fused_scaled(const FusedParams& p, hipStream_t s);
 hipError_t launch_tone_map(const ToneMapParams& p, hipStream_t s);
 hipError_t launch_transform_yuv(const YuvXformParams& p, hipStream_t s);
 hipError_t launch_rgb_to_ycbcr(const RgbToYcbcrParams& p, hipStream_t s);

@@ -217,7 +217,53 @@ class UltraHdr:
         gm.sync_meta_from_raw()
         return base, md, gm
 
-    def encodeApi0ScansAny(self, hdr_intent: Image, qt_base, qt_map, base_capacity: int, map_capacity: int, any_format=True):
+    def _map_image(self, w, h, dev):
+        mw, mh = self.gainmap_dims(w, h)
+        fmt = A.UHDR_IMG_FMT_24bppRGB888 if self.mUseMultiChannelGainMap else A.UHDR_IMG_FMT_8bppYCbCr400
+        return Image(fmt, mw, mh, align=64, device=dev)
+
+    def encodeApi0FusedScaled(self, hdr_intent: Image, want_sdr_rgba=True, use_luminance=False, sdr: Image = None, ycc: Image = None, gm: Image = None):
+        """encodeApi0Fused for a gain map at scale factor 1, 2 or 4 (uhdr_hip_encode_api0_fused_scaled_dev; 2 and 4: RGBA1010102, one
+        pass).  sdr / ycc / gm: the device images to fill (fresh 64-aligned ones when None; the map is (w / S) x (h / S)).
+        Returns (sdr_rgba or None, base_ycc444, metadata, gainmap), bit-identical to the three separate calls at that scale factor."""
+        assert _is_dev(hdr_intent)
+        w, h, dev = hdr_intent.w, hdr_intent.h, hdr_intent.device
+        if sdr is None and want_sdr_rgba:
+            sdr = Image(A.UHDR_IMG_FMT_32bppRGBA8888, w, h, align=64, device=dev)
+        if ycc is None:
+            ycc = Image(A.UHDR_IMG_FMT_24bppYCbCr444, w, h, align=64, device=dev)
+        if gm is None:
+            gm = self._map_image(w, h, dev)
+        md = A.GainmapMetadata()
+        cfg = self.encode_cfg(False, use_luminance)
+        self._call(True, self.lib.uhdr_hip_encode_api0_fused_scaled_dev, self.ctx.handle, C.byref(hdr_intent.raw), C.byref(cfg),
+                   C.byref(sdr.raw) if sdr is not None else None, C.byref(ycc.raw), C.byref(md), C.byref(gm.raw))
+        gm.sync_meta_from_raw()
+        return sdr, ycc, md, gm
+
+    def encodeApi0FusedP010Scaled(self, hdr_intent: Image, base: Image = None, gm: Image = None, use_luminance=False):
+        """encodeApi0FusedP010 for a gain map at scale factor 1, 2 or 4 (uhdr_hip_encode_api0_p010_fused_scaled_dev; 2 and 4: one pass).
+        Returns (base_ycc420, metadata, gainmap), bit-identical to the two separate calls at that scale factor."""
+        assert _is_dev(hdr_intent)
+        w, h, dev = hdr_intent.w, hdr_intent.h, hdr_intent.device
+        if base is None:
+            base = Image(A.UHDR_IMG_FMT_12bppYCbCr420, w, h, align=64, device=dev)
+        if gm is None:
+            gm = self._map_image(w, h, dev)
+        md = A.GainmapMetadata()
+        cfg = self.encode_cfg(False, use_luminance)
+        self._call(True, self.lib.uhdr_hip_encode_api0_p010_fused_scaled_dev, self.ctx.handle, C.byref(hdr_intent.raw), C.byref(cfg),
+                   C.byref(base.raw), C.byref(md), C.byref(gm.raw))
+        base.sync_meta_from_raw()
+        gm.sync_meta_from_raw()
+        return base, md, gm
+
+    def encodeApi0ScansScaled(self, hdr_intent: Image, qt_base, qt_map, base_capacity: int, map_capacity: int):
+        """encodeApi0ScansAny for a gain map at scale factor 1, 2 or 4 (uhdr_hip_encode_api0_scans_scaled): same arguments, same returns;
+        the gainmap descriptor carries the map's (w / S) x (h / S)."""
+        return self.encodeApi0ScansAny(hdr_intent, qt_base, qt_map, base_capacity, map_capacity, _fn=self.lib.uhdr_hip_encode_api0_scans_scaled)
+
+    def encodeApi0ScansAny(self, hdr_intent: Image, qt_base, qt_map, base_capacity: int, map_capacity: int, any_format=True, _fn=None):
         """JpegR::encodeJPEGR API-0 (jpegr.cpp:179-244) without the container in ONE C call on a HOST intent: RGBA1010102, RGBA half
         float or P010 (uhdr_hip_encode_api0_scans_any; any_format=False: uhdr_hip_encode_api0_scans, which declines P010).
         Returns (base scan bytes, map scan bytes, metadata, gainmap descriptor, gamut of the SDR rendition); raises UhdrError --
@@ -228,7 +274,7 @@ class UltraHdr:
         cfg = self.encode_cfg(False, False)
         ob, om = np.empty(max(1, base_capacity), np.uint8), np.empty(max(1, map_capacity), np.uint8)
         nb, nm = C.c_size_t(0), C.c_size_t(0)
-        fn = self.lib.uhdr_hip_encode_api0_scans_any if any_format else self.lib.uhdr_hip_encode_api0_scans
+        fn = _fn or (self.lib.uhdr_hip_encode_api0_scans_any if any_format else self.lib.uhdr_hip_encode_api0_scans)
         try:
             self._call(False, fn, self.ctx.handle, C.byref(hdr_intent.raw), C.byref(cfg), C.c_void_p(qb.ctypes.data), C.c_void_p(qm.ctypes.data),
                        C.byref(md), C.byref(desc), C.byref(cg), C.c_void_p(ob.ctypes.data), int(base_capacity), C.byref(nb),
