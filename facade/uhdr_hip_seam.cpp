@@ -277,6 +277,12 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
   // when asked to: UHDR_HIP_SEAM_FUSED_RGBA_SDR; without it the per-stage seams run as before
   const bool rgba = sdr_intent->fmt == UHDR_IMG_FMT_32bppRGBA8888 && getenv("UHDR_HIP_SEAM_FUSED_RGBA_SDR") != nullptr;
   if ((!rgba && sdr_intent->fmt != UHDR_IMG_FMT_12bppYCbCr420) || *scale_factor < 1) return false;
+  // the one-pass (real-time) preset takes the fused route only when asked to: UHDR_HIP_SEAM_FUSED_REALTIME hands it to
+  // uhdr_hip_encode_api1_scans_onepass; without it the entry points below decline it and the per-stage seams run as before.  A
+  // sub-sampled map is declined here even then: at scale factor 4 the one-pass kernel has a wave per SIMD and loses to the staged
+  // launches (tools/api1_onepass_time.py, profiles/README.md)
+  const bool realtime = preset == UHDR_USAGE_REALTIME && getenv("UHDR_HIP_SEAM_FUSED_REALTIME") != nullptr;
+  if (realtime && *scale_factor != 1) return false;
   const unsigned w = sdr_intent->w, h = sdr_intent->h;
   const int s = *scale_factor;
   const unsigned grid = rgba ? 8 : 16;  // whole MCUs: 1x1 / 1x1 / 1x1 sampling for RGBA8888, 2x2 / 1x1 / 1x1 otherwise
@@ -340,8 +346,9 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
     out->gainmap_data.reset(new (std::nothrow) unsigned char[lead_m + cap_m + 2]);
     if (!out->base_data || !out->gainmap_data) return false;
     nb = nm = 0;
-    *st = (rgba ? uhdr_hip_encode_api1_scans_any : uhdr_hip_encode_api1_scans)(cur(), sdr_intent, hdr_intent, &cfg, UHDR_CG_DISPLAY_P3, qt_base, qt_map, &md, &gm_desc,
-                                                                               out->base_data.get() + lead_b, cap_b, &nb, out->gainmap_data.get() + lead_m, cap_m, &nm);
+    *st = (realtime ? uhdr_hip_encode_api1_scans_onepass : rgba ? uhdr_hip_encode_api1_scans_any : uhdr_hip_encode_api1_scans)(
+        cur(), sdr_intent, hdr_intent, &cfg, UHDR_CG_DISPLAY_P3, qt_base, qt_map, &md, &gm_desc, out->base_data.get() + lead_b, cap_b, &nb,
+        out->gainmap_data.get() + lead_m, cap_m, &nm);
     // a stream busier than the first guess: the encoder reports the size it needs -- once more with room for that (the device chain is ~1 ms at 4K;
     // the per-stage seams this used to fall to carry every intermediate over PCIe).  Any other MEM_ERROR (a device allocation) has no such sizes.
     if (st->error_code == UHDR_CODEC_MEM_ERROR && attempt == 0 && (nb > cap_b || nm > cap_m)) {

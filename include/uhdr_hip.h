@@ -860,6 +860,38 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans_any_dev(uhdr_hip_ctx_t* ctx, const 
                                                      uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
                                                      uint8_t* map_scan, size_t map_capacity, size_t* map_bytes);
 
+/* ---- The fused API-1 encode for the one-pass (real-time) preset as well (lib/src/jpegr.cpp:247-291 with generateGainMap's one-pass
+ * branch, lib/src/jpegr.cpp:719-835) -----------------------------------------------------------------------------------------------------
+ * Three entry points with the parameter lists of uhdr_hip_encode_api1_fused_any_dev, uhdr_hip_encode_api1_scans_any and
+ * uhdr_hip_encode_api1_scans_any_dev.  UHDR_USAGE_BEST_QUALITY: exactly what those run.  UHDR_USAGE_REALTIME -- the legacy JpegR()
+ * defaults (scale factor 4, one channel), every per-frame pipeline -- is TWO launches: the gain range is known before a pixel is read
+ * (min boost 1, max boost hdr white / 203), so one kernel takes both intents to the map's quantized coefficients (samplePixels over the
+ * S x S box at any scale factor, the reference's per-pixel sequence, the byte through the gain -> byte step table, rgb_ycc_convert for
+ * three channels, FDCT, quantize; the 8-bit map is written only when gm is given), and the base image's launch of the siblings runs beside
+ * it on the auxiliary stream.  No ratio plane, no reduction, no range read-back: the metadata is host arithmetic.  Coefficient blocks, map
+ * bytes and metadata are bit-identical to one-pass uhdr_hip_generate_gainmap_dev + uhdr_hip_fdct_quant_dev / _rgb_dev + the base image's
+ * staged blocks; the scans to those coefficients through uhdr_hip_huffman_encode_dev.
+ * UHDR_CODEC_UNSUPPORTED_FEATURE before anything is launched or uploaded: everything the siblings refuse but the preset -- gamma != 1,
+ * dimensions that are not whole MCUs, map dimensions (w / S, h / S) that are not multiples of 8, other SDR formats -- and, for
+ * UHDR_USAGE_REALTIME, a context with a communicator (row stripes stay two-pass).  Every other fused API-1 entry point keeps refusing
+ * UHDR_USAGE_REALTIME. */
+uhdr_error_info_t uhdr_hip_encode_api1_fused_onepass_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                         const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                         const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                         const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm);
+uhdr_error_info_t uhdr_hip_encode_api1_scans_onepass(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                     const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                     const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                     uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                     uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
+                                                     uint8_t* map_scan, size_t map_capacity, size_t* map_bytes);
+uhdr_error_info_t uhdr_hip_encode_api1_scans_onepass_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                         const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                         const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                         uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                         uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
+                                                         uint8_t* map_scan, size_t map_capacity, size_t* map_bytes);
+
 /* JpegR::encodeJPEGR API-0 (lib/src/jpegr.cpp:179-244) for the HDR intents whose tone-mapped rendition is RGBA8888 -- RGBA1010102 and RGBA
  * half float -- in ONE call (round 6): host intent in, the two entropy-coded scans out (host buffers).  uhdr_hip_encode_api0_fused_dev (tone
  * map + one-pass gain map + RGB -> YCbCr 4:4:4) + FDCT / quantize + both scans Huffman-coded; what the facade binds at encodeJPEGR API-0.

@@ -242,6 +242,31 @@ class UltraHdr {
                                                                                        base_bytes, map_scan, map_capacity, map_bytes);
   }
 
+  // encodeApi1FusedAny / encodeApi1ScansAny for the one-pass preset as well (uhdr_hip_encode_api1_fused_onepass_dev,
+  // uhdr_hip_encode_api1_scans_onepass / _onepass_dev): UHDR_USAGE_REALTIME is two launches -- both intents to the map's coefficients, the base
+  // image's blocks -- at any scale factor whose map is whole 8 x 8 blocks; UHDR_USAGE_BEST_QUALITY runs what the siblings run.
+  uhdr_error_info_t encodeApi1FusedOnePass(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* hdr_intent, uhdr_color_gamut_t base_encoding,
+                                           const uint16_t qt_base[2][64], const uint16_t qt_map[2][64], const uhdr_hip_api1_blocks_t* blocks,
+                                           uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_raw_image_t* gainmap_img, bool sdr_is_601 = false,
+                                           bool use_luminance = true) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, sdr_is_601 ? 1 : 0, use_luminance ? 1 : 0};
+    return uhdr_hip_encode_api1_fused_onepass_dev(mCtx, sdr_intent, hdr_intent, &cfg, base_encoding, qt_base, qt_map, blocks, gainmap_metadata, gainmap_img);
+  }
+  uhdr_error_info_t encodeApi1ScansOnePass(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* hdr_intent, uhdr_color_gamut_t base_encoding,
+                                           const uint16_t qt_base[2][64], const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* gainmap_metadata,
+                                           uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
+                                           uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, bool dev = false, bool sdr_is_601 = false,
+                                           bool use_luminance = true) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, sdr_is_601 ? 1 : 0, use_luminance ? 1 : 0};
+    return (dev ? uhdr_hip_encode_api1_scans_onepass_dev : uhdr_hip_encode_api1_scans_onepass)(mCtx, sdr_intent, hdr_intent, &cfg, base_encoding, qt_base,
+                                                                                               qt_map, gainmap_metadata, gainmap_desc, base_scan,
+                                                                                               base_capacity, base_bytes, map_scan, map_capacity, map_bytes);
+  }
+
   uhdr_error_info_t convertYuv(uhdr_raw_image_t* image, uhdr_color_gamut_t src_encoding, uhdr_color_gamut_t dst_encoding) {
     if (!mCtx) return mCreateStatus;
     return uhdr_hip_convert_yuv(mCtx, image, src_encoding, dst_encoding);

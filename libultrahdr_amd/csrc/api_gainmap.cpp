@@ -703,6 +703,29 @@ uhdr_error_info_t uhdr_api::two_pass_tail(uhdr_hip_ctx* c, const GenParams& p, i
   return ok_status();
 }
 
+// One pass (jpegr.cpp:724-737): the range is known before a pixel is read -- the metadata, the kernel's clamp and log2 constants, and the
+// gain -> byte step table for that range (p->gain8.tab stays null where host_tables.cpp has none: the kernels then evaluate per sample)
+uhdr_error_info_t uhdr_api::fill_onepass_range(uhdr_hip_ctx* c, const uhdr_hip_encode_cfg_t* cfg, float hdr_white_nits, int use_base_cg, GenParams* p,
+                                               uhdr_gainmap_metadata_t* md) {
+  for (int i = 0; i < 3; i++) {
+    md->max_content_boost[i] = hdr_white_nits / 203.0f;
+    md->min_content_boost[i] = 1.0f;
+    md->gamma[i] = cfg->gamma;
+    md->offset_sdr[i] = 0.0f;
+    md->offset_hdr[i] = 0.0f;
+  }
+  md->hdr_capacity_min = 1.0f;
+  md->hdr_capacity_max = cfg->target_disp_peak_nits != -1.0f ? cfg->target_disp_peak_nits / 203.0f : md->max_content_boost[0];
+  md->use_base_cg = use_base_cg;
+  p->min_boost = md->min_content_boost[0];
+  p->max_boost = md->max_content_boost[0];
+  p->log2min = log2f(md->min_content_boost[0]);
+  p->log2max = log2f(md->max_content_boost[0]);
+  p->log2_range = (double)(p->log2max - p->log2min);
+  p->log2_range_rcp = 1.0 / p->log2_range;
+  return gain_step_table(c, *p, &p->gain8);
+}
+
 uhdr_error_info_t uhdr_hip_generate_gainmap_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
                                                 const uhdr_hip_encode_cfg_t* cfg, uhdr_gainmap_metadata_t* md,
                                                 uhdr_raw_image_t* gm) {
@@ -716,23 +739,7 @@ uhdr_error_info_t uhdr_hip_generate_gainmap_dev(uhdr_hip_ctx_t* c, const uhdr_ra
   fill_gainmap_desc(hdr, p, gm);
   if (gm->stride[0] < gm->w) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap stride (%u) cannot be less than its width (%u)", gm->stride[0], gm->w);
   if (cfg->preset == UHDR_USAGE_REALTIME) {  // one pass: jpegr.cpp:724-737
-    for (int i = 0; i < 3; i++) {
-      md->max_content_boost[i] = hdr_white_nits / 203.0f;
-      md->min_content_boost[i] = 1.0f;
-      md->gamma[i] = cfg->gamma;
-      md->offset_sdr[i] = 0.0f;
-      md->offset_hdr[i] = 0.0f;
-    }
-    md->hdr_capacity_min = 1.0f;
-    md->hdr_capacity_max = cfg->target_disp_peak_nits != -1.0f ? cfg->target_disp_peak_nits / 203.0f : md->max_content_boost[0];
-    md->use_base_cg = use_base_cg;
-    p.min_boost = md->min_content_boost[0];
-    p.max_boost = md->max_content_boost[0];
-    p.log2min = log2f(md->min_content_boost[0]);
-    p.log2max = log2f(md->max_content_boost[0]);
-    p.log2_range = (double)(p.log2max - p.log2min);
-    p.log2_range_rcp = 1.0 / p.log2_range;
-    UHDR_TRY(gain_step_table(c, p, &p.gain8));
+    UHDR_TRY(fill_onepass_range(c, cfg, hdr_white_nits, use_base_cg, &p, md));
     p.out = (uint8_t*)gm->planes[0];
     p.out_stride = gm->stride[0];
     ProfScope ps(c, "generate_gainmap");

@@ -284,6 +284,7 @@ uhdr_error_info_t get_apply_tables(uhdr_hip_ctx* c, const uhdr_gainmap_metadata_
 // ---- api_gainmap.cpp: parameter blocks of the gain-map operators (shared with the striped and the fused entry points) ----
 uhdr_error_info_t fill_gen_params(uhdr_hip_ctx* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg, GenParams* p,
                                   int* use_base_cg, float* hdr_white_nits_out, bool sdr_in_registers = false);
+uhdr_error_info_t fill_onepass_range(uhdr_hip_ctx* c, const uhdr_hip_encode_cfg_t* cfg, float hdr_white_nits, int use_base_cg, GenParams* p, uhdr_gainmap_metadata_t* md);
 void fill_finalize(MinmaxTableParams* t, const uhdr_hip_encode_cfg_t* cfg);
 void fill_gainmap_desc(const uhdr_raw_image_t* hdr, const GenParams& p, uhdr_raw_image_t* gm);
 uhdr_error_info_t generate_gainmap_finalize_md(const uhdr_hip_encode_cfg_t* cfg, uhdr_color_transfer_t hdr_ct, int use_base_cg, const float mm[6], uhdr_gainmap_metadata_t* md);

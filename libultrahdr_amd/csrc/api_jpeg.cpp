@@ -338,11 +338,16 @@ uhdr_error_info_t uhdr_hip_encode_api0_p010_fused_scaled_dev(uhdr_hip_ctx_t* c, 
 static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
                                                 const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
                                                 const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
-                                                const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm, bool any_sdr) {
+                                                const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm, bool any_sdr,
+                                                bool onepass = false) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   HIP_TRY(hipSetDevice(c->device));
   const bool striped = c->comm != nullptr || c->comm_custom;
   const bool rgba = any_sdr && sdr && sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888;
+  // onepass (uhdr_hip_encode_api1_fused_onepass_dev): the real-time preset is taken too, as TWO launches -- launch_map_blocks_onepass (the
+  // range is known beforehand, jpegr.cpp:724-737: no ratio plane, no reduction, no range read-back) and the base image's blocks
+  const bool one = onepass && cfg && cfg->preset == UHDR_USAGE_REALTIME;
+  if (one && striped) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes, which stay two-pass (uhdr_hip_encode_api1_fused_dev)");
   if (rgba && striped) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes of 4:2:0 base images; an RGBA8888 SDR intent is encoded whole");
   Rgb2Yuv base_k;
   GenParams p;
@@ -365,7 +370,7 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
       return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_12bppYCbCr420 base image whose dimensions are multiples of 16 "
                         "(received format %d, %ux%u); use the operators", sdr->fmt, sdr->w, sdr->h);
     }
-    if (cfg->preset == UHDR_USAGE_REALTIME) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain is the two-pass (best quality) encode; one pass: generate_gainmap + fdct_quant");
+    if (cfg->preset == UHDR_USAGE_REALTIME && !onepass) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain is the two-pass (best quality) encode; one pass: generate_gainmap + fdct_quant");
     if (cfg->gamma != 1.0f) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs gain-map gamma 1 (received %f); use the operators", cfg->gamma);
     for (int t = 0; t < 2; t++)
       for (int i = 0; i < 64; i++)
@@ -406,17 +411,19 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
       if (r == -2) return err_status(UHDR_CODEC_INVALID_PARAM, "Unrecognized dest color gamut %d", base_encoding);
       convert = r == 0;
     }
-    UHDR_TRY(ensure(c->scratch[7], (size_t)p.map_w * p.map_h * nch * sizeof(float)));
+    if (!one) UHDR_TRY(ensure(c->scratch[7], (size_t)p.map_w * p.map_h * nch * sizeof(float)));
     return ok_status();
   };
-  // the exchange buffers first: without them a rank cannot even contribute the identity
-  UHDR_TRY(upload_math(c));
-  UHDR_TRY(ensure(c->minmax, (6 + 2048 * 6) * sizeof(float)));
-  UHDR_TRY(ensure(c->affine, kAffineDevBytes));
-  UHDR_TRY(ensure(c->exchange, 256));
-  if (!c->h_mm) HIP_TRY(hipHostMalloc((void**)&c->h_mm, 9 * sizeof(float), hipHostMallocDefault));
+  if (!one) {  // the exchange buffers first: without them a rank cannot even contribute the identity
+    UHDR_TRY(upload_math(c));
+    UHDR_TRY(ensure(c->minmax, (6 + 2048 * 6) * sizeof(float)));
+    UHDR_TRY(ensure(c->affine, kAffineDevBytes));
+    UHDR_TRY(ensure(c->exchange, 256));
+    if (!c->h_mm) HIP_TRY(hipHostMalloc((void**)&c->h_mm, 9 * sizeof(float), hipHostMallocDefault));
+  }
   uhdr_error_info_t local = prepare();
   if (local.error_code != UHDR_CODEC_OK && !striped) return local;
+  if (one) UHDR_TRY(fill_onepass_range(c, cfg, hdr_white_nits, use_base_cg, &p, md));  // the metadata is host arithmetic: complete here
   auto base_launch = [&](hipStream_t s) -> hipError_t {
     if (rgba) return launch_base_blocks_rgba(view_of(sdr), base_k, convert ? &conv : nullptr, qt_base[0], qt_base[1], blocks->base_coef, s);
     return launch_base_blocks(view_of(sdr), convert ? &conv : nullptr, qt_base[0], qt_base[1], blocks->base_coef, s);
@@ -436,7 +443,7 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   // stream UNDER pass 1 / the range kernel / the map's blocks instead of behind them (the chain's four launches were strictly serial: 21 of
   // 103 us at 4K).  Whole images only (a stripe's chain keeps its order around the exchange); UHDR_HIP_NO_CHAIN_OVERLAP=1: the serial form.
   uhdr_hip_ctx* side = nullptr;
-  if (run && !striped && !getenv("UHDR_HIP_NO_CHAIN_OVERLAP")) {
+  auto base_on_side = [&]() {
     uhdr_hip_ctx* x = nullptr;
     if (aux_context(c, &x).error_code == UHDR_CODEC_OK && x) {
       hipError_t e = hipSuccess;
@@ -454,6 +461,24 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
         if (c->on_side_launched) c->on_side_launched();
       }
     }
+  };
+  if (run && !striped && !getenv("UHDR_HIP_NO_CHAIN_OVERLAP")) base_on_side();
+  if (one) {  // map blocks here, base blocks there (or behind them); nothing to read back
+    {
+      ProfScope ps(c, "map_blocks_onepass");
+      note_hip(launch_map_blocks_onepass(p, nch, qt_map[0], qt_map[1], blocks->map_coef, map_out, map_stride, c->stream), "one-pass map blocks");
+    }
+    if (!side) {
+      ProfScope ps(c, rgba ? "base_blocks_rgba" : "fdct_quant");
+      note_hip(base_launch(c->stream), "base blocks");
+    }
+    if (side) {
+      note_hip(hipStreamWaitEvent(c->stream, c->aux_ev2, 0), "base blocks wait");
+      if (!c->side_job_posted) aux_merge(c);
+    }
+    chain.reset();
+    if (!c->defer_md) note_hip(hipStreamSynchronize(c->stream), "synchronize");  // (as the two-pass chain returns: coefficients complete)
+    return local;
   }
   {
     ProfScope ps(c, "generate_gainmap");
@@ -547,6 +572,12 @@ uhdr_error_info_t uhdr_hip_encode_api1_fused_any_dev(uhdr_hip_ctx_t* c, const uh
                                                      const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
   return encode_api1_fused_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, blocks, md, gm, true);
 }
+uhdr_error_info_t uhdr_hip_encode_api1_fused_onepass_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                         const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                         const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                         const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
+  return encode_api1_fused_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, blocks, md, gm, true, true);
+}
 
 // JpegR::encodeJPEGR API-1 (jpegr.cpp:253-316) from its two raw intents to its two entropy-coded scans in ONE entry point: the
 // intents go up once (fast_h2d), the fused chain leaves coefficient blocks in HBM, the marker-less Huffman coder turns them into
@@ -554,7 +585,8 @@ uhdr_error_info_t uhdr_hip_encode_api1_fused_any_dev(uhdr_hip_ctx_t* c, const uh
 static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
                                                 uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
                                                 uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
-                                                size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, bool dev = false, bool any_sdr = false);
+                                                size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, bool dev = false, bool any_sdr = false,
+                                                bool onepass = false);
 // ... and on DEVICE-resident intents, into DEVICE buffers (round 6): one call per direction of the round trip, so that no binding
 // layer sits between the stages (a Python caller's 30-100 us between two entry points were a third of a 4K round trip)
 uhdr_error_info_t uhdr_hip_encode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
@@ -581,6 +613,25 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans_any(uhdr_hip_ctx_t* c, const uhdr_r
   if (c) c->stats.last_encode_api1_scans_ns = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
   return r;
 }
+// ... and with the one-pass (real-time) preset as well: what the _any siblings run for UHDR_USAGE_BEST_QUALITY, the two launches of
+// uhdr_hip_encode_api1_fused_onepass_dev in front of the same entropy stage for UHDR_USAGE_REALTIME
+uhdr_error_info_t uhdr_hip_encode_api1_scans_onepass_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                         uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                         uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                                         size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
+  return encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
+                                map_bytes, true, true, true);
+}
+uhdr_error_info_t uhdr_hip_encode_api1_scans_onepass(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                     uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                     uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                                     size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const uhdr_error_info_t r = encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes,
+                                                     map_scan, map_capacity, map_bytes, false, true, true);
+  if (c) c->stats.last_encode_api1_scans_ns = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+  return r;
+}
 uhdr_error_info_t uhdr_hip_encode_api1_scans(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
                                              uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
                                              uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
@@ -594,7 +645,7 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans(uhdr_hip_ctx_t* c, const uhdr_raw_i
 static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
                                                 uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
                                                 uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
-                                                size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, bool dev, bool any_sdr) {
+                                                size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, bool dev, bool any_sdr, bool onepass) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!sdr || !hdr || !cfg || !qt_base || !qt_map || !md || !base_scan || !map_scan || !base_bytes || !map_bytes)
     return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
@@ -610,7 +661,7 @@ static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   } else if (sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420 || sdr->w % 16 || sdr->h % 16 || sdr->w == 0 || sdr->h == 0)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_12bppYCbCr420 base image whose dimensions are multiples of 16 "
                       "(received format %d, %ux%u); use the operators", sdr->fmt, sdr->w, sdr->h);
-  if (cfg->preset == UHDR_USAGE_REALTIME) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain is the two-pass (best quality) encode");
+  if (cfg->preset == UHDR_USAGE_REALTIME && !onepass) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain is the two-pass (best quality) encode");
   if (cfg->gamma != 1.0f) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs gain-map gamma 1 (received %f)", cfg->gamma);
   const int scale = cfg->map_dimension_scale_factor;
   if (scale < 1 || sdr->w / (unsigned)scale == 0 || sdr->h / (unsigned)scale == 0 || (sdr->w / (unsigned)scale) % 8 || (sdr->h / (unsigned)scale) % 8)
@@ -690,7 +741,7 @@ static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   c->side_job_posted = false;
   c->defer_md = dev;  // device-resident callers: no host synchronisation between the chain and the entropy stage
   c->deferred_md.valid = false;
-  const uhdr_error_info_t fs = encode_api1_fused_impl(c, &ds, &dh, cfg, base_encoding, qt_base, qt_map, &blocks, md, nullptr, any_sdr);
+  const uhdr_error_info_t fs = encode_api1_fused_impl(c, &ds, &dh, cfg, base_encoding, qt_base, qt_map, &blocks, md, nullptr, any_sdr, onepass);
   c->defer_md = false;
   c->on_side_launched = nullptr;
   const bool base_posted = c->side_job_posted;

@@ -16,6 +16,7 @@
 //                       FDCT / quantize from registers (below; tests/test_gpu_api1_rgba.py)
 //
 // Coefficients are bit-identical to the unfused chain (tests/test_gpu_parity.py::test_api1_fused_chain_equals_the_operators).
+#include <stdlib.h>
 #include <string.h>
 #include "lds_copy.h"
 
@@ -130,6 +131,45 @@ __device__ __forceinline__ void store_coef_row(int16_t* dst, const int v[8]) {
   *(uint4*)dst = o;
 }
 
+// The block side of a gain map, shared by map_blocks_kernel and map_blocks_onepass_kernel, in the halves of their strip loop.
+// An ACTIVE lane (row rr, block rb) holds the 8 * NCH map bytes of its row of its block in w, packed as they come:
+// map_row_samples: libjpeg's rgb_ycc_convert for three channels, level shift (the optional 8-byte stores of the map itself stay in the
+// kernels: inside a helper they cost map_blocks_kernel<3> 14 VGPRs and a workgroup per CU).
+// map_strip_transform: the NCH transforms of the strip; inactive lanes (blocks past bw) take part in the transposes only.
+#define FIX16(x) ((int)((x) * 65536.0 + 0.5))
+template <int NCH>
+__device__ __forceinline__ void map_row_samples(const uint32_t (&w)[2 * NCH], int (&comp)[3][8]) {
+  auto byte_at = [&](int e) -> int { return (int)((w[e >> 2] >> (8 * (e & 3))) & 0xffu); };
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    if (NCH == 3) {  // jccolor.c rgb_ycc_convert (fdct_quant.hip / jpeg_decode.hip: both published constant sets give these bytes)
+      const int r = byte_at(3 * k), gg = byte_at(3 * k + 1), bb = byte_at(3 * k + 2);
+      const int half = 1 << 15, off = 128 << 16;
+      comp[0][k] = ((__mul24(FIX16(0.29900), r) + __mul24(FIX16(0.58700), gg) + __mul24(FIX16(0.11400), bb) + half) >> 16) - 128;
+      comp[1][k] = ((__mul24(-FIX16(0.16874), r) + __mul24(-FIX16(0.33126), gg) + __mul24(FIX16(0.50000), bb) + off + half - 1) >> 16) - 128;
+      comp[2][k] = ((__mul24(FIX16(0.50000), r) + __mul24(-FIX16(0.41869), gg) + __mul24(-FIX16(0.08131), bb) + off + half - 1) >> 16) - 128;
+    } else {
+      comp[0][k] = byte_at(k) - 128;
+    }
+  }
+}
+template <int NCH>
+__device__ __forceinline__ void map_strip_transform(const int (&comp)[3][8], bool active, int16_t* const coef[3], int bw, int by, int bx, int lane, int* ws,
+                                                    const uint2 (*s_q)[64]) {
+#pragma unroll
+  for (int ci = 0; ci < NCH; ci++) {
+    int out[8], v[8];
+    if (active) {
+      fdct_1d<0>(comp[ci], out);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 8; c++) out[c] = 0;
+    }
+    column_pass_and_quantize(ws, lane, out, s_q[ci == 0 ? 0 : 1], v);
+    if (active) store_coef_row(coef[ci] + ((size_t)by * bw + bx) * 64 + (lane >> 3) * 8, v);
+  }
+}
+
 // ---- the gain map: ratio plane -> coefficients ------------------------------------------------------------------------------------
 struct MapBlocksParams {
   const float* ratio;      // map_w * map_h * nch gain ratios (pass 1)
@@ -142,7 +182,6 @@ struct MapBlocksParams {
   QuantPair q;
 };
 
-#define FIX16(x) ((int)((x) * 65536.0 + 0.5))
 constexpr int kMapBlock = 512;  // eight waves share one copy of the step tables (24 KB): three workgroups = 24 waves per CU
 template <int NCH>
 __global__ __launch_bounds__(kMapBlock) void map_blocks_kernel(const MapBlocksParams p) {
@@ -221,32 +260,153 @@ __global__ __launch_bounds__(kMapBlock) void map_blocks_kernel(const MapBlocksPa
 #pragma unroll
         for (int k = 0; k < NCH; k++) *(uint2*)(o + 8 * k) = uint2{w[2 * k], w[2 * k + 1]};
       }
-      auto byte_at = [&](int e) -> int { return (int)((w[e >> 2] >> (8 * (e & 3))) & 0xffu); };
+      map_row_samples<NCH>(w, comp);
+    }
+    map_strip_transform<NCH>(comp, active, p.coef, p.bw, by, bx, lane, ws, s_q);
+  }
+}
+
+// ---- the gain map in one pass: the two intents -> coefficients --------------------------------------------------------------------
+// The one-pass (UHDR_USAGE_REALTIME) generateGainMap (jpegr.cpp:719-835) knows its gain range before it reads a pixel, so nothing has to
+// wait between the pixel side and the block side: generate_kernel<.., TWO_PASS = false>'s pixel (generate_gainmap.hip) and
+// map_blocks_kernel's strip in one kernel.  Lane (row rr, block rb) computes the eight map pixels of row rr of block rb -- sample_box
+// over the s x s box of both intents, yuv -> rgb, the inverse-OETF tables, gamut matrix + clipNegatives, gain, byte through the gain8
+// step table -- packs them into the words map_blocks_kernel builds and goes on with map_row_samples / map_strip_transform.  The 8-bit map reaches HBM only when
+// the caller wants it (g.out != null).  A call without a gain8 table (host_tables.cpp declined the boost range) evaluates encode_gain's
+// float64 form per sample, as a rolled loop that parks its bytes in the wave's idle workspace, as map_blocks_kernel does.
+// FAST: 4:2:0 + P010 at scale 1 with rows the vector loads can take (map_onepass_fast_layout) -- a lane's row is one 8-byte luma load,
+// two 4-byte chroma loads and two 16-byte P010 loads instead of forty scalar ones; fetch_pixel's normalisation, the same floats.
+// LDS: sRGB 4 KB + HDR table 16 KB + unorm 5 KB + gain8 16 KB + 8 workspaces 18 KB + quantiser 1 KB = 60 KB: two workgroups per CU.
+struct MapOnepassParams {
+  GenParams g;             // g.out / g.out_stride: the optional 8-bit map
+  int bw, bh;              // blocks (map_w / 8, map_h / 8)
+  int16_t* coef[3];
+  QuantPair q;
+};
+struct OnepassLds {
+  float srgb[kSrgbN];
+  float hdr[kInvOetfN];
+  UnormTables unorm;
+};
+
+// one map pixel from the two box means: generate_kernel's sequence, with gain_of_pixel<false>'s bytes (encode_core.h) kept in registers
+template <int NCH>
+__device__ __forceinline__ void onepass_codes(Color3 s, Color3 h, const GenParams& p, const OnepassLds& L, const uint2* gain8, bool hdr_lut,
+                                              bool hdr_lut_4096, uint32_t code[NCH]) {
+  if (!p.sdr_is_rgb) s = yuv_to_rgb(s.r, s.g, s.b, p.sdr_yuv);
+  Color3 sl = linearise_hdr(s, L.srgb, true, false);
+  if (p.sdr_gamut_on) {
+    sl = mat3_apply(sl, p.sdr_gamut);
+    sl.r = clip_neg(sl.r); sl.g = clip_neg(sl.g); sl.b = clip_neg(sl.b);
+  }
+  if (!p.hdr_is_rgb) h = yuv_to_rgb(h.r, h.g, h.b, p.hdr_yuv);
+  Color3 hl = linearise_hdr(h, L.hdr, hdr_lut, hdr_lut_4096);
+  if (p.hdr_gamut_on) {
+    hl = mat3_apply(hl, p.hdr_gamut);
+    hl.r = clip_neg(hl.r); hl.g = clip_neg(hl.g); hl.b = clip_neg(hl.b);
+  }
+  if (NCH == 3) {
+    code[0] = encode_gain(sl.r * 203.0f, hl.r * p.hdr_nits, p, p.math_tab, gain8);
+    code[1] = encode_gain(sl.g * 203.0f, hl.g * p.hdr_nits, p, p.math_tab, gain8);
+    code[2] = encode_gain(sl.b * 203.0f, hl.b * p.hdr_nits, p, p.math_tab, gain8);
+  } else {
+    float sy, hy;
+    if (p.use_luminance) {
+      sy = (p.lum[0] * sl.r + p.lum[1] * sl.g + p.lum[2] * sl.b) * 203.0f;
+      hy = (p.lum[0] * hl.r + p.lum[1] * hl.g + p.lum[2] * hl.b) * p.hdr_nits;
+    } else {
+      sy = fmaxf(sl.r, fmaxf(sl.g, sl.b)) * 203.0f;
+      hy = fmaxf(hl.r, fmaxf(hl.g, hl.b)) * p.hdr_nits;
+    }
+    code[0] = encode_gain(sy, hy, p, p.math_tab, gain8);
+  }
+}
+
+template <int SDRF, int HDRF, int NCH, bool FAST>
+__global__ __launch_bounds__(kMapBlock, 4) void map_blocks_onepass_kernel(const MapOnepassParams p) {
+  constexpr int kBlock = kMapBlock;
+  __shared__ int s_ws[kBlock / 64][8 * 8 * 9];
+  __shared__ OnepassLds L;
+  __shared__ alignas(16) uint2 s_gain8[kStepTabMax];
+  __shared__ uint2 s_q[2][64];
+  const uint32_t tid = threadIdx.x;
+  if (tid < 128) s_q[tid >> 6][tid & 63] = uint2{p.q.qv[tid >> 6][tid & 63], p.q.qm[tid >> 6][tid & 63]};
+  const GenParams& g = p.g;
+  stage_step_tab(s_gain8, g.gain8, tid, kBlock);
+  copy_to_lds(L.srgb, g.srgb_lut, (uint32_t)kSrgbN, tid, kBlock);
+  if (g.hdr_inv_lut) copy_to_lds(L.hdr, g.hdr_inv_lut, (uint32_t)g.hdr_inv_n, tid, kBlock);
+  fill_unorm_tables(L.unorm, tid, kBlock);
+  __syncthreads();
+  const bool hdr_lut = g.hdr_inv_lut != nullptr, hdr_lut_4096 = g.hdr_inv_n == kInvOetfN;
+  const bool tab = g.gain8.tab != nullptr;
+  const int lane = tid & 63, wv = tid >> 6;
+  int* ws = s_ws[wv];
+  const int groups_x = (p.bw + 7) >> 3, total = groups_x * p.bh;
+  const int gwave = blockIdx.x * (kBlock / 64) + wv, nwaves = gridDim.x * (kBlock / 64);
+  const int rr = lane >> 3, rb = lane & 7;
+  for (int t = gwave; t < total; t += nwaves) {
+    const int by = t / groups_x, gx = t - by * groups_x;
+    const int bx = gx * 8 + rb;
+    const bool active = bx < p.bw;
+    int comp[3][8];
+    if (active) {
+      const uint32_t y = by * 8 + rr, x0 = bx * 8;
+      uint32_t w[2 * NCH];  // the 8 * NCH map bytes of this row, packed as they come
 #pragma unroll
-      for (int k = 0; k < 8; k++) {
-        if (NCH == 3) {  // jccolor.c rgb_ycc_convert (fdct_quant.hip / jpeg_decode.hip: both published constant sets give these bytes)
-          const int r = byte_at(3 * k), gg = byte_at(3 * k + 1), bb = byte_at(3 * k + 2);
-          const int half = 1 << 15, off = 128 << 16;
-          comp[0][k] = ((__mul24(FIX16(0.29900), r) + __mul24(FIX16(0.58700), gg) + __mul24(FIX16(0.11400), bb) + half) >> 16) - 128;
-          comp[1][k] = ((__mul24(-FIX16(0.16874), r) + __mul24(-FIX16(0.33126), gg) + __mul24(FIX16(0.50000), bb) + off + half - 1) >> 16) - 128;
-          comp[2][k] = ((__mul24(FIX16(0.50000), r) + __mul24(-FIX16(0.41869), gg) + __mul24(-FIX16(0.08131), bb) + off + half - 1) >> 16) - 128;
-        } else {
-          comp[0][k] = byte_at(k) - 128;
+      for (int i = 0; i < 2 * NCH; i++) w[i] = 0;
+      if (FAST) {  // (the launcher comes here with a gain8 table only)
+        const uint2 yl = *(const uint2*)((const uint8_t*)g.sdr.p[0] + (size_t)y * g.sdr.stride[0] + x0);
+        const uint32_t ub = *(const uint32_t*)((const uint8_t*)g.sdr.p[1] + (size_t)(y >> 1) * g.sdr.stride[1] + (x0 >> 1));
+        const uint32_t vb = *(const uint32_t*)((const uint8_t*)g.sdr.p[2] + (size_t)(y >> 1) * g.sdr.stride[2] + (x0 >> 1));
+        const uint4 hyv = *(const uint4*)((const uint16_t*)g.hdr.p[0] + (size_t)y * g.hdr.stride[0] + x0);
+        const uint4 hcv = *(const uint4*)((const uint16_t*)g.hdr.p[1] + (size_t)(y >> 1) * g.hdr.stride[1] + x0);
+        const uint32_t yw[2] = {yl.x, yl.y}, hy2[4] = {hyv.x, hyv.y, hyv.z, hyv.w}, hc2[4] = {hcv.x, hcv.y, hcv.z, hcv.w};
+        const bool full = g.hdr.range == UHDR_CR_FULL_RANGE;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {  // fetch_pixel's normalisation of both formats (pixel_io.h)
+          const int yy = (int)((yw[k >> 2] >> (8 * (k & 3))) & 0xff), uu = (int)((ub >> (8 * (k >> 1))) & 0xff), vv = (int)((vb >> (8 * (k >> 1))) & 0xff);
+          const Color3 s = {(float)yy * (1 / 255.0f), (float)(uu - 128) * (1 / 255.0f), (float)(vv - 128) * (1 / 255.0f)};
+          const int hy = (int)(((hy2[k >> 1] >> (16 * (k & 1))) & 0xffff) >> 6), hu = (int)((hc2[k >> 1] & 0xffff) >> 6), hv = (int)(hc2[k >> 1] >> 22);
+          Color3 h;
+          if (full) h = {L.unorm.u10[hy], L.unorm.u10[hu] - 0.5f, L.unorm.u10[hv] - 0.5f};
+          else h = {(float)(hy - 64) * (1 / 876.0f), (float)(hu - 64) * (1 / 896.0f) - 0.5f, (float)(hv - 64) * (1 / 896.0f) - 0.5f};
+          uint32_t code[NCH];
+          onepass_codes<NCH>(s, h, g, L, s_gain8, hdr_lut, hdr_lut_4096, code);
+#pragma unroll
+          for (int c = 0; c < NCH; c++) w[(k * NCH + c) >> 2] |= code[c] << (8 * ((k * NCH + c) & 3));
         }
-      }
-    }
+      } else if (HDRF >= 0 && tab) {
 #pragma unroll
-    for (int ci = 0; ci < NCH; ci++) {
-      int out[8], v[8];
-      if (active) {
-        fdct_1d<0>(comp[ci], out);
-      } else {
+        for (int k = 0; k < 8; k++) {
+          const Color3 s = sample_box<SDRF>(g.sdr, g.scale, x0 + k, y, &L.unorm), h = sample_box<HDRF>(g.hdr, g.scale, x0 + k, y, &L.unorm);
+          uint32_t code[NCH];
+          onepass_codes<NCH>(s, h, g, L, s_gain8, hdr_lut, hdr_lut_4096, code);
 #pragma unroll
-        for (int c = 0; c < 8; c++) out[c] = 0;
+          for (int c = 0; c < NCH; c++) w[(k * NCH + c) >> 2] |= code[c] << (8 * ((k * NCH + c) & 3));
+        }
+      } else {  // no gain8 table for this boost range: encode_gain's own per-sample evaluation, rolled, bytes parked in the idle workspace
+                // (and the HDR formats without an instantiation of their own -- 30-bit 4:4:4, half float: eight copies of the format
+                // switch are not worth their registers)
+        uint8_t* park = (uint8_t*)(ws + lane * 9);
+#pragma unroll 1
+        for (int k = 0; k < 8; k++) {
+          const Color3 s = sample_box<SDRF>(g.sdr, g.scale, x0 + k, y, &L.unorm), h = sample_box<HDRF>(g.hdr, g.scale, x0 + k, y, &L.unorm);
+          uint32_t code[NCH];
+          onepass_codes<NCH>(s, h, g, L, tab ? s_gain8 : nullptr, hdr_lut, hdr_lut_4096, code);
+#pragma unroll
+          for (int c = 0; c < NCH; c++) park[k * NCH + c] = (uint8_t)code[c];
+        }
+#pragma unroll
+        for (int i = 0; i < 2 * NCH; i++) w[i] = (uint32_t)ws[lane * 9 + i];
       }
-      column_pass_and_quantize(ws, lane, out, s_q[ci == 0 ? 0 : 1], v);
-      if (active) store_coef_row(p.coef[ci] + ((size_t)by * p.bw + bx) * 64 + rr * 8, v);
+      if (g.out) {
+        uint8_t* o = g.out + ((size_t)y * g.out_stride + x0) * NCH;
+#pragma unroll
+        for (int k = 0; k < NCH; k++) *(uint2*)(o + 8 * k) = uint2{w[2 * k], w[2 * k + 1]};
+      }
+      map_row_samples<NCH>(w, comp);
     }
+    map_strip_transform<NCH>(comp, active, p.coef, p.bw, by, bx, lane, ws, s_q);
   }
 }
 
@@ -475,6 +635,53 @@ hipError_t launch_map_blocks(const float* ratio, const AffineDev* dev, const dou
   if (grid > cap) grid = cap;
   if (nch == 3) hipLaunchKernelGGL((map_blocks_kernel<3>), dim3(grid), dim3(kMapBlock), 0, s, p);
   else hipLaunchKernelGGL((map_blocks_kernel<1>), dim3(grid), dim3(kMapBlock), 0, s, p);
+  return hipGetLastError();
+}
+
+// do the vector loads of map_blocks_onepass_kernel<.., FAST> stay aligned?  4:2:0 + P010 at scale 1: 8 luma bytes, 4 + 4 chroma bytes,
+// 16 + 16 bytes of P010 per lane and row
+static bool map_onepass_fast_layout(const GenParams& g) {
+  if (g.scale != 1 || g.sdr.fmt != UHDR_IMG_FMT_12bppYCbCr420 || g.hdr.fmt != UHDR_IMG_FMT_24bppYCbCrP010 || g.sdr.h % 2) return false;
+  if (((uintptr_t)g.sdr.p[0] | g.sdr.stride[0]) & 7) return false;
+  if (((uintptr_t)g.sdr.p[1] | (uintptr_t)g.sdr.p[2] | g.sdr.stride[1] | g.sdr.stride[2]) & 3) return false;
+  if (((uintptr_t)g.hdr.p[0] | (uintptr_t)g.hdr.p[1]) & 15) return false;
+  return g.hdr.stride[0] % 8 == 0 && g.hdr.stride[1] % 8 == 0;  // (strides in 16-bit samples)
+}
+template <int SDRF, int HDRF>
+static void launch_onepass_n(const MapOnepassParams& p, int nch, int grid, hipStream_t s) {
+  if (nch == 3) hipLaunchKernelGGL((map_blocks_onepass_kernel<SDRF, HDRF, 3, false>), dim3(grid), dim3(kMapBlock), 0, s, p);
+  else hipLaunchKernelGGL((map_blocks_onepass_kernel<SDRF, HDRF, 1, false>), dim3(grid), dim3(kMapBlock), 0, s, p);
+}
+
+// The one-pass gain map of the two intents in g (fill_gen_params + the one-pass range + gain8; g.out: the optional 8-bit map, g.out_stride
+// pixels) -> quantized coefficients of the map's JPEG.  map_w, map_h multiples of 8, gamma 1; SDR 4:2:0 or RGBA8888, every HDR format
+// fill_gen_params takes; nch as in launch_map_blocks.
+hipError_t launch_map_blocks_onepass(const GenParams& g, int nch, const uint16_t* qt_luma, const uint16_t* qt_chroma, int16_t* const coef[3],
+                                     uint8_t* map_out, uint32_t out_stride, hipStream_t s) {
+  MapOnepassParams p;
+  memset(&p, 0, sizeof p);
+  p.g = g;
+  p.g.out = map_out; p.g.out_stride = out_stride;
+  p.bw = (int)(g.map_w / 8); p.bh = (int)(g.map_h / 8);
+  for (int i = 0; i < nch; i++) p.coef[i] = coef[i];
+  fill_quant(qt_luma, qt_chroma, &p.q);
+  int grid = (((p.bw + 7) / 8) * p.bh + kMapBlock / 64 - 1) / (kMapBlock / 64);
+  const int cap = resident_grid(1 << 30, 2);  // 60 KB of LDS (tables + workspaces) per 512 threads: two workgroups per CU
+  if (grid > cap) grid = cap;
+  constexpr int k420 = UHDR_IMG_FMT_12bppYCbCr420, kRgba = UHDR_IMG_FMT_32bppRGBA8888, kP010 = UHDR_IMG_FMT_24bppYCbCrP010, k1010102 = UHDR_IMG_FMT_32bppRGBA1010102;
+  // UHDR_HIP_ONEPASS_NO_VECTOR_FETCH=1: the per-sample fetch on every layout (tools/api1_onepass_time.py times the two against each other)
+  if (g.gain8.tab && map_onepass_fast_layout(g) && !getenv("UHDR_HIP_ONEPASS_NO_VECTOR_FETCH")) {
+    if (nch == 3) hipLaunchKernelGGL((map_blocks_onepass_kernel<k420, kP010, 3, true>), dim3(grid), dim3(kMapBlock), 0, s, p);
+    else hipLaunchKernelGGL((map_blocks_onepass_kernel<k420, kP010, 1, true>), dim3(grid), dim3(kMapBlock), 0, s, p);
+  } else if (g.sdr.fmt == k420) {
+    if (g.hdr.fmt == kP010) launch_onepass_n<k420, kP010>(p, nch, grid, s);
+    else launch_onepass_n<k420, -1>(p, nch, grid, s);
+  } else if (g.sdr.fmt == kRgba) {
+    if (g.hdr.fmt == k1010102) launch_onepass_n<kRgba, k1010102>(p, nch, grid, s);
+    else launch_onepass_n<kRgba, -1>(p, nch, grid, s);
+  } else {
+    return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

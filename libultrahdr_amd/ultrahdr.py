@@ -285,7 +285,7 @@ class UltraHdr:
         return ob[:nb.value].tobytes(), om[:nm.value].tobytes(), md, desc, int(cg.value)
 
     def encodeApi1Fused(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, want_map=True,
-                        sdr_is_601=False, use_luminance=True, _any=False):
+                        sdr_is_601=False, use_luminance=True, _any=False, _fn=None):
         """MI355X extension: the sample -> coefficient part of an API-1 encode (jpegr.cpp:253-316) in four launches on
         device-resident images -- two-pass generateGainMap fused with the map's rgb->ycc + FDCT, convertYuv fused with the base
         image's three FDCTs.  qt_base / qt_map: (luma, chroma) quantization tables.  Returns (base coefficient tensors [3],
@@ -310,7 +310,7 @@ class UltraHdr:
             gm = Image(A.UHDR_IMG_FMT_24bppRGB888 if nch == 3 else A.UHDR_IMG_FMT_8bppYCbCr400, mw, mh, align=64, device=sdr_intent.device)
         md = A.GainmapMetadata()
         cfg = self.encode_cfg(sdr_is_601, use_luminance)
-        fn = self.lib.uhdr_hip_encode_api1_fused_any_dev if _any else self.lib.uhdr_hip_encode_api1_fused_dev
+        fn = _fn or (self.lib.uhdr_hip_encode_api1_fused_any_dev if _any else self.lib.uhdr_hip_encode_api1_fused_dev)
         self._call(True, fn, self.ctx.handle, C.byref(sdr_intent.raw), C.byref(hdr_intent.raw), C.byref(cfg),
                    base_encoding, C.c_void_p(qb.ctypes.data), C.c_void_p(qm.ctypes.data), C.byref(blocks), C.byref(md),
                    C.byref(gm.raw) if gm is not None else None)
@@ -324,6 +324,15 @@ class UltraHdr:
         encodeApi1Fused runs; an RGBA8888 intent (dimensions multiples of 8) has a 4:4:4 base image -- three (h/8, w/8, 64) base
         coefficient tensors, bit-identical to convert_raw_input_to_ycbcr + convertYuv + fdct_quant x 3.  encodeApi1Fused keeps refusing RGBA8888."""
         return self.encodeApi1Fused(sdr_intent, hdr_intent, base_encoding, qt_base, qt_map, want_map, sdr_is_601, use_luminance, _any=True)
+
+    def encodeApi1FusedOnePass(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, want_map=True,
+                               sdr_is_601=False, use_luminance=True):
+        """encodeApi1FusedAny for the one-pass preset as well (uhdr_hip_encode_api1_fused_onepass_dev): with UHDR_USAGE_REALTIME two launches
+        -- both intents to the map's coefficients at any scale factor whose map is whole 8 x 8 blocks, the base image's blocks --
+        bit-identical to one-pass generateGainMap + fdct_quant / fdct_quant_rgb + the base image's staged blocks; with
+        UHDR_USAGE_BEST_QUALITY what encodeApi1FusedAny runs.  The other encodeApi1* methods keep refusing the one-pass preset."""
+        return self.encodeApi1Fused(sdr_intent, hdr_intent, base_encoding, qt_base, qt_map, want_map, sdr_is_601, use_luminance, _any=True,
+                                    _fn=self.lib.uhdr_hip_encode_api1_fused_onepass_dev)
 
     # ---- one entry point per direction of the API-1 round trip, device resident (round 6) -----------------
     def encodeApi1Scans(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, out_base, out_map,
@@ -341,8 +350,15 @@ class UltraHdr:
                    C.c_void_p(out_map.data_ptr()), int(out_map.numel()), C.byref(nm))
         return int(nb.value), int(nm.value), md
 
+    def encodeApi1ScansOnePass(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, out_base, out_map,
+                               sdr_is_601=False, use_luminance=True):
+        """encodeApi1ScansAny for the one-pass preset as well (uhdr_hip_encode_api1_scans_onepass_dev for device images,
+        uhdr_hip_encode_api1_scans_onepass for host images): same arguments, same returns."""
+        return self.encodeApi1ScansAny(sdr_intent, hdr_intent, base_encoding, qt_base, qt_map, out_base, out_map, sdr_is_601, use_luminance,
+                                       _fns=(self.lib.uhdr_hip_encode_api1_scans_onepass_dev, self.lib.uhdr_hip_encode_api1_scans_onepass))
+
     def encodeApi1ScansAny(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, out_base, out_map,
-                           sdr_is_601=False, use_luminance=True):
+                           sdr_is_601=False, use_luminance=True, _fns=None):
         """encodeApi1Scans for both SDR intents API-1 takes, YCbCr 4:2:0 and RGBA8888 (base scan 1x1 / 1x1 / 1x1), in ONE C call.
         Device images (uhdr_hip_encode_api1_scans_any_dev): out_base / out_map are uint8 CUDA tensors; returns (bytes of the base scan,
         bytes of the map scan, metadata).  Host images (uhdr_hip_encode_api1_scans_any): out_base / out_map are the two capacities in
@@ -352,9 +368,10 @@ class UltraHdr:
         md = A.GainmapMetadata()
         cfg = self.encode_cfg(sdr_is_601, use_luminance)
         nb, nm = C.c_size_t(0), C.c_size_t(0)
+        fn_dev, fn_host = _fns or (self.lib.uhdr_hip_encode_api1_scans_any_dev, self.lib.uhdr_hip_encode_api1_scans_any)
         if _is_dev(sdr_intent, hdr_intent):
             assert out_base.is_cuda and out_map.is_cuda
-            self._call(True, self.lib.uhdr_hip_encode_api1_scans_any_dev, self.ctx.handle, C.byref(sdr_intent.raw), C.byref(hdr_intent.raw), C.byref(cfg),
+            self._call(True, fn_dev, self.ctx.handle, C.byref(sdr_intent.raw), C.byref(hdr_intent.raw), C.byref(cfg),
                        base_encoding, C.c_void_p(qb.ctypes.data), C.c_void_p(qm.ctypes.data), C.byref(md), None, C.c_void_p(out_base.data_ptr()),
                        int(out_base.numel()), C.byref(nb), C.c_void_p(out_map.data_ptr()), int(out_map.numel()), C.byref(nm))
             return int(nb.value), int(nm.value), md
@@ -362,7 +379,7 @@ class UltraHdr:
         desc = A.RawImage()
         ob, om = np.empty(max(1, int(out_base)), np.uint8), np.empty(max(1, int(out_map)), np.uint8)
         try:
-            self._call(False, self.lib.uhdr_hip_encode_api1_scans_any, self.ctx.handle, C.byref(sdr_intent.raw), C.byref(hdr_intent.raw), C.byref(cfg),
+            self._call(False, fn_host, self.ctx.handle, C.byref(sdr_intent.raw), C.byref(hdr_intent.raw), C.byref(cfg),
                        base_encoding, C.c_void_p(qb.ctypes.data), C.c_void_p(qm.ctypes.data), C.byref(md), C.byref(desc), C.c_void_p(ob.ctypes.data),
                        int(out_base), C.byref(nb), C.c_void_p(om.ctypes.data), int(out_map), C.byref(nm))
         except A.UhdrError as e:
