@@ -125,79 +125,115 @@ static uhdr_error_info_t check_scaled_request(const uhdr_raw_image_t* hdr, const
   return ok_status();
 }
 
-// scaled == false: uhdr_hip_encode_api0_fused_dev; true: uhdr_hip_encode_api0_fused_scaled_dev, which also takes scale factors 2 and 4
-static uhdr_error_info_t encode_api0_fused_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
-                                                uhdr_raw_image_t* sdr_rgba, uhdr_raw_image_t* base_ycc, uhdr_gainmap_metadata_t* md,
-                                                uhdr_raw_image_t* gm, bool scaled) {
-  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
-  if (!hdr || !cfg || !base_ycc || !md || !gm || !gm->planes[0]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
+// What every intent format's request is held to behind its own format check: the scale factor, the HDR gamut and transfer (what
+// uhdr_hip_tone_map_dev accepts) and base planes that hold the image -- chroma_halved: the chroma planes are 4:2:0
+static uhdr_error_info_t api0_front_request(const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg, const uhdr_raw_image_t* base, bool scaled,
+                                            bool chroma_halved) {
+  if (scaled) UHDR_TRY(check_scaled_request(hdr, cfg, false));
+  if (hdr->cg < UHDR_CG_BT_709 || hdr->cg > UHDR_CG_BT_2100)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "No implementation available for color gamut %d", hdr->cg);
+  if (hdr->ct < UHDR_CT_LINEAR || hdr->ct > UHDR_CT_SRGB)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "No implementation available for color transfer %d", hdr->ct);
+  for (int i = 0; i < 3; i++) {
+    if (!base->planes[i]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for base image plane %d", i);
+    const unsigned need = (i && chroma_halved) ? (hdr->w + 1) / 2 : hdr->w;
+    if (base->stride[i] < need) return err_status(UHDR_CODEC_INVALID_PARAM, "base image stride (%u) cannot be less than width (%u)", base->stride[i], need);
+  }
+  return ok_status();
+}
+
+// ---- the RGB piece: RGBA1010102 / RGBA half float intents, base image YCbCr 4:4:4, an optional RGBA8888 rendition ----
+static uhdr_error_info_t api0_rgb_request(const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg, const uhdr_raw_image_t* sdr_rgba,
+                                          const uhdr_raw_image_t* base_ycc, bool scaled) {
   if (hdr->fmt != UHDR_IMG_FMT_32bppRGBA1010102 && hdr->fmt != UHDR_IMG_FMT_64bppRGBAHalfFloat)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 front end takes UHDR_IMG_FMT_32bppRGBA1010102 or UHDR_IMG_FMT_64bppRGBAHalfFloat "
                       "(the inputs toneMap renders to RGBA8888). Received %d", hdr->fmt);
   if (!scaled && cfg->map_dimension_scale_factor != 1)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 front end needs a full-resolution gain map (scale factor 1), received %d; "
                       "use tone_map + generate_gainmap + convert_raw_input_to_ycbcr", cfg->map_dimension_scale_factor);
-  if (scaled) UHDR_TRY(check_scaled_request(hdr, cfg, false));
-  const bool sub = cfg->map_dimension_scale_factor != 1;  // the scaled kernel
-  if (hdr->cg < UHDR_CG_BT_709 || hdr->cg > UHDR_CG_BT_2100)
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "No implementation available for color gamut %d", hdr->cg);
-  if (hdr->ct < UHDR_CT_LINEAR || hdr->ct > UHDR_CT_SRGB)
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "No implementation available for color transfer %d", hdr->ct);
-  for (int i = 0; i < 3; i++) {
-    if (!base_ycc->planes[i]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for base image plane %d", i);
-    if (base_ycc->stride[i] < hdr->w) return err_status(UHDR_CODEC_INVALID_PARAM, "base image stride (%u) cannot be less than width (%u)", base_ycc->stride[i], hdr->w);
-  }
+  UHDR_TRY(api0_front_request(hdr, cfg, base_ycc, scaled, false));
   if (sdr_rgba && sdr_rgba->planes[0] && sdr_rgba->stride[0] < hdr->w)
     return err_status(UHDR_CODEC_INVALID_PARAM, "sdr stride (%u) cannot be less than width (%u)", sdr_rgba->stride[0], hdr->w);
-  HIP_TRY(hipSetDevice(c->device));
-  // the SDR rendition toneMap would hand to generateGainMap: RGBA8888, Display-P3, sRGB, full range
-  uhdr_raw_image_t sdr_desc;
-  memset(&sdr_desc, 0, sizeof sdr_desc);
-  if (sdr_rgba) sdr_desc = *sdr_rgba;
-  sdr_desc.fmt = UHDR_IMG_FMT_32bppRGBA8888; sdr_desc.cg = UHDR_CG_DISPLAY_P3; sdr_desc.ct = UHDR_CT_SRGB; sdr_desc.range = UHDR_CR_FULL_RANGE;
-  sdr_desc.w = hdr->w; sdr_desc.h = hdr->h;
-  if (!sdr_desc.planes[0]) sdr_desc.stride[0] = hdr->w;
-  if (sdr_rgba) { sdr_rgba->fmt = sdr_desc.fmt; sdr_rgba->cg = sdr_desc.cg; sdr_rgba->ct = sdr_desc.ct; sdr_rgba->range = sdr_desc.range; sdr_rgba->w = hdr->w; sdr_rgba->h = hdr->h; }
-  FusedParams p;
-  UHDR_TRY(fill_tone_map_params(c, hdr, &p.tm));
-  p.tm.sdr = view_mut_of(&sdr_desc);
-  int use_base_cg = 1;
-  float hdr_white_nits;
-  UHDR_TRY(fill_gen_params(c, &sdr_desc, hdr, cfg, &p.gen, &use_base_cg, &hdr_white_nits, /*sdr_in_registers=*/true));
+  return ok_status();
+}
+// the SDR rendition toneMap would hand to generateGainMap: RGBA8888, Display-P3, sRGB, full range (stored only where the caller gave a plane)
+static void api0_rgb_rendition(const uhdr_raw_image_t* hdr, uhdr_raw_image_t* sdr_rgba, uhdr_raw_image_t* sdr_desc) {
+  memset(sdr_desc, 0, sizeof *sdr_desc);
+  if (sdr_rgba) *sdr_desc = *sdr_rgba;
+  sdr_desc->fmt = UHDR_IMG_FMT_32bppRGBA8888; sdr_desc->cg = UHDR_CG_DISPLAY_P3; sdr_desc->ct = UHDR_CT_SRGB; sdr_desc->range = UHDR_CR_FULL_RANGE;
+  sdr_desc->w = hdr->w; sdr_desc->h = hdr->h;
+  if (!sdr_desc->planes[0]) sdr_desc->stride[0] = hdr->w;
+  if (sdr_rgba) { sdr_rgba->fmt = sdr_desc->fmt; sdr_rgba->cg = sdr_desc->cg; sdr_rgba->ct = sdr_desc->ct; sdr_rgba->range = sdr_desc->range; sdr_rgba->w = hdr->w; sdr_rgba->h = hdr->h; }
+}
+// convert_raw_input_to_ycbcr's side of the kernel: the sRGB-of-byte LUT, the base image and its coefficients, and the layout the scaled kernel takes
+static uhdr_error_info_t api0_rgb_base(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* base_ycc, FusedParams* p) {
   UHDR_TRY(upload_lut(&c->d_srgb_of_byte, host::srgb_inv_oetf_of_byte(), c->stream));
-  p.gen.srgb_of_byte = c->d_srgb_of_byte;
-  fill_gainmap_desc(hdr, p.gen, gm);
-  if (gm->stride[0] < gm->w) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap stride (%u) cannot be less than its width (%u)", gm->stride[0], gm->w);
+  p->gen.srgb_of_byte = c->d_srgb_of_byte;
   base_ycc->fmt = UHDR_IMG_FMT_24bppYCbCr444; base_ycc->cg = UHDR_CG_DISPLAY_P3; base_ycc->ct = UHDR_CT_SRGB; base_ycc->range = UHDR_CR_FULL_RANGE;
   base_ycc->w = hdr->w; base_ycc->h = hdr->h;
-  p.ycc = view_mut_of(base_ycc);
-  p.base_k = host::rgb2yuv_coeffs(UHDR_CG_DISPLAY_P3);
-  if (sub && !encode_api0_fused_scaled_layout_ok(p))
+  p->ycc = view_mut_of(base_ycc);
+  p->base_k = host::rgb2yuv_coeffs(UHDR_CG_DISPLAY_P3);
+  if (cfg->map_dimension_scale_factor != 1 && !encode_api0_fused_scaled_layout_ok(*p))
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 front end at scale factor %d reads and writes vectors: a 16-byte aligned intent and rendition, "
                       "4-byte aligned base planes, strides that are multiples of 4; use the operators", cfg->map_dimension_scale_factor);
+  return ok_status();
+}
+
+// ---- the P010 piece: toneMap (P010 -> YCbCr 4:2:0) + generateGainMap ----
+// jpegr.cpp:179-244 compresses the tone mapper's 4:2:0 planes as they are, so the base image leaves here in the form the base JPEG's
+// FDCT takes.  Declines (UHDR_CODEC_UNSUPPORTED_FEATURE, before anything is launched) what the quad kernel cannot read with its vector
+// accesses; the caller then runs uhdr_hip_tone_map_dev + uhdr_hip_generate_gainmap_dev.
+static uhdr_error_info_t api0_p010_request(const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* base_ycc420, bool scaled) {
+  if (hdr->fmt != UHDR_IMG_FMT_24bppYCbCrP010)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused P010 API-0 front end takes UHDR_IMG_FMT_24bppYCbCrP010. Received %d", hdr->fmt);
+  if (!scaled && cfg->map_dimension_scale_factor != 1)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused P010 API-0 front end needs a full-resolution gain map (scale factor 1), received %d; "
+                      "use tone_map + generate_gainmap", cfg->map_dimension_scale_factor);
+  UHDR_TRY(api0_front_request(hdr, cfg, base_ycc420, scaled, true));
+  UHDR_TRY(validate_image(hdr, "hdr intent"));
+  // the SDR rendition uhdr_hip_tone_map_dev would hand to generateGainMap: YCbCr 4:2:0, Display-P3, sRGB, full range
+  base_ycc420->fmt = UHDR_IMG_FMT_12bppYCbCr420; base_ycc420->cg = UHDR_CG_DISPLAY_P3; base_ycc420->ct = UHDR_CT_SRGB; base_ycc420->range = UHDR_CR_FULL_RANGE;
+  base_ycc420->w = hdr->w; base_ycc420->h = hdr->h;
+  if (!encode_api0_p010_layout_ok(view_of(hdr), view_of(base_ycc420)))
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused P010 API-0 front end reads quads with vector loads: even dimensions, even strides, a 4-byte aligned "
+                      "luma and chroma base of the HDR intent and a 2-byte aligned luma base of the base image; use tone_map + generate_gainmap");
+  return ok_status();
+}
+
+// The driver behind uhdr_hip_encode_api0_fused_dev, _fused_scaled_dev (p010 == false; sdr_rgba optional) and uhdr_hip_encode_api0_p010_fused_dev,
+// _p010_fused_scaled_dev (p010 == true; no sdr_rgba: the base image IS the rendition).  scaled: the entry point also takes scale factors 2 and 4.
+// A request's checks run in the order: arguments, the format's request, the gain-map side, the map's stride, the RGB piece's layout.
+static uhdr_error_info_t encode_api0_front(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* sdr_rgba,
+                                           uhdr_raw_image_t* base, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm, bool p010, bool scaled) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  if (!hdr || !cfg || !base || !md || !gm || !gm->planes[0]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
+  UHDR_TRY(p010 ? api0_p010_request(hdr, cfg, base, scaled) : api0_rgb_request(hdr, cfg, sdr_rgba, base, scaled));
+  HIP_TRY(hipSetDevice(c->device));
+  uhdr_raw_image_t sdr_desc;
+  const uhdr_raw_image_t* rendition = base;  // what generateGainMap takes as the SDR side (the pixels themselves stay in registers)
+  if (!p010) {
+    api0_rgb_rendition(hdr, sdr_rgba, &sdr_desc);
+    rendition = &sdr_desc;
+  }
+  FusedParams p;
+  memset(&p.ycc, 0, sizeof p.ycc);
+  memset(&p.base_k, 0, sizeof p.base_k);
+  UHDR_TRY(fill_tone_map_params(c, hdr, &p.tm));
+  p.tm.sdr = view_mut_of(rendition);
+  int use_base_cg = 1;
+  float hdr_white_nits;
+  UHDR_TRY(fill_gen_params(c, rendition, hdr, cfg, &p.gen, &use_base_cg, &hdr_white_nits, /*sdr_in_registers=*/true));
+  fill_gainmap_desc(hdr, p.gen, gm);
+  if (gm->stride[0] < gm->w) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap stride (%u) cannot be less than its width (%u)", gm->stride[0], gm->w);
+  if (!p010) UHDR_TRY(api0_rgb_base(c, hdr, cfg, base, &p));
   if (cfg->preset == UHDR_USAGE_REALTIME) {  // one pass: jpegr.cpp:724-737
-    for (int i = 0; i < 3; i++) {
-      md->max_content_boost[i] = hdr_white_nits / 203.0f;
-      md->min_content_boost[i] = 1.0f;
-      md->gamma[i] = cfg->gamma;
-      md->offset_sdr[i] = 0.0f;
-      md->offset_hdr[i] = 0.0f;
-    }
-    md->hdr_capacity_min = 1.0f;
-    md->hdr_capacity_max = cfg->target_disp_peak_nits != -1.0f ? cfg->target_disp_peak_nits / 203.0f : md->max_content_boost[0];
-    md->use_base_cg = use_base_cg;
-    p.gen.min_boost = md->min_content_boost[0];
-    p.gen.max_boost = md->max_content_boost[0];
-    p.gen.log2min = log2f(md->min_content_boost[0]);
-    p.gen.log2max = log2f(md->max_content_boost[0]);
-    p.gen.log2_range = (double)(p.gen.log2max - p.gen.log2min);
-    p.gen.log2_range_rcp = 1.0 / p.gen.log2_range;
-    UHDR_TRY(gain_step_table(c, p.gen, &p.gen.gain8));
+    UHDR_TRY(fill_onepass_range(c, cfg, hdr_white_nits, use_base_cg, &p.gen, md));
     p.gen.out = (uint8_t*)gm->planes[0];
     p.gen.out_stride = gm->stride[0];
+    const bool sub = cfg->map_dimension_scale_factor != 1;  // the scaled kernel
     ProfScope ps(c, "encode_api0_fused");
-    if (sub) HIP_TRY(launch_encode_api0_fused_scaled(p, c->stream));
-    else HIP_TRY(launch_encode_api0_fused(p, false, nullptr, c->stream));
+    if (p010) HIP_TRY(sub ? launch_encode_api0_p010_fused_scaled(p, c->stream) : launch_encode_api0_p010_fused(p, false, nullptr, c->stream));
+    else HIP_TRY(sub ? launch_encode_api0_fused_scaled(p, c->stream) : launch_encode_api0_fused(p, false, nullptr, c->stream));
     return ok_status();
   }
   const size_t nfl = (size_t)p.gen.map_w * p.gen.map_h * (p.gen.multichannel ? 3 : 1);
@@ -208,7 +244,7 @@ static uhdr_error_info_t encode_api0_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   int grid = 0;
   {
     ProfScope ps(c, "encode_api0_fused");
-    HIP_TRY(launch_encode_api0_fused(p, true, &grid, c->stream));
+    HIP_TRY(p010 ? launch_encode_api0_p010_fused(p, true, &grid, c->stream) : launch_encode_api0_fused(p, true, &grid, c->stream));
   }
   UHDR_TRY(two_pass_tail(c, p.gen, grid, cfg, gm));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -220,130 +256,124 @@ static uhdr_error_info_t encode_api0_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
 uhdr_error_info_t uhdr_hip_encode_api0_fused_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
                                                  uhdr_raw_image_t* sdr_rgba, uhdr_raw_image_t* base_ycc, uhdr_gainmap_metadata_t* md,
                                                  uhdr_raw_image_t* gm) {
-  return encode_api0_fused_impl(c, hdr, cfg, sdr_rgba, base_ycc, md, gm, false);
+  return encode_api0_front(c, hdr, cfg, sdr_rgba, base_ycc, md, gm, /*p010=*/false, /*scaled=*/false);
 }
 uhdr_error_info_t uhdr_hip_encode_api0_fused_scaled_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
                                                         uhdr_raw_image_t* sdr_rgba, uhdr_raw_image_t* base_ycc, uhdr_gainmap_metadata_t* md,
                                                         uhdr_raw_image_t* gm) {
-  return encode_api0_fused_impl(c, hdr, cfg, sdr_rgba, base_ycc, md, gm, true);
-}
-
-// -------------------------------------------------------------------------------------------------
-// API-0 front end fused for P010 intents: toneMap (P010 -> YCbCr 4:2:0) + generateGainMap in one pass
-// -------------------------------------------------------------------------------------------------
-// jpegr.cpp:179-244 compresses the tone mapper's 4:2:0 planes as they are, so the base image leaves here in the form the base JPEG's
-// FDCT takes.  Declines (UHDR_CODEC_UNSUPPORTED_FEATURE, before anything is launched) what the quad kernel cannot read with its vector
-// accesses; the caller then runs uhdr_hip_tone_map_dev + uhdr_hip_generate_gainmap_dev.
-// scaled == false: uhdr_hip_encode_api0_p010_fused_dev; true: uhdr_hip_encode_api0_p010_fused_scaled_dev, which also takes scale factors 2 and 4
-static uhdr_error_info_t encode_api0_p010_fused_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
-                                                     uhdr_raw_image_t* base_ycc420, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm, bool scaled) {
-  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
-  if (!hdr || !cfg || !base_ycc420 || !md || !gm || !gm->planes[0]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
-  if (hdr->fmt != UHDR_IMG_FMT_24bppYCbCrP010)
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused P010 API-0 front end takes UHDR_IMG_FMT_24bppYCbCrP010. Received %d", hdr->fmt);
-  if (scaled) UHDR_TRY(check_scaled_request(hdr, cfg, false));
-  const bool sub = scaled && cfg->map_dimension_scale_factor != 1;  // the scaled kernel
-  if (!scaled && cfg->map_dimension_scale_factor != 1)
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused P010 API-0 front end needs a full-resolution gain map (scale factor 1), received %d; "
-                      "use tone_map + generate_gainmap", cfg->map_dimension_scale_factor);
-  if (hdr->cg < UHDR_CG_BT_709 || hdr->cg > UHDR_CG_BT_2100)  // (what uhdr_hip_tone_map_dev accepts for P010)
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "No implementation available for color gamut %d", hdr->cg);
-  if (hdr->ct < UHDR_CT_LINEAR || hdr->ct > UHDR_CT_SRGB)
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "No implementation available for color transfer %d", hdr->ct);
-  for (int i = 0; i < 3; i++) {
-    if (!base_ycc420->planes[i]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for base image plane %d", i);
-    const unsigned need = i ? (hdr->w + 1) / 2 : hdr->w;
-    if (base_ycc420->stride[i] < need) return err_status(UHDR_CODEC_INVALID_PARAM, "base image stride (%u) cannot be less than width (%u)", base_ycc420->stride[i], need);
-  }
-  UHDR_TRY(validate_image(hdr, "hdr intent"));
-  // the SDR rendition uhdr_hip_tone_map_dev would hand to generateGainMap: YCbCr 4:2:0, Display-P3, sRGB, full range
-  base_ycc420->fmt = UHDR_IMG_FMT_12bppYCbCr420; base_ycc420->cg = UHDR_CG_DISPLAY_P3; base_ycc420->ct = UHDR_CT_SRGB; base_ycc420->range = UHDR_CR_FULL_RANGE;
-  base_ycc420->w = hdr->w; base_ycc420->h = hdr->h;
-  if (!encode_api0_p010_layout_ok(view_of(hdr), view_of(base_ycc420)))
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused P010 API-0 front end reads quads with vector loads: even dimensions, even strides, a 4-byte aligned "
-                      "luma and chroma base of the HDR intent and a 2-byte aligned luma base of the base image; use tone_map + generate_gainmap");
-  HIP_TRY(hipSetDevice(c->device));
-  FusedParams p;
-  memset(&p.ycc, 0, sizeof p.ycc);
-  memset(&p.base_k, 0, sizeof p.base_k);
-  UHDR_TRY(fill_tone_map_params(c, hdr, &p.tm));
-  p.tm.sdr = view_mut_of(base_ycc420);
-  int use_base_cg = 1;
-  float hdr_white_nits;
-  UHDR_TRY(fill_gen_params(c, base_ycc420, hdr, cfg, &p.gen, &use_base_cg, &hdr_white_nits, /*sdr_in_registers=*/true));
-  fill_gainmap_desc(hdr, p.gen, gm);
-  if (gm->stride[0] < gm->w) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap stride (%u) cannot be less than its width (%u)", gm->stride[0], gm->w);
-  if (cfg->preset == UHDR_USAGE_REALTIME) {  // one pass: jpegr.cpp:724-737
-    for (int i = 0; i < 3; i++) {
-      md->max_content_boost[i] = hdr_white_nits / 203.0f;
-      md->min_content_boost[i] = 1.0f;
-      md->gamma[i] = cfg->gamma;
-      md->offset_sdr[i] = 0.0f;
-      md->offset_hdr[i] = 0.0f;
-    }
-    md->hdr_capacity_min = 1.0f;
-    md->hdr_capacity_max = cfg->target_disp_peak_nits != -1.0f ? cfg->target_disp_peak_nits / 203.0f : md->max_content_boost[0];
-    md->use_base_cg = use_base_cg;
-    p.gen.min_boost = md->min_content_boost[0];
-    p.gen.max_boost = md->max_content_boost[0];
-    p.gen.log2min = log2f(md->min_content_boost[0]);
-    p.gen.log2max = log2f(md->max_content_boost[0]);
-    p.gen.log2_range = (double)(p.gen.log2max - p.gen.log2min);
-    p.gen.log2_range_rcp = 1.0 / p.gen.log2_range;
-    UHDR_TRY(gain_step_table(c, p.gen, &p.gen.gain8));
-    p.gen.out = (uint8_t*)gm->planes[0];
-    p.gen.out_stride = gm->stride[0];
-    ProfScope ps(c, "encode_api0_fused");
-    if (sub) HIP_TRY(launch_encode_api0_p010_fused_scaled(p, c->stream));
-    else HIP_TRY(launch_encode_api0_p010_fused(p, false, nullptr, c->stream));
-    return ok_status();
-  }
-  const size_t nfl = (size_t)p.gen.map_w * p.gen.map_h * (p.gen.multichannel ? 3 : 1);
-  UHDR_TRY(ensure(c->scratch[7], nfl * sizeof(float)));
-  UHDR_TRY(ensure(c->minmax, (6 + 2048 * 6) * sizeof(float)));
-  p.gen.gain_log2 = (float*)c->scratch[7].p;
-  p.gen.minmax = (float*)c->minmax.p;
-  int grid = 0;
-  {
-    ProfScope ps(c, "encode_api0_fused");
-    HIP_TRY(launch_encode_api0_p010_fused(p, true, &grid, c->stream));
-  }
-  UHDR_TRY(two_pass_tail(c, p.gen, grid, cfg, gm));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  float mm[6];
-  memcpy(mm, c->h_mm, sizeof mm);
-  note_table_stats(c, cfg);
-  return generate_gainmap_finalize_md(cfg, hdr->ct, use_base_cg, mm, md);
+  return encode_api0_front(c, hdr, cfg, sdr_rgba, base_ycc, md, gm, /*p010=*/false, /*scaled=*/true);
 }
 uhdr_error_info_t uhdr_hip_encode_api0_p010_fused_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
                                                       uhdr_raw_image_t* base_ycc420, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
-  return encode_api0_p010_fused_impl(c, hdr, cfg, base_ycc420, md, gm, false);
+  return encode_api0_front(c, hdr, cfg, nullptr, base_ycc420, md, gm, /*p010=*/true, /*scaled=*/false);
 }
 uhdr_error_info_t uhdr_hip_encode_api0_p010_fused_scaled_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
                                                              uhdr_raw_image_t* base_ycc420, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
-  return encode_api0_p010_fused_impl(c, hdr, cfg, base_ycc420, md, gm, true);
+  return encode_api0_front(c, hdr, cfg, nullptr, base_ycc420, md, gm, /*p010=*/true, /*scaled=*/true);
+}
+
+// -------------------------------------------------------------------------------------------------
+// What the fused encode drivers below share: table check, coefficient arrays, scan descriptions, the scans' way to the host
+// -------------------------------------------------------------------------------------------------
+static uhdr_error_info_t check_quant_tables(const uint16_t qt_base[2][64], const uint16_t qt_map[2][64]) {
+  for (int t = 0; t < 2; t++)
+    for (int i = 0; i < 64; i++)
+      if (qt_base[t][i] == 0 || qt_base[t][i] > 255 || qt_map[t][i] == 0 || qt_map[t][i] > 255)
+        return err_status(UHDR_CODEC_INVALID_PARAM, "quantization table entry %d out of baseline range", i);
+  return ok_status();
+}
+
+// n (at most 6) coefficient arrays of nblocks[i] blocks each, 256-byte aligned, one behind the other in `buf`
+static uhdr_error_info_t carve_coef_arrays(DeviceBuf& buf, const size_t* nblocks, int n, int16_t** coef) {
+  size_t off[6], total = 0;
+  for (int i = 0; i < n; i++) { off[i] = total; total += (nblocks[i] * 128 + 255) & ~(size_t)255; }
+  UHDR_TRY(ensure(buf, total));
+  for (int i = 0; i < n; i++) coef[i] = (int16_t*)((uint8_t*)buf.p + off[i]);
+  return ok_status();
+}
+
+// The scan of a w x h image of whole blocks.  chroma_div: a chroma block's width in luma samples -- 8: every component 1x1 (4:4:4, a map);
+// 16: 4:2:0, the luma component 2x2
+static void fill_scan(uhdr_hip_jpeg_scan_t* s, unsigned w, unsigned h, int components, unsigned chroma_div, int16_t* const* coef) {
+  memset(s, 0, sizeof *s);
+  s->num_components = components;
+  s->w = w; s->h = h;
+  for (int i = 0; i < components; i++) {
+    s->coef[i] = coef[i];
+    s->blocks_w[i] = (int)(i ? w / chroma_div : w / 8);
+    s->blocks_h[i] = (int)(i ? h / chroma_div : h / 8);
+    s->h_samp[i] = s->v_samp[i] = (i || chroma_div == 8) ? 1 : 2;
+  }
+}
+
+// Both scans Huffman-coded at once (round 5: the base image on this context's stream, the map on the auxiliary one) into the two device
+// buffers the caller names, and only the bytes come down
+static uhdr_error_info_t scans_to_host(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_scan_t* sb, const uhdr_hip_jpeg_scan_t* sm, DeviceBuf& dev_base, DeviceBuf& dev_map,
+                                       uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
+  if (base_capacity > 0xFFFFFFF0u) base_capacity = 0xFFFFFFF0u;
+  if (map_capacity > 0xFFFFFFF0u) map_capacity = 0xFFFFFFF0u;
+  UHDR_TRY(ensure(dev_base, base_capacity + 64));
+  UHDR_TRY(ensure(dev_map, map_capacity + 64));
+  size_t nbs = 0, nms = 0;
+  const uhdr_error_info_t e2 = uhdr_hip_huffman_encode2_dev(c, sb, (uint8_t*)dev_base.p, base_capacity, &nbs, sm, (uint8_t*)dev_map.p, map_capacity, &nms);
+  *base_bytes = nbs;
+  *map_bytes = nms;
+  if (e2.error_code != UHDR_CODEC_OK) return e2;
+  HIP_TRY(hipMemcpyAsync(base_scan, dev_base.p, nbs, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(map_scan, dev_map.p, nms, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ok_status();
 }
 
 // -------------------------------------------------------------------------------------------------
 // API-1 encode chain fused (encode_api1_fused.hip): pass 1 -> range + tables -> map blocks; base blocks
 // -------------------------------------------------------------------------------------------------
+// What an API-1 entry point asks of the two drivers below
+enum Api1Route : unsigned {
+  kApi1Dev = 1,      // (scans) the intents and the two scans are device buffers
+  kApi1AnySdr = 2,   // an RGBA8888 SDR intent is taken as well as a 4:2:0 one
+  kApi1Onepass = 4,  // the real-time preset is taken too
+};
+
+// What the chain declines whatever else the request holds -- the SDR intent's format and MCU rule, the preset, gamma -- stated once: the
+// scans entry points ask before 37 MB go up for nothing.  whole_image: h == 0 is declined with the dimensions (the chain lets an empty stripe through)
+static uhdr_error_info_t check_api1_request(const uhdr_raw_image_t* sdr, const uhdr_hip_encode_cfg_t* cfg, unsigned route, bool whole_image) {
+  const bool empty = sdr->w == 0 || (whole_image && sdr->h == 0);
+  if ((route & kApi1AnySdr) && sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888) {
+    if (sdr->w % 8 || sdr->h % 8 || empty)
+      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_32bppRGBA8888 SDR intent whose dimensions are multiples of 8 "
+                        "(received %ux%u); use the operators", sdr->w, sdr->h);
+  } else if ((route & kApi1AnySdr) && sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420) {
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_12bppYCbCr420 or UHDR_IMG_FMT_32bppRGBA8888 SDR intent "
+                      "(received format %d); use the operators", sdr->fmt);
+  } else if (sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420 || sdr->w % 16 || sdr->h % 16 || empty) {
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_12bppYCbCr420 base image whose dimensions are multiples of 16 "
+                      "(received format %d, %ux%u); use the operators", sdr->fmt, sdr->w, sdr->h);
+  }
+  if (cfg->preset == UHDR_USAGE_REALTIME && !(route & kApi1Onepass))
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain is the two-pass (best quality) encode; one pass: generate_gainmap + fdct_quant");
+  if (cfg->gamma != 1.0f) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs gain-map gamma 1 (received %f); use the operators", cfg->gamma);
+  return ok_status();
+}
+
+
 // With a communicator on the context (uhdr_hip_comm_init / _init_custom) the images are this rank's ROW STRIPE and the extrema
 // are merged across ranks between the passes, exactly as in uhdr_hip_generate_gainmap_striped_dev: reduce -> ONE all-reduce(min)
 // over {min, -max} -> finalize + tables.  Every rank takes part in that exchange whatever happens locally (a rank that
 // failed validation, or whose stripe is empty -- h == 0 --, contributes the identity), and reports its error afterwards.
 //
-// any_sdr (uhdr_hip_encode_api1_fused_any_dev): a packed RGBA8888 SDR intent is taken as well -- the other form API-1 accepts (jpegr.cpp:247-291),
+// kApi1AnySdr (uhdr_hip_encode_api1_fused_any_dev): a packed RGBA8888 SDR intent is taken as well -- the other form API-1 accepts (jpegr.cpp:247-291),
 // whose base image is YCbCr 4:4:4: the gain-map passes read it as they are (pass 1 fetches RGBA8888), launch_base_blocks_rgba is the base
 // launch (three (w / 8) x (h / 8) coefficient arrays), dimensions are multiples of 8, whole images only.
 static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
                                                 const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
                                                 const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
-                                                const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm, bool any_sdr,
-                                                bool onepass = false) {
+                                                const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm, unsigned route) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   HIP_TRY(hipSetDevice(c->device));
   const bool striped = c->comm != nullptr || c->comm_custom;
-  const bool rgba = any_sdr && sdr && sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888;
+  const bool onepass = (route & kApi1Onepass) != 0;
+  const bool rgba = (route & kApi1AnySdr) && sdr && sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888;
   // onepass (uhdr_hip_encode_api1_fused_onepass_dev): the real-time preset is taken too, as TWO launches -- launch_map_blocks_onepass (the
   // range is known beforehand, jpegr.cpp:724-737: no ratio plane, no reduction, no range read-back) and the base image's blocks
   const bool one = onepass && cfg && cfg->preset == UHDR_USAGE_REALTIME;
@@ -359,23 +389,8 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   bool convert = false, empty = false;
   auto prepare = [&]() -> uhdr_error_info_t {
     if (!sdr || !hdr || !cfg || !qt_base || !qt_map || !blocks || !md) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
-    if (rgba) {
-      if (sdr->w % 8 || sdr->h % 8 || sdr->w == 0)
-        return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_32bppRGBA8888 SDR intent whose dimensions are multiples of 8 "
-                          "(received %ux%u); use the operators", sdr->w, sdr->h);
-    } else if (any_sdr && sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420) {
-      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_12bppYCbCr420 or UHDR_IMG_FMT_32bppRGBA8888 SDR intent "
-                        "(received format %d); use the operators", sdr->fmt);
-    } else if (sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420 || sdr->w % 16 || sdr->h % 16 || sdr->w == 0) {
-      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_12bppYCbCr420 base image whose dimensions are multiples of 16 "
-                        "(received format %d, %ux%u); use the operators", sdr->fmt, sdr->w, sdr->h);
-    }
-    if (cfg->preset == UHDR_USAGE_REALTIME && !onepass) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain is the two-pass (best quality) encode; one pass: generate_gainmap + fdct_quant");
-    if (cfg->gamma != 1.0f) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs gain-map gamma 1 (received %f); use the operators", cfg->gamma);
-    for (int t = 0; t < 2; t++)
-      for (int i = 0; i < 64; i++)
-        if (qt_base[t][i] == 0 || qt_base[t][i] > 255 || qt_map[t][i] == 0 || qt_map[t][i] > 255)
-          return err_status(UHDR_CODEC_INVALID_PARAM, "quantization table entry %d out of baseline range", i);
+    UHDR_TRY(check_api1_request(sdr, cfg, route, /*whole_image=*/false));
+    UHDR_TRY(check_quant_tables(qt_base, qt_map));
     if (striped && sdr->h == 0 && hdr->h == 0) {  // a rank without rows: nothing to launch, the identity to contribute
       empty = true;
       use_base_cg = !(hdr->cg == UHDR_CG_BT_2100 || (hdr->cg == UHDR_CG_DISPLAY_P3 && sdr->cg != UHDR_CG_BT_2100)) || sdr->cg == hdr->cg;
@@ -564,19 +579,19 @@ uhdr_error_info_t uhdr_hip_encode_api1_fused_dev(uhdr_hip_ctx_t* c, const uhdr_r
                                                  const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
                                                  const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
                                                  const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
-  return encode_api1_fused_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, blocks, md, gm, false);
+  return encode_api1_fused_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, blocks, md, gm, kApi1Dev);
 }
 uhdr_error_info_t uhdr_hip_encode_api1_fused_any_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
                                                      const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
                                                      const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
                                                      const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
-  return encode_api1_fused_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, blocks, md, gm, true);
+  return encode_api1_fused_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, blocks, md, gm, kApi1Dev | kApi1AnySdr);
 }
 uhdr_error_info_t uhdr_hip_encode_api1_fused_onepass_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
                                                          const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
                                                          const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
                                                          const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
-  return encode_api1_fused_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, blocks, md, gm, true, true);
+  return encode_api1_fused_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, blocks, md, gm, kApi1Dev | kApi1AnySdr | kApi1Onepass);
 }
 
 // JpegR::encodeJPEGR API-1 (jpegr.cpp:253-316) from its two raw intents to its two entropy-coded scans in ONE entry point: the
@@ -585,84 +600,13 @@ uhdr_error_info_t uhdr_hip_encode_api1_fused_onepass_dev(uhdr_hip_ctx_t* c, cons
 static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
                                                 uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
                                                 uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
-                                                size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, bool dev = false, bool any_sdr = false,
-                                                bool onepass = false);
-// ... and on DEVICE-resident intents, into DEVICE buffers (round 6): one call per direction of the round trip, so that no binding
-// layer sits between the stages (a Python caller's 30-100 us between two entry points were a third of a 4K round trip)
-uhdr_error_info_t uhdr_hip_encode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
-                                                 uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
-                                                 uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
-                                                 size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
-  return encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
-                                map_bytes, true);
-}
-uhdr_error_info_t uhdr_hip_encode_api1_scans_any_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
-                                                     uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
-                                                     uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
-                                                     size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
-  return encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
-                                map_bytes, true, true);
-}
-uhdr_error_info_t uhdr_hip_encode_api1_scans_any(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
-                                                 uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
-                                                 uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
-                                                 size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const uhdr_error_info_t r = encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes,
-                                                     map_scan, map_capacity, map_bytes, false, true);
-  if (c) c->stats.last_encode_api1_scans_ns = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-  return r;
-}
-// ... and with the one-pass (real-time) preset as well: what the _any siblings run for UHDR_USAGE_BEST_QUALITY, the two launches of
-// uhdr_hip_encode_api1_fused_onepass_dev in front of the same entropy stage for UHDR_USAGE_REALTIME
-uhdr_error_info_t uhdr_hip_encode_api1_scans_onepass_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
-                                                         uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
-                                                         uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
-                                                         size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
-  return encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
-                                map_bytes, true, true, true);
-}
-uhdr_error_info_t uhdr_hip_encode_api1_scans_onepass(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
-                                                     uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
-                                                     uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
-                                                     size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const uhdr_error_info_t r = encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes,
-                                                     map_scan, map_capacity, map_bytes, false, true, true);
-  if (c) c->stats.last_encode_api1_scans_ns = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-  return r;
-}
-uhdr_error_info_t uhdr_hip_encode_api1_scans(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
-                                             uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
-                                             uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
-                                             size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const uhdr_error_info_t r = encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes,
-                                                     map_scan, map_capacity, map_bytes);
-  if (c) c->stats.last_encode_api1_scans_ns = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-  return r;
-}
-static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
-                                                uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
-                                                uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
-                                                size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, bool dev, bool any_sdr, bool onepass) {
+                                                size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned route) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!sdr || !hdr || !cfg || !qt_base || !qt_map || !md || !base_scan || !map_scan || !base_bytes || !map_bytes)
     return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
-  // what the fused chain would decline is declined before 37 MB go up for nothing (the same conditions, uhdr_hip_encode_api1_fused_dev)
-  const bool rgba = any_sdr && sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888;  // base image 4:4:4: a 1x1 / 1x1 / 1x1 scan
-  if (rgba) {
-    if (sdr->w % 8 || sdr->h % 8 || sdr->w == 0 || sdr->h == 0)
-      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_32bppRGBA8888 SDR intent whose dimensions are multiples of 8 "
-                        "(received %ux%u); use the operators", sdr->w, sdr->h);
-  } else if (any_sdr && sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420) {
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_12bppYCbCr420 or UHDR_IMG_FMT_32bppRGBA8888 SDR intent "
-                      "(received format %d); use the operators", sdr->fmt);
-  } else if (sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420 || sdr->w % 16 || sdr->h % 16 || sdr->w == 0 || sdr->h == 0)
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_12bppYCbCr420 base image whose dimensions are multiples of 16 "
-                      "(received format %d, %ux%u); use the operators", sdr->fmt, sdr->w, sdr->h);
-  if (cfg->preset == UHDR_USAGE_REALTIME && !onepass) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain is the two-pass (best quality) encode");
-  if (cfg->gamma != 1.0f) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs gain-map gamma 1 (received %f)", cfg->gamma);
+  UHDR_TRY(check_api1_request(sdr, cfg, route, /*whole_image=*/true));
+  const bool dev = (route & kApi1Dev) != 0;
+  const bool rgba = (route & kApi1AnySdr) && sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888;  // base image 4:4:4: a 1x1 / 1x1 / 1x1 scan
   const int scale = cfg->map_dimension_scale_factor;
   if (scale < 1 || sdr->w / (unsigned)scale == 0 || sdr->h / (unsigned)scale == 0 || (sdr->w / (unsigned)scale) % 8 || (sdr->h / (unsigned)scale) % 8)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs map dimensions that are multiples of 8 (scale factor %d on %ux%u)", scale, sdr->w, sdr->h);
@@ -687,39 +631,19 @@ static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   }
   // coefficient arrays: base Y, Cb, Cr, then the map's 1 or 3 components; 256-byte aligned
   const unsigned cdiv = rgba ? 8 : 16;  // a chroma block's width in luma samples
-  const size_t nb[3] = {(size_t)(w / 8) * (h / 8), (size_t)(w / cdiv) * (h / cdiv), (size_t)(w / cdiv) * (h / cdiv)};
-  const size_t nm = (size_t)(mw / 8) * (mh / 8);
-  size_t off = 0, o_base[3], o_map[3] = {0, 0, 0};
-  for (int i = 0; i < 3; i++) { o_base[i] = off; off += (nb[i] * 128 + 255) & ~(size_t)255; }
-  for (int i = 0; i < nch; i++) { o_map[i] = off; off += (nm * 128 + 255) & ~(size_t)255; }
-  UHDR_TRY(ensure(c->enc[0], off));
+  const size_t nbc = (size_t)(w / cdiv) * (h / cdiv), nm = (size_t)(mw / 8) * (mh / 8);
+  const size_t nblocks[6] = {(size_t)(w / 8) * (h / 8), nbc, nbc, nm, nm, nm};
   uhdr_hip_api1_blocks_t blocks;
   memset(&blocks, 0, sizeof blocks);
-  for (int i = 0; i < 3; i++) blocks.base_coef[i] = (int16_t*)((uint8_t*)c->enc[0].p + o_base[i]);
-  for (int i = 0; i < nch; i++) blocks.map_coef[i] = (int16_t*)((uint8_t*)c->enc[0].p + o_map[i]);
-  uhdr_raw_image_t gm;
-  memset(&gm, 0, sizeof gm);
+  int16_t* coef[6];
+  UHDR_TRY(carve_coef_arrays(c->enc[0], nblocks, 3 + nch, coef));
+  for (int i = 0; i < 3; i++) blocks.base_coef[i] = coef[i];
+  for (int i = 0; i < nch; i++) blocks.map_coef[i] = coef[3 + i];
   // the two scans
   uhdr_hip_jpeg_scan_t sb, sm;
-  memset(&sb, 0, sizeof sb);
-  memset(&sm, 0, sizeof sm);
-  sb.num_components = 3;
-  sb.w = w; sb.h = h;
-  for (int i = 0; i < 3; i++) {
-    sb.coef[i] = blocks.base_coef[i];
-    sb.blocks_w[i] = (int)(i ? w / cdiv : w / 8);
-    sb.blocks_h[i] = (int)(i ? h / cdiv : h / 8);
-    sb.h_samp[i] = sb.v_samp[i] = (i || rgba) ? 1 : 2;
-  }
-  sm.num_components = nch;
-  sm.w = mw; sm.h = mh;
-  for (int i = 0; i < nch; i++) {
-    sm.coef[i] = blocks.map_coef[i];
-    sm.blocks_w[i] = (int)(mw / 8);
-    sm.blocks_h[i] = (int)(mh / 8);
-    sm.h_samp[i] = sm.v_samp[i] = 1;
-  }
-  if (base_capacity > 0xFFFFFFF0u) base_capacity = 0xFFFFFFF0u;
+  fill_scan(&sb, w, h, 3, cdiv, coef);
+  fill_scan(&sm, mw, mh, nch, 8, coef + 3);
+  if (base_capacity > 0xFFFFFFF0u) base_capacity = 0xFFFFFFF0u;  // (for the device route; scans_to_host clamps for itself)
   if (map_capacity > 0xFFFFFFF0u) map_capacity = 0xFFFFFFF0u;
   size_t nbs = 0, nms = 0;
   // Round 6, device-resident callers: the base image's scan is coded on the auxiliary stream, straight behind the base image's blocks there -- the
@@ -741,7 +665,7 @@ static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   c->side_job_posted = false;
   c->defer_md = dev;  // device-resident callers: no host synchronisation between the chain and the entropy stage
   c->deferred_md.valid = false;
-  const uhdr_error_info_t fs = encode_api1_fused_impl(c, &ds, &dh, cfg, base_encoding, qt_base, qt_map, &blocks, md, nullptr, any_sdr, onepass);
+  const uhdr_error_info_t fs = encode_api1_fused_impl(c, &ds, &dh, cfg, base_encoding, qt_base, qt_map, &blocks, md, nullptr, route);
   c->defer_md = false;
   c->on_side_launched = nullptr;
   const bool base_posted = c->side_job_posted;
@@ -784,17 +708,64 @@ static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
     HIP_TRY(hipStreamSynchronize(c->stream));  // (the entropy stage has synchronised already: the metadata's copy is long done)
     return finish_deferred_md();
   }
-  UHDR_TRY(ensure(c->enc[1], base_capacity + 64));
-  UHDR_TRY(ensure(c->enc[2], map_capacity + 64));
-  // both scans at once (round 5): the base image on this context's stream, the map on the auxiliary one
-  const uhdr_error_info_t e2 = uhdr_hip_huffman_encode2_dev(c, &sb, (uint8_t*)c->enc[1].p, base_capacity, &nbs, &sm, (uint8_t*)c->enc[2].p, map_capacity, &nms);
-  *base_bytes = nbs;
-  *map_bytes = nms;
-  if (e2.error_code != UHDR_CODEC_OK) return e2;
-  HIP_TRY(hipMemcpyAsync(base_scan, c->enc[1].p, nbs, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(map_scan, c->enc[2].p, nms, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ok_status();
+  return scans_to_host(c, &sb, &sm, c->enc[1], c->enc[2], base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes);
+}
+// the host-buffer entry points leave their wall time in the stats
+static uhdr_error_info_t encode_api1_scans_timed(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                 uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                 uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                                 size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned route) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const uhdr_error_info_t r = encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes,
+                                                     map_scan, map_capacity, map_bytes, route);
+  if (c) c->stats.last_encode_api1_scans_ns = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+  return r;
+}
+uhdr_error_info_t uhdr_hip_encode_api1_scans(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                             uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                             uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                             size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
+  return encode_api1_scans_timed(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
+                                 map_bytes, 0);
+}
+uhdr_error_info_t uhdr_hip_encode_api1_scans_any(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                 uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                 uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                                 size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
+  return encode_api1_scans_timed(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
+                                 map_bytes, kApi1AnySdr);
+}
+// ... and on DEVICE-resident intents, into DEVICE buffers (round 6): one call per direction of the round trip, so that no binding
+// layer sits between the stages (a Python caller's 30-100 us between two entry points were a third of a 4K round trip)
+uhdr_error_info_t uhdr_hip_encode_api1_scans_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                 uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                 uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                                 size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
+  return encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
+                                map_bytes, kApi1Dev);
+}
+uhdr_error_info_t uhdr_hip_encode_api1_scans_any_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                     uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                     uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                                     size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
+  return encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
+                                map_bytes, kApi1Dev | kApi1AnySdr);
+}
+// ... and with the one-pass (real-time) preset as well: what the _any siblings run for UHDR_USAGE_BEST_QUALITY, the two launches of
+// uhdr_hip_encode_api1_fused_onepass_dev in front of the same entropy stage for UHDR_USAGE_REALTIME
+uhdr_error_info_t uhdr_hip_encode_api1_scans_onepass_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                         uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                         uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                                         size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
+  return encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
+                                map_bytes, kApi1Dev | kApi1AnySdr | kApi1Onepass);
+}
+uhdr_error_info_t uhdr_hip_encode_api1_scans_onepass(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                     uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                     uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                                     size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
+  return encode_api1_scans_timed(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
+                                 map_bytes, kApi1AnySdr | kApi1Onepass);
 }
 
 // JpegR::encodeJPEGR API-0 (jpegr.cpp:179-244) for the HDR intents its tone map renders to RGBA8888 -- RGBA1010102 (BASELINE config 3) and
@@ -818,151 +789,51 @@ static uhdr_error_info_t check_scaled_scans(const uhdr_raw_image_t* hdr, const u
   return ok_status();
 }
 
-// scaled == false: uhdr_hip_encode_api0_scans; true: the RGB half of uhdr_hip_encode_api0_scans_scaled, which also takes scale factors 2 and 4
-static uhdr_error_info_t encode_api0_scans_rgb_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
-                                                    const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
-                                                    uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
-                                                    size_t map_capacity, size_t* map_bytes, bool scaled) {
+// The driver behind uhdr_hip_encode_api0_scans (any_format == false: RGBA1010102 / RGBA half float only), uhdr_hip_encode_api0_scans_any and
+// uhdr_hip_encode_api0_scans_scaled (scaled: scale factors 2 and 4 as well, for RGBA1010102 and P010 -- the map is then a (w / S) x (h / S) image
+// of whole blocks).  A P010 intent (what camera and video frames arrive as; jpegr.cpp:179-244 compresses the tone mapper's 4:2:0 planes as they
+// are) differs in two places: its base image is 4:2:0 -- whole 16 x 16 MCUs, a 2x2 / 1x1 / 1x1 scan -- and that image's blocks come from the
+// API-1 chain's launch_base_blocks (no conversion matrix) where the 4:4:4 planes take three uhdr_hip_fdct_quant_dev calls.
+static uhdr_error_info_t encode_api0_scans_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
+                                                const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
+                                                size_t map_capacity, size_t* map_bytes, bool any_format, bool scaled) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!hdr || !cfg_in || !qt_base || !qt_map || !md || !base_scan || !map_scan || !base_bytes || !map_bytes)
     return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
-  if (hdr->fmt != UHDR_IMG_FMT_32bppRGBA1010102 && hdr->fmt != UHDR_IMG_FMT_64bppRGBAHalfFloat)
+  const bool p010 = any_format && hdr->fmt == UHDR_IMG_FMT_24bppYCbCrP010;
+  if (!p010 && hdr->fmt != UHDR_IMG_FMT_32bppRGBA1010102 && hdr->fmt != UHDR_IMG_FMT_64bppRGBAHalfFloat)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain takes UHDR_IMG_FMT_32bppRGBA1010102 or UHDR_IMG_FMT_64bppRGBAHalfFloat. Received %d", hdr->fmt);
   if (!scaled && cfg_in->map_dimension_scale_factor != 1)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs a full-resolution gain map (scale factor 1), received %d", cfg_in->map_dimension_scale_factor);
-  if (hdr->w == 0 || hdr->h == 0 || hdr->w % 8 || hdr->h % 8 || hdr->w > 65535 || hdr->h > 65535)
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs dimensions that are multiples of 8 (received %ux%u); use the operators", hdr->w, hdr->h);
+  // the base image's layout: cdiv = a chroma block's width in luma samples, csub = luma samples per chroma sample; the image is whole MCUs
+  const unsigned w = hdr->w, h = hdr->h, cdiv = p010 ? 16 : 8, csub = cdiv / 8;
+  if (w == 0 || h == 0 || w % cdiv || h % cdiv || w > 65535 || h > 65535)
+    return p010 ? err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs P010 dimensions that are multiples of 16 (received %ux%u); use the operators", w, h)
+                : err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs dimensions that are multiples of 8 (received %ux%u); use the operators", w, h);
   if (scaled) UHDR_TRY(check_scaled_scans(hdr, cfg_in));
   if (c->comm != nullptr || c->comm_custom) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes");
   UHDR_TRY(validate_image(hdr, "hdr intent"));
-  for (int t = 0; t < 2; t++)
-    for (int i = 0; i < 64; i++)
-      if (qt_base[t][i] == 0 || qt_base[t][i] > 255 || qt_map[t][i] == 0 || qt_map[t][i] > 255)
-        return err_status(UHDR_CODEC_INVALID_PARAM, "quantization table entry %d out of baseline range", i);
+  UHDR_TRY(check_quant_tables(qt_base, qt_map));
   HIP_TRY(hipSetDevice(c->device));
   uhdr_hip_encode_cfg_t cfg = *cfg_in;
   cfg.preset = UHDR_USAGE_REALTIME;  // jpegr.cpp:207
   cfg.sdr_is_601 = 0;                // jpegr.cpp:213-214
   cfg.use_luminance = 0;
-  const unsigned w = hdr->w, h = hdr->h;
   const int nch = cfg.use_multi_channel_gainmap ? 3 : 1;
   uhdr_raw_image_t dh;
   if (c->resident_on) UHDR_TRY(resident_write_back_all(c));
   UHDR_TRY(stage_in(c, 1, hdr, &dh, true));
-  // device images: the base image's three 4:4:4 planes and the map (rows padded to 64 samples), then the coefficient arrays
+  // device images: the base image's three planes and the map (rows padded to 64 samples), then the coefficient arrays
   const unsigned scale = (unsigned)cfg.map_dimension_scale_factor, mw = w / scale, mh = h / scale;  // (1 unless scaled)
-  const size_t pitch = ((size_t)w + 63) & ~(size_t)63, plane = pitch * h, map_pitch_px = ((size_t)mw + 63) & ~(size_t)63;
-  UHDR_TRY(ensure(c->enc[1], 3 * plane + 256));
-  UHDR_TRY(ensure(c->enc[2], map_pitch_px * (size_t)nch * mh + 256));
-  const size_t nblk = (size_t)(w / 8) * (h / 8), cbytes = (nblk * 128 + 255) & ~(size_t)255;
-  UHDR_TRY(ensure(c->enc[0], cbytes * (size_t)(3 + nch)));
-  uhdr_raw_image_t ycc, gm;
-  memset(&ycc, 0, sizeof ycc);
-  memset(&gm, 0, sizeof gm);
-  for (int i = 0; i < 3; i++) {
-    ycc.planes[i] = (uint8_t*)c->enc[1].p + (size_t)i * plane;
-    ycc.stride[i] = (unsigned int)pitch;
-  }
-  gm.planes[0] = c->enc[2].p;
-  gm.stride[0] = (unsigned int)map_pitch_px;
-  UHDR_TRY(encode_api0_fused_impl(c, &dh, &cfg, nullptr, &ycc, md, &gm, scaled));
-  if (sdr_cg) *sdr_cg = ycc.cg;  // what toneMap gives its SDR rendition (jpegr.cpp:2024-2030) and convert_raw_input_to_ycbcr keeps
-  if (gainmap_desc) {
-    *gainmap_desc = gm;
-    gainmap_desc->planes[0] = gainmap_desc->planes[1] = gainmap_desc->planes[2] = nullptr;
-  }
-  int16_t* coef[6];
-  for (int i = 0; i < 3 + nch; i++) coef[i] = (int16_t*)((uint8_t*)c->enc[0].p + (size_t)i * cbytes);
-  for (int i = 0; i < 3; i++)
-    UHDR_TRY(uhdr_hip_fdct_quant_dev(c, (const uint8_t*)ycc.planes[i], pitch, (int)(w / 8), (int)(h / 8), qt_base[i ? 1 : 0], coef[i]));
-  if (nch == 3) UHDR_TRY(uhdr_hip_fdct_quant_rgb_dev(c, &gm, qt_map[0], qt_map[1], coef[3], coef[4], coef[5]));
-  else UHDR_TRY(uhdr_hip_fdct_quant_dev(c, (const uint8_t*)gm.planes[0], (size_t)gm.stride[0], (int)(mw / 8), (int)(mh / 8), qt_map[0], coef[3]));
-  uhdr_hip_jpeg_scan_t sb, sm;
-  memset(&sb, 0, sizeof sb);
-  memset(&sm, 0, sizeof sm);
-  sb.num_components = 3;
-  sm.num_components = nch;
-  sb.w = w; sm.w = mw;
-  sb.h = h; sm.h = mh;
-  for (int i = 0; i < 3; i++) {
-    sb.coef[i] = coef[i];
-    sb.blocks_w[i] = (int)(w / 8); sb.blocks_h[i] = (int)(h / 8);
-    sb.h_samp[i] = sb.v_samp[i] = 1;
-  }
-  for (int i = 0; i < nch; i++) {
-    sm.coef[i] = coef[3 + i];
-    sm.blocks_w[i] = (int)(mw / 8); sm.blocks_h[i] = (int)(mh / 8);
-    sm.h_samp[i] = sm.v_samp[i] = 1;
-  }
-  if (base_capacity > 0xFFFFFFF0u) base_capacity = 0xFFFFFFF0u;
-  if (map_capacity > 0xFFFFFFF0u) map_capacity = 0xFFFFFFF0u;
-  // the scans' device buffers: the image planes are free again once the FDCTs have run -- but those are only enqueued, so separate ones
-  UHDR_TRY(ensure(c->jpg[0], base_capacity + 64));
-  UHDR_TRY(ensure(c->jpg[4], map_capacity + 64));
-  size_t nbs = 0, nms = 0;
-  const uhdr_error_info_t e2 = uhdr_hip_huffman_encode2_dev(c, &sb, (uint8_t*)c->jpg[0].p, base_capacity, &nbs, &sm, (uint8_t*)c->jpg[4].p, map_capacity, &nms);
-  *base_bytes = nbs;
-  *map_bytes = nms;
-  if (e2.error_code != UHDR_CODEC_OK) return e2;
-  HIP_TRY(hipMemcpyAsync(base_scan, c->jpg[0].p, nbs, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(map_scan, c->jpg[4].p, nms, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ok_status();
-}
-uhdr_error_info_t uhdr_hip_encode_api0_scans(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
-                                             const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
-                                             uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
-                                             size_t map_capacity, size_t* map_bytes) {
-  return encode_api0_scans_rgb_impl(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes, false);
-}
-
-// uhdr_hip_encode_api0_scans for every intent a fused front end takes: RGBA1010102 / RGBA half float go to the entry point above unchanged;
-// a P010 intent (what camera and video frames arrive as; jpegr.cpp:179-244 compresses the tone mapper's 4:2:0 planes as they are) goes up once,
-// uhdr_hip_encode_api0_p010_fused_dev leaves the 4:2:0 base image and the one-pass map in HBM, the base image's blocks come from the API-1
-// chain's launch_base_blocks (no conversion matrix), the map's as above, both scans are Huffman-coded concurrently (the base scan is
-// 2x2 / 1x1 / 1x1) and only the bytes come down.  Preset, sdr_is_601 and use_luminance are overridden as above.
-// scaled == false: uhdr_hip_encode_api0_scans_any; true: uhdr_hip_encode_api0_scans_scaled, which also takes scale factors 2 and 4 for RGBA1010102 and
-// P010 intents -- the map is then a (w / S) x (h / S) image of whole blocks.
-static uhdr_error_info_t encode_api0_scans_any_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
-                                                    const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
-                                                    uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
-                                                    size_t map_capacity, size_t* map_bytes, bool scaled) {
-  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
-  if (!hdr || !cfg_in || !qt_base || !qt_map || !md || !base_scan || !map_scan || !base_bytes || !map_bytes)
-    return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
-  if (hdr->fmt != UHDR_IMG_FMT_24bppYCbCrP010)
-    return encode_api0_scans_rgb_impl(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes, scaled);
-  if (!scaled && cfg_in->map_dimension_scale_factor != 1)
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs a full-resolution gain map (scale factor 1), received %d", cfg_in->map_dimension_scale_factor);
-  if (hdr->w == 0 || hdr->h == 0 || hdr->w % 16 || hdr->h % 16 || hdr->w > 65535 || hdr->h > 65535)
-    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs P010 dimensions that are multiples of 16 (received %ux%u); use the operators", hdr->w, hdr->h);
-  if (scaled) UHDR_TRY(check_scaled_scans(hdr, cfg_in));
-  if (c->comm != nullptr || c->comm_custom) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes");
-  UHDR_TRY(validate_image(hdr, "hdr intent"));
-  for (int t = 0; t < 2; t++)
-    for (int i = 0; i < 64; i++)
-      if (qt_base[t][i] == 0 || qt_base[t][i] > 255 || qt_map[t][i] == 0 || qt_map[t][i] > 255)
-        return err_status(UHDR_CODEC_INVALID_PARAM, "quantization table entry %d out of baseline range", i);
-  HIP_TRY(hipSetDevice(c->device));
-  uhdr_hip_encode_cfg_t cfg = *cfg_in;
-  cfg.preset = UHDR_USAGE_REALTIME;  // jpegr.cpp:207
-  cfg.sdr_is_601 = 0;                // jpegr.cpp:213-214
-  cfg.use_luminance = 0;
-  const unsigned w = hdr->w, h = hdr->h;
-  const int nch = cfg.use_multi_channel_gainmap ? 3 : 1;
-  uhdr_raw_image_t dh;
-  if (c->resident_on) UHDR_TRY(resident_write_back_all(c));
-  UHDR_TRY(stage_in(c, 1, hdr, &dh, true));
-  // device images: the base image's 4:2:0 planes and the map (rows padded to 64 samples), then the coefficient arrays
-  const unsigned scale = (unsigned)cfg.map_dimension_scale_factor, mw = w / scale, mh = h / scale;  // (1 unless scaled)
-  const size_t pitch = ((size_t)w + 63) & ~(size_t)63, cpitch = ((size_t)(w / 2) + 63) & ~(size_t)63, map_pitch = ((size_t)mw + 63) & ~(size_t)63;
-  const size_t plane_y = pitch * h, plane_c = cpitch * (h / 2);
+  const size_t pitch = ((size_t)w + 63) & ~(size_t)63, cpitch = ((size_t)(w / csub) + 63) & ~(size_t)63, map_pitch = ((size_t)mw + 63) & ~(size_t)63;
+  const size_t plane_y = pitch * h, plane_c = cpitch * (h / csub);
   UHDR_TRY(ensure(c->enc[1], plane_y + 2 * plane_c + 256));
   UHDR_TRY(ensure(c->enc[2], map_pitch * (size_t)nch * mh + 256));
-  const size_t nb[3] = {(size_t)(w / 8) * (h / 8), (size_t)(w / 16) * (h / 16), (size_t)(w / 16) * (h / 16)};
-  size_t off = 0, o_coef[6];
-  for (int i = 0; i < 3 + nch; i++) { o_coef[i] = off; off += ((i < 3 ? nb[i] : nb[0]) * 128 + 255) & ~(size_t)255; }
-  UHDR_TRY(ensure(c->enc[0], off));
+  const size_t nby = (size_t)(w / 8) * (h / 8), nbc = (size_t)(w / cdiv) * (h / cdiv);
+  const size_t nblocks[6] = {nby, nbc, nbc, nby, nby, nby};  // (the map's arrays have room for a full-resolution map)
+  int16_t* coef[6];
+  UHDR_TRY(carve_coef_arrays(c->enc[0], nblocks, 3 + nch, coef));
   uhdr_raw_image_t ycc, gm;
   memset(&ycc, 0, sizeof ycc);
   memset(&gm, 0, sizeof gm);
@@ -973,63 +844,47 @@ static uhdr_error_info_t encode_api0_scans_any_impl(uhdr_hip_ctx_t* c, const uhd
   ycc.stride[1] = ycc.stride[2] = (unsigned int)cpitch;
   gm.planes[0] = c->enc[2].p;
   gm.stride[0] = (unsigned int)map_pitch;
-  UHDR_TRY(encode_api0_p010_fused_impl(c, &dh, &cfg, &ycc, md, &gm, scaled));
-  if (sdr_cg) *sdr_cg = ycc.cg;  // what toneMap gives its SDR rendition (jpegr.cpp:2024-2030)
+  UHDR_TRY(encode_api0_front(c, &dh, &cfg, nullptr, &ycc, md, &gm, p010, scaled));
+  if (sdr_cg) *sdr_cg = ycc.cg;  // what toneMap gives its SDR rendition (jpegr.cpp:2024-2030) and convert_raw_input_to_ycbcr keeps
   if (gainmap_desc) {
     *gainmap_desc = gm;
     gainmap_desc->planes[0] = gainmap_desc->planes[1] = gainmap_desc->planes[2] = nullptr;
   }
-  int16_t* coef[6];
-  for (int i = 0; i < 3 + nch; i++) coef[i] = (int16_t*)((uint8_t*)c->enc[0].p + o_coef[i]);
-  {
+  if (p010) {
     ProfScope ps(c, "fdct_quant");
     HIP_TRY(launch_base_blocks(view_of(&ycc), nullptr, qt_base[0], qt_base[1], coef, c->stream));
+  } else {
+    for (int i = 0; i < 3; i++)
+      UHDR_TRY(uhdr_hip_fdct_quant_dev(c, (const uint8_t*)ycc.planes[i], pitch, (int)(w / 8), (int)(h / 8), qt_base[i ? 1 : 0], coef[i]));
   }
   if (nch == 3) UHDR_TRY(uhdr_hip_fdct_quant_rgb_dev(c, &gm, qt_map[0], qt_map[1], coef[3], coef[4], coef[5]));
   else UHDR_TRY(uhdr_hip_fdct_quant_dev(c, (const uint8_t*)gm.planes[0], (size_t)gm.stride[0], (int)(mw / 8), (int)(mh / 8), qt_map[0], coef[3]));
   uhdr_hip_jpeg_scan_t sb, sm;
-  memset(&sb, 0, sizeof sb);
-  memset(&sm, 0, sizeof sm);
-  sb.num_components = 3;
-  sm.num_components = nch;
-  sb.w = w; sm.w = mw;
-  sb.h = h; sm.h = mh;
-  for (int i = 0; i < 3; i++) {
-    sb.coef[i] = coef[i];
-    sb.blocks_w[i] = (int)(i ? w / 16 : w / 8);
-    sb.blocks_h[i] = (int)(i ? h / 16 : h / 8);
-    sb.h_samp[i] = sb.v_samp[i] = i ? 1 : 2;
-  }
-  for (int i = 0; i < nch; i++) {
-    sm.coef[i] = coef[3 + i];
-    sm.blocks_w[i] = (int)(mw / 8); sm.blocks_h[i] = (int)(mh / 8);
-    sm.h_samp[i] = sm.v_samp[i] = 1;
-  }
-  if (base_capacity > 0xFFFFFFF0u) base_capacity = 0xFFFFFFF0u;
-  if (map_capacity > 0xFFFFFFF0u) map_capacity = 0xFFFFFFF0u;
-  UHDR_TRY(ensure(c->jpg[0], base_capacity + 64));
-  UHDR_TRY(ensure(c->jpg[4], map_capacity + 64));
-  size_t nbs = 0, nms = 0;
-  const uhdr_error_info_t e2 = uhdr_hip_huffman_encode2_dev(c, &sb, (uint8_t*)c->jpg[0].p, base_capacity, &nbs, &sm, (uint8_t*)c->jpg[4].p, map_capacity, &nms);
-  *base_bytes = nbs;
-  *map_bytes = nms;
-  if (e2.error_code != UHDR_CODEC_OK) return e2;
-  HIP_TRY(hipMemcpyAsync(base_scan, c->jpg[0].p, nbs, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(map_scan, c->jpg[4].p, nms, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ok_status();
+  fill_scan(&sb, w, h, 3, cdiv, coef);
+  fill_scan(&sm, mw, mh, nch, 8, coef + 3);
+  // the scans' device buffers: the image planes are free again once the FDCTs have run -- but those are only enqueued, so separate ones
+  return scans_to_host(c, &sb, &sm, c->jpg[0], c->jpg[4], base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes);
+}
+uhdr_error_info_t uhdr_hip_encode_api0_scans(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
+                                             const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                             uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
+                                             size_t map_capacity, size_t* map_bytes) {
+  return encode_api0_scans_impl(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes,
+                                /*any_format=*/false, /*scaled=*/false);
 }
 uhdr_error_info_t uhdr_hip_encode_api0_scans_any(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
                                                  const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
                                                  uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
                                                  size_t map_capacity, size_t* map_bytes) {
-  return encode_api0_scans_any_impl(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes, false);
+  return encode_api0_scans_impl(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes,
+                                /*any_format=*/true, /*scaled=*/false);
 }
 uhdr_error_info_t uhdr_hip_encode_api0_scans_scaled(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
                                                     const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
                                                     uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
                                                     size_t map_capacity, size_t* map_bytes) {
-  return encode_api0_scans_any_impl(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes, true);
+  return encode_api0_scans_impl(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes,
+                                /*any_format=*/true, /*scaled=*/true);
 }
 
 // -------------------------------------------------------------------------------------------------
