@@ -557,6 +557,31 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_coef444_dev(uhdr_hip_ctx_t* ctx,
                                                      uhdr_img_fmt_t output_format, float max_display_boost,
                                                      uhdr_raw_image_t* dest);
 
+/* The mirror on the encode side: generateGainMap (lib/src/jpegr.cpp:530-1050) with the SDR intent still in coefficient form -- the
+ * compressed SDR intent of JpegR::encodeJPEGR API-3 (lib/src/jpegr.cpp:327-385) after its Huffman decode.  JpegDecoderHelper's
+ * dequantize + IDCT stage (jpegdecoderhelper.cpp:468-535) runs inside generateGainMap's first launch (pass 1 of the two-pass preset, the
+ * whole one-pass generation): a wave dequantizes and inverse-transforms a 128 x 16 pixel tile (32 + 8 + 8 blocks of a 4:2:0 frame,
+ * 32 + 16 + 16 of a 4:2:2 one) into LDS and produces the tile's map pixels from there; the 8-bit Y / Cb / Cr planes never exist in
+ * memory.  sdr: as for uhdr_hip_apply_gainmap_coef_dev (DEVICE arrays on libjpeg's block grid for w x h, 16-byte aligned;
+ * UHDR_CODEC_INVALID_PARAM for any other grid); sdr_cg: the SDR intent's colour gamut; hdr_intent, cfg, md, gainmap_img: as for
+ * uhdr_hip_generate_gainmap_dev -- both presets, gamma != 1, the content-boost hints, use_luminance, sdr_is_601 (honoured as given) and
+ * every HDR format and transfer are taken.  Result == uhdr_hip_idct_dequant_dev x 3 into a UHDR_IMG_FMT_12bppYCbCr420 image of w x h
+ * followed by uhdr_hip_generate_gainmap_dev: map bytes and metadata bit for bit.  UHDR_CODEC_UNSUPPORTED_FEATURE before anything is
+ * uploaded or launched (decode with uhdr_hip_idct_dequant_dev and call uhdr_hip_generate_gainmap_dev): gain-map scale factors other
+ * than 1, 2 and 4 (the small-image fallback of lib/src/jpegr.cpp:696-706 included when it changes the factor), odd w or h, a context
+ * with a communicator.  Synchronous for the two-pass preset (the metadata needs the range), enqueued only for the one-pass preset. */
+uhdr_error_info_t uhdr_hip_generate_gainmap_coef_dev(uhdr_hip_ctx_t* ctx, const uhdr_hip_jpeg_coefficients_t* sdr,
+                                                     unsigned int w, unsigned int h, uhdr_color_gamut_t sdr_cg,
+                                                     const uhdr_raw_image_t* hdr_intent, const uhdr_hip_encode_cfg_t* cfg,
+                                                     uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_img);
+/* uhdr_hip_generate_gainmap_coef422_dev: arguments and behaviour as uhdr_hip_generate_gainmap_coef_dev; the SDR intent is a 4:2:2 frame
+ * (2x1 / 1x1 / 1x1, block grids as for uhdr_hip_apply_gainmap_coef422_dev) and the result that of the staged operators on the
+ * UHDR_IMG_FMT_16bppYCbCr422 image. */
+uhdr_error_info_t uhdr_hip_generate_gainmap_coef422_dev(uhdr_hip_ctx_t* ctx, const uhdr_hip_jpeg_coefficients_t* sdr,
+                                                        unsigned int w, unsigned int h, uhdr_color_gamut_t sdr_cg,
+                                                        const uhdr_raw_image_t* hdr_intent, const uhdr_hip_encode_cfg_t* cfg,
+                                                        uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_img);
+
 /* ---- JPEG entropy stage (the step after uhdr_hip_fdct_quant) ---------------------------------
  * Baseline Huffman coding of quantized coefficient blocks with the Annex K tables -- what libjpeg does behind
  * JpegEncoderHelper::compressImage (jpegencoderhelper.cpp:131-244: jpeg_set_defaults, optimize_coding off).  libjpeg's
@@ -962,6 +987,34 @@ uhdr_error_info_t uhdr_hip_decode_api1_scans_any_dev(uhdr_hip_ctx_t* ctx, const 
                                                      const uint8_t* map_data, size_t map_bytes, uhdr_color_gamut_t map_cg,
                                                      int libjpeg_variant, const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t output_ct,
                                                      uhdr_img_fmt_t output_format, float max_display_boost, uhdr_raw_image_t* dest);
+
+/* JpegR::encodeJPEGR API-3 (lib/src/jpegr.cpp:327-385) behind its container in ONE call: a raw HDR intent and a COMPRESSED SDR intent -- an
+ * existing camera or phone JPEG that stays the file's base image, byte for byte -- to the gain map's entropy-coded scan (the transcoding
+ * case).  sdr_jpeg: the SDR file's parsed header (uhdr_hip_jpeg_parse, or filled by the caller; an all-zero DHT block selects the Annex K
+ * tables; scan.coef is ignored); sdr_data / sdr_bytes: its entropy-coded bytes, between the SOS header and the marker that ends them;
+ * sdr_cg: its colour gamut; hdr, cfg as for uhdr_hip_generate_gainmap_dev with cfg->sdr_is_601 forced to 1 (lib/src/jpegr.cpp:377);
+ * qt_map: the map's {luma, chroma} quantization tables.  Sequence: uhdr_hip_huffman_decode_dev into the context's coefficient arrays ->
+ * generateGainMap (lib/src/jpegr.cpp:530-1050) straight from those coefficients (uhdr_hip_generate_gainmap_coef_dev / _coef422_dev; JpegDecoderHelper's
+ * dequantize + IDCT stage, jpegdecoderhelper.cpp:468-535, inside the kernel) or from planes (three uhdr_hip_idct_dequant_dev launches +
+ * uhdr_hip_generate_gainmap_dev: a 4:4:4 file, a geometry the coefficient operator declines, the staged route) -> the map's coefficients (two
+ * pass: the block kernel of the fused API-1 chain behind the range kernel; one pass: the byte map in context scratch through
+ * uhdr_hip_fdct_quant_dev / _rgb_dev) -> uhdr_hip_huffman_encode_dev with restart_interval 0.  Map scan, metadata and gainmap_desc equal
+ * those of the staged public chain (uhdr_hip_jpeg_decode_scan -> uhdr_hip_generate_gainmap_dev -> FDCT -> Huffman).  The route of a 4:2:0 /
+ * 4:2:2 file is the measured default; UHDR_HIP_API3_ROUTE=fused|staged in the environment forces one.
+ * uhdr_hip_encode_api3_scans: sdr_data, the HDR intent's planes and map_scan are HOST memory; _dev: all three DEVICE memory.  Synchronous.
+ * UHDR_CODEC_MEM_ERROR with the needed size in *map_bytes when map_capacity is too small.  UHDR_CODEC_UNSUPPORTED_FEATURE before anything is
+ * uploaded or launched: grayscale, 4:4:0 and 4:1:1 files (a progressive file has no uhdr_hip_jpeg_header_t: uhdr_hip_jpeg_parse returns -8),
+ * map dimensions (w / S, h / S) that are not multiples of 8, gamma != 1, a context with a communicator -- the operators take those. */
+uhdr_error_info_t uhdr_hip_encode_api3_scans(uhdr_hip_ctx_t* ctx, const uhdr_hip_jpeg_header_t* sdr_jpeg, const uint8_t* sdr_data,
+                                             size_t sdr_bytes, uhdr_color_gamut_t sdr_cg, const uhdr_raw_image_t* hdr,
+                                             const uhdr_hip_encode_cfg_t* cfg, const uint16_t qt_map[2][64],
+                                             uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                             uint8_t* map_scan, size_t map_capacity, size_t* map_bytes);
+uhdr_error_info_t uhdr_hip_encode_api3_scans_dev(uhdr_hip_ctx_t* ctx, const uhdr_hip_jpeg_header_t* sdr_jpeg, const uint8_t* sdr_data,
+                                                 size_t sdr_bytes, uhdr_color_gamut_t sdr_cg, const uhdr_raw_image_t* hdr,
+                                                 const uhdr_hip_encode_cfg_t* cfg, const uint16_t qt_map[2][64],
+                                                 uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                 uint8_t* map_scan, size_t map_capacity, size_t* map_bytes);
 
 /* ---- handing a context to its next user (round 6; what the facade's context pool calls when a codec lets go of one) --------------------
  * Forgets everything that belonged to the previous user: the device-resident image copies, a write-back error that was latched for

@@ -267,6 +267,32 @@ class UltraHdr {
                                                                                                base_capacity, base_bytes, map_scan, map_capacity, map_bytes);
   }
 
+  // generateGainMap on an SDR intent still in coefficient form -- the compressed intent of an API-3 encode after its Huffman decode (device
+  // pointers; hdr_intent and gainmap_img are device images): the dequantize + IDCT stage runs inside the kernel
+  // (uhdr_hip_generate_gainmap_coef_dev; sampling422: uhdr_hip_generate_gainmap_coef422_dev).  == idct_dequant x 3 + generateGainMap.
+  uhdr_error_info_t generateGainMapFromCoefficients(const uhdr_hip_jpeg_coefficients_t* sdr, unsigned int w, unsigned int h, uhdr_color_gamut_t sdr_cg,
+                                                    uhdr_raw_image_t* hdr_intent, uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_raw_image_t* gainmap_img,
+                                                    bool sampling422 = false, bool sdr_is_601 = false, bool use_luminance = true) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, sdr_is_601 ? 1 : 0, use_luminance ? 1 : 0};
+    return (sampling422 ? uhdr_hip_generate_gainmap_coef422_dev : uhdr_hip_generate_gainmap_coef_dev)(mCtx, sdr, w, h, sdr_cg, hdr_intent, &cfg,
+                                                                                                      gainmap_metadata, gainmap_img);
+  }
+
+  // JpegR::encodeJPEGR API-3 (jpegr.cpp:327-385) without the container in one call (uhdr_hip_encode_api3_scans / _dev): the compressed SDR
+  // intent's parsed header and entropy-coded bytes + the raw HDR intent -> the gain map's scan.  The base image stays the caller's JPEG.
+  uhdr_error_info_t encodeApi3Scans(const uhdr_hip_jpeg_header_t* sdr_jpeg, const uint8_t* sdr_data, size_t sdr_bytes, uhdr_color_gamut_t sdr_cg,
+                                    uhdr_raw_image_t* hdr_intent, const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* gainmap_metadata,
+                                    uhdr_raw_image_t* gainmap_desc, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, bool dev = false,
+                                    bool use_luminance = true) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, 1, use_luminance ? 1 : 0};
+    return (dev ? uhdr_hip_encode_api3_scans_dev : uhdr_hip_encode_api3_scans)(mCtx, sdr_jpeg, sdr_data, sdr_bytes, sdr_cg, hdr_intent, &cfg, qt_map,
+                                                                               gainmap_metadata, gainmap_desc, map_scan, map_capacity, map_bytes);
+  }
+
   uhdr_error_info_t convertYuv(uhdr_raw_image_t* image, uhdr_color_gamut_t src_encoding, uhdr_color_gamut_t dst_encoding) {
     if (!mCtx) return mCreateStatus;
     return uhdr_hip_convert_yuv(mCtx, image, src_encoding, dst_encoding);

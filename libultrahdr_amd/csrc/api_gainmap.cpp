@@ -112,6 +112,13 @@ constexpr uint64_t kMallHotBytes = 160ull << 20;
 // the quad kernel at scale 1 -- take less time than the generic kernel with the resizing sampler, for Y400 and RGBA8888 maps and for
 // linear and PQ output alike, by more than the two spreads added.
 constexpr bool kResizeDefaultStaged = true;
+// uhdr_hip_encode_api3_scans: the route of a 4:2:0 / 4:2:2 SDR intent when UHDR_HIP_API3_ROUTE does not say.  Measured at 3840 x 2176 and
+// 1920 x 1080 (tools/api3_time.py, profiles/api3_time.json): with the coefficient kernel the whole _dev call takes less time than the staged
+// chain of public entry points in every row of either sampling (three channels at S = 1, one channel at S = 4, both presets), by more than
+// the two spreads added.  (Against the planes route INSIDE the same call it is 4:2:2 and the S = 4 rows that gain; a 4:2:0 file at S = 1 is
+// up to 28 us quicker through UHDR_HIP_API3_ROUTE=staged -- profiles/README.md.)
+constexpr bool kApi3DefaultStaged420 = false;
+constexpr bool kApi3DefaultStaged422 = false;
 size_t input_bytes(const uhdr_raw_image_t* im) {
   size_t n = 0;
   const ImageView v = view_of(im);
@@ -239,6 +246,16 @@ bool resize_route_staged() {
 }
 }  // namespace
 
+// uhdr_hip_encode_api3_scans / _dev: UHDR_HIP_API3_ROUTE=fused|staged forces the coefficient kernel (generate_coef.hip) or the planes route
+// (three IDCT launches + generate_gainmap) for a 4:2:0 / 4:2:2 SDR intent; otherwise the measured default of that sampling (profiles/README.md)
+bool uhdr_api::api3_route_staged(int sampling) {
+  if (const char* e = getenv("UHDR_HIP_API3_ROUTE")) {
+    if (!strcmp(e, "staged")) return true;
+    if (!strcmp(e, "fused")) return false;
+  }
+  return sampling == 420 ? kApi3DefaultStaged420 : kApi3DefaultStaged422;
+}
+
 uhdr_error_info_t uhdr_hip_apply_gainmap_any_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
                                                  const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct, uhdr_img_fmt_t out_fmt,
                                                  float max_display_boost, uhdr_raw_image_t* dest, unsigned int y0, unsigned int full_height) {
@@ -352,6 +369,31 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_batch_dev(uhdr_hip_ctx_t* c, unsigned i
   return ok_status();
 }
 
+// The descriptor of a 4:2:0 / 4:2:2 / 4:4:4 frame in coefficient form, after the checks every operator that reads one shares: the block grid must be
+// libjpeg's for w x h at that sampling, the arrays 16-byte aligned, no table entry zero
+static uhdr_error_info_t fill_coef_src(const uhdr_hip_jpeg_coefficients_t* base, unsigned int w, unsigned int h, int sampling, CoefSrc* cs) {
+  if (!base) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for the base image coefficients");
+  if (w == 0 || h == 0) return err_status(UHDR_CODEC_INVALID_PARAM, "image dimensions cannot be zero, received %ux%u", w, h);
+  // the block grid of a 4:2:0 / 4:2:2 / 4:4:4 frame (jpeg_component_info::width_in_blocks / height_in_blocks)
+  const unsigned int cw = sampling == 444 ? w : (w + 1) / 2, ch = sampling == 420 ? (h + 1) / 2 : h;
+  const unsigned int want_w[3] = {(w + 7) / 8, (cw + 7) / 8, (cw + 7) / 8}, want_h[3] = {(h + 7) / 8, (ch + 7) / 8, (ch + 7) / 8};
+  for (int i = 0; i < 3; i++) {
+    if (!base->coef[i] || ((uintptr_t)base->coef[i] & 15))
+      return err_status(UHDR_CODEC_INVALID_PARAM, "coefficient buffer %d is null or not 16-byte aligned", i);
+    if (base->blocks_w[i] != (int)want_w[i] || base->blocks_h[i] != (int)want_h[i])
+      return err_status(UHDR_CODEC_INVALID_PARAM, "component %d: a %dx%d block grid does not match a 4:%d:%d image of %ux%u (expected %ux%u)", i,
+                        base->blocks_w[i], base->blocks_h[i], sampling == 444 ? 4 : 2, sampling == 420 ? 0 : (sampling == 422 ? 2 : 4), w, h, want_w[i], want_h[i]);
+    cs->coef[i] = base->coef[i];
+    cs->bw[i] = base->blocks_w[i];
+    cs->bh[i] = base->blocks_h[i];
+    for (int k = 0; k < 64; k++) {
+      if (base->qtable[i][k] == 0) return err_status(UHDR_CODEC_INVALID_PARAM, "component %d: quantization table entry %d is zero", i, k);
+      cs->q[i][k] = base->qtable[i][k];
+    }
+  }
+  return ok_status();
+}
+
 // applyGainMap with the base image still in coefficient form: JpegDecoderHelper's dequantize + IDCT stage
 // (jpegdecoderhelper.cpp:468-535) runs inside the applyGainMap kernel, the 8-bit planes never exist in memory.
 // All three samplings share this body (and the context's descriptor slots); a uhdr_hip_jpeg_coefficients_t cannot say which
@@ -360,26 +402,8 @@ static uhdr_error_info_t apply_gainmap_coef_impl(uhdr_hip_ctx_t* c, const uhdr_h
                                                  uhdr_color_gamut_t base_cg, const uhdr_raw_image_t* gm, const uhdr_gainmap_metadata_t* md,
                                                  uhdr_color_transfer_t out_ct, float max_display_boost, uhdr_raw_image_t* dest) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
-  if (!base) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for the base image coefficients");
-  if (w == 0 || h == 0) return err_status(UHDR_CODEC_INVALID_PARAM, "image dimensions cannot be zero, received %ux%u", w, h);
-  // the block grid of a 4:2:0 / 4:2:2 / 4:4:4 frame (jpeg_component_info::width_in_blocks / height_in_blocks)
-  const unsigned int cw = sampling == 444 ? w : (w + 1) / 2, ch = sampling == 420 ? (h + 1) / 2 : h;
-  const unsigned int want_w[3] = {(w + 7) / 8, (cw + 7) / 8, (cw + 7) / 8}, want_h[3] = {(h + 7) / 8, (ch + 7) / 8, (ch + 7) / 8};
   CoefSrc cs;
-  for (int i = 0; i < 3; i++) {
-    if (!base->coef[i] || ((uintptr_t)base->coef[i] & 15))
-      return err_status(UHDR_CODEC_INVALID_PARAM, "coefficient buffer %d is null or not 16-byte aligned", i);
-    if (base->blocks_w[i] != (int)want_w[i] || base->blocks_h[i] != (int)want_h[i])
-      return err_status(UHDR_CODEC_INVALID_PARAM, "component %d: a %dx%d block grid does not match a 4:%d:%d image of %ux%u (expected %ux%u)", i,
-                        base->blocks_w[i], base->blocks_h[i], sampling == 444 ? 4 : 2, sampling == 420 ? 0 : (sampling == 422 ? 2 : 4), w, h, want_w[i], want_h[i]);
-    cs.coef[i] = base->coef[i];
-    cs.bw[i] = base->blocks_w[i];
-    cs.bh[i] = base->blocks_h[i];
-    for (int k = 0; k < 64; k++) {
-      if (base->qtable[i][k] == 0) return err_status(UHDR_CODEC_INVALID_PARAM, "component %d: quantization table entry %d is zero", i, k);
-      cs.q[i][k] = base->qtable[i][k];
-    }
-  }
+  UHDR_TRY(fill_coef_src(base, w, h, sampling, &cs));
   HIP_TRY(hipSetDevice(c->device));
   // geometry-only view of the image the coefficients decode to (the kernel never dereferences these planes)
   uhdr_raw_image_t sdr;
@@ -762,6 +786,92 @@ uhdr_error_info_t uhdr_hip_generate_gainmap_dev(uhdr_hip_ctx_t* c, const uhdr_ra
   memcpy(mm, c->h_mm, sizeof mm);
   note_table_stats(c, cfg);
   return generate_gainmap_finalize_md(cfg, hdr->ct, use_base_cg, mm, md);
+}
+
+// generateGainMap with the SDR intent still in coefficient form -- JpegR::encodeJPEGR API-3 (jpegr.cpp:327-385): JpegDecoderHelper's
+// dequantize + IDCT stage (jpegdecoderhelper.cpp:468-535) runs inside the first launch of generateGainMap (jpegr.cpp:530-1050), the 8-bit SDR
+// planes never exist in memory (generate_coef.hip).  What the kernel does not cover is declined with UHDR_CODEC_UNSUPPORTED_FEATURE before
+// anything is uploaded or launched; the staged operators take all of it.
+uhdr_error_info_t uhdr_api::prepare_gen_coef(uhdr_hip_ctx* c, const uhdr_hip_jpeg_coefficients_t* sdr, unsigned int w, unsigned int h, int sampling,
+                                             uhdr_color_gamut_t sdr_cg, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg, GenParams* p, CoefSrc* cs,
+                                             int* use_base_cg, float* hdr_white_nits) {
+  if (!hdr || !cfg) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
+  UHDR_TRY(fill_coef_src(sdr, w, h, sampling, cs));
+  static const char* const kStaged = "decode with uhdr_hip_idct_dequant_dev and call uhdr_hip_generate_gainmap_dev";
+  if (c->comm != nullptr || c->comm_custom)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "generate_gainmap_coef takes whole images, not the stripes of a context with a communicator; %s (or _striped_dev)", kStaged);
+  if (w % 2 || h % 2)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "generate_gainmap_coef covers even dimensions (received %ux%u); %s", w, h, kStaged);
+  unsigned int scale = cfg->map_dimension_scale_factor < 1 ? 0u : (unsigned int)cfg->map_dimension_scale_factor;
+  if (scale && (w / scale == 0 || h / scale == 0)) {  // the small-image fallback of jpegr.cpp:696-706 (fill_gen_params)
+    const unsigned int s = w < h ? w : h;
+    scale = s >= 8 ? s / 8 : 1;
+  }
+  if (scale && scale != 1 && scale != 2 && scale != 4)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "generate_gainmap_coef covers gain-map scale factors 1, 2 and 4 (%u for %ux%u at the configured %d); %s", scale, w, h,
+                      cfg->map_dimension_scale_factor, kStaged);
+  // geometry-only description of the image the coefficients decode to (the kernel never dereferences these planes)
+  uhdr_raw_image_t img;
+  memset(&img, 0, sizeof img);
+  img.fmt = sampling == 420 ? UHDR_IMG_FMT_12bppYCbCr420 : UHDR_IMG_FMT_16bppYCbCr422;
+  img.cg = sdr_cg; img.ct = UHDR_CT_SRGB; img.range = UHDR_CR_FULL_RANGE;
+  img.w = w; img.h = h;
+  for (int i = 0; i < 3; i++) { img.planes[i] = (void*)sdr->coef[i]; img.stride[i] = (unsigned int)sdr->blocks_w[i] * 8; }
+  HIP_TRY(hipSetDevice(c->device));
+  UHDR_TRY(fill_gen_params(c, &img, hdr, cfg, p, use_base_cg, hdr_white_nits, /*sdr_in_registers=*/true));
+  if (p->scale != scale) return err_status(UHDR_CODEC_ERROR, "internal: scale factor %u / %u", p->scale, scale);
+  return ok_status();
+}
+
+static uhdr_error_info_t generate_gainmap_coef_impl(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_coefficients_t* sdr, unsigned int w, unsigned int h, int sampling,
+                                                    uhdr_color_gamut_t sdr_cg, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                    uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  if (!md || !gm || !gm->planes[0]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for gainmap metadata or image");
+  GenParams p;
+  CoefSrc cs;
+  int use_base_cg = 1;
+  float hdr_white_nits;
+  UHDR_TRY(prepare_gen_coef(c, sdr, w, h, sampling, sdr_cg, hdr, cfg, &p, &cs, &use_base_cg, &hdr_white_nits));
+  fill_gainmap_desc(hdr, p, gm);
+  if (gm->stride[0] < gm->w) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap stride (%u) cannot be less than its width (%u)", gm->stride[0], gm->w);
+  const int vsamp = sampling == 420 ? 2 : 1;
+  if (cfg->preset == UHDR_USAGE_REALTIME) {  // one pass: jpegr.cpp:724-737
+    UHDR_TRY(fill_onepass_range(c, cfg, hdr_white_nits, use_base_cg, &p, md));
+    p.out = (uint8_t*)gm->planes[0];
+    p.out_stride = gm->stride[0];
+    ProfScope ps(c, "generate_gainmap");
+    HIP_TRY(launch_generate_gainmap_coef(p, cs, vsamp, false, c->stream));
+    return ok_status();
+  }
+  const size_t nfl = (size_t)p.map_w * p.map_h * (p.multichannel ? 3 : 1);
+  UHDR_TRY(ensure(c->scratch[7], nfl * sizeof(float)));
+  UHDR_TRY(ensure(c->minmax, (6 + 2048 * 6) * sizeof(float)));
+  p.gain_log2 = (float*)c->scratch[7].p;
+  p.minmax = (float*)c->minmax.p;
+  {
+    ProfScope ps(c, "generate_gainmap");
+    HIP_TRY(launch_generate_gainmap_coef(p, cs, vsamp, true, c->stream));
+  }
+  UHDR_TRY(two_pass_tail(c, p, gen_coef_partials_count(p), cfg, gm));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // the only host synchronisation: the metadata needs the final range
+  float mm[6];
+  memcpy(mm, c->h_mm, sizeof mm);
+  note_table_stats(c, cfg);
+  return generate_gainmap_finalize_md(cfg, hdr->ct, use_base_cg, mm, md);
+}
+
+uhdr_error_info_t uhdr_hip_generate_gainmap_coef_dev(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_coefficients_t* sdr, unsigned int w, unsigned int h,
+                                                     uhdr_color_gamut_t sdr_cg, const uhdr_raw_image_t* hdr_intent, const uhdr_hip_encode_cfg_t* cfg,
+                                                     uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_img) {
+  return generate_gainmap_coef_impl(c, sdr, w, h, 420, sdr_cg, hdr_intent, cfg, md, gainmap_img);
+}
+
+// The same operator on the coefficients of a 4:2:2 SDR intent (h_samp 2x1 / 1x1 / 1x1: what most cameras write).
+uhdr_error_info_t uhdr_hip_generate_gainmap_coef422_dev(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_coefficients_t* sdr, unsigned int w, unsigned int h,
+                                                        uhdr_color_gamut_t sdr_cg, const uhdr_raw_image_t* hdr_intent, const uhdr_hip_encode_cfg_t* cfg,
+                                                        uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_img) {
+  return generate_gainmap_coef_impl(c, sdr, w, h, 422, sdr_cg, hdr_intent, cfg, md, gainmap_img);
 }
 
 // -------------------------------------------------------------------------------------------------

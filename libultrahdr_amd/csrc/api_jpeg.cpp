@@ -1487,6 +1487,14 @@ uhdr_error_info_t uhdr_hip_jpeg_decode_rgb_any(uhdr_hip_ctx_t* c, const uhdr_hip
   return jpeg_decode_rgb_timed(c, hdr, scan_data, scan_bytes, out_channels, variant, rgb, stride_px, true);
 }
 
+// a header's DHT content for the entropy decoder; an all-zero DHT block: the Annex K tables
+static const uhdr_hip_huff_tables_t* tables_of(const uhdr_hip_jpeg_header_t* h) {
+  for (int t = 0; t < 4; t++)
+    for (int l = 0; l < 17; l++)
+      if (h->tables.bits[t][l]) return &h->tables;
+  return nullptr;
+}
+
 // JpegR::decodeJPEGR behind its container parsing (jpegr.cpp:1469-1531) on DEVICE-resident data in ONE entry point (round 6): the two
 // JPEG streams' parsed headers + their entropy-coded bytes in HBM -> [both scans entropy-decoded concurrently] -> the gain map's
 // dequant + IDCT (+ ycc -> rgb for a three-channel map) -> applyGainMap with the base image's dequant + IDCT inside the kernel -> dest.
@@ -1527,12 +1535,6 @@ static uhdr_error_info_t decode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_hi
   UHDR_TRY(ensure(c->enc[0], off));
   for (int i = 0; i < nm; i++) sm.coef[i] = (const int16_t*)((const uint8_t*)c->enc[0].p + o_map[i]);
   c->huff_serial_ok = false;  // a scan the parallel decoder declines goes back to the caller (UNSUPPORTED_FEATURE), not to one lane
-  auto tables_of = [](const uhdr_hip_jpeg_header_t* h) -> const uhdr_hip_huff_tables_t* {  // an all-zero DHT block: the Annex K tables
-    for (int t = 0; t < 4; t++)
-      for (int l = 0; l < 17; l++)
-        if (h->tables.bits[t][l]) return &h->tables;
-    return nullptr;
-  };
   const uhdr_error_info_t hs = uhdr_hip_huffman_decode2_dev(c, &sb, tables_of(base), base_data, base_bytes, &sm, tables_of(map), map_data, map_bytes);
   c->huff_serial_ok = true;
   if (hs.error_code != UHDR_CODEC_OK) return hs;
@@ -1614,6 +1616,212 @@ uhdr_error_info_t uhdr_hip_decode_api1_scans_any_dev(uhdr_hip_ctx_t* c, const uh
                                                      uhdr_raw_image_t* dest) {
   return decode_api1_scans_impl(c, base, base_data, base_bytes, base_cg, map, map_data, map_bytes, map_cg, libjpeg_variant, md, output_ct, output_format,
                                 max_display_boost, dest, true);
+}
+
+// -------------------------------------------------------------------------------------------------
+// JpegR::encodeJPEGR API-3 (jpegr.cpp:327-385) behind its container: a raw HDR intent and a COMPRESSED SDR intent -> the gain map's scan
+// -------------------------------------------------------------------------------------------------
+// The SDR intent's entropy-coded bytes are decoded into the context's coefficient arrays; generateGainMap reads them as they are
+// (generate_coef.hip: 4:2:0 and 4:2:2) or through three IDCT launches (4:4:4, the staged route, and wherever the coefficient operator answers
+// UNSUPPORTED_FEATURE for geometry); the map's coefficients come from map_blocks_kernel behind the range kernel (two pass) or from the byte map
+// in context scratch through the FDCT operators (one pass); the marker-less Huffman coder writes the scan.  sdr_is_601 is forced to 1
+// (jpegr.cpp:377).  Only the map's scan comes back: the base image of the file is the caller's JPEG, byte for byte.
+static uhdr_error_info_t encode_api3_scans_impl(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* sdr_jpeg, const uint8_t* sdr_data, size_t sdr_bytes,
+                                                uhdr_color_gamut_t sdr_cg, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in,
+                                                const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* map_scan,
+                                                size_t map_capacity, size_t* map_bytes, bool dev) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  if (!sdr_jpeg || !sdr_data || !hdr || !cfg_in || !qt_map || !md || !map_scan || !map_bytes) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
+  uhdr_hip_jpeg_scan_t sb = sdr_jpeg->scan;
+  int mpr = 0, mrows = 0, bpm = 0;
+  UHDR_TRY(check_scan(&sb, false, &mpr, &mrows, &bpm));
+  const int vsamp = subsampled_vsamp(sb);  // 2: 4:2:0, 1: 4:2:2
+  bool is444 = sb.num_components == 3;
+  for (int i = 0; i < 3 && is444; i++) is444 = sb.h_samp[i] == 1 && sb.v_samp[i] == 1;
+  if (vsamp == 0 && !is444)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "encode_api3_scans takes a baseline 4:2:0, 4:2:2 or 4:4:4 SDR intent; decode it with uhdr_hip_jpeg_decode_scan and use the operators");
+  UHDR_TRY(check_quant_tables(qt_map, qt_map));
+  uhdr_hip_encode_cfg_t cfg = *cfg_in;
+  cfg.sdr_is_601 = 1;  // jpegr.cpp:377: a decoded JPEG is BT.601 whatever its gamut
+  if (cfg.gamma != 1.0f) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the API-3 chain needs gain-map gamma 1 (received %f); use the operators", cfg.gamma);
+  if (c->comm != nullptr || c->comm_custom) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes; the API-3 chain takes whole images: use the operators");
+  const unsigned w = sb.w, h = sb.h;
+  if (hdr->w != w || hdr->h != h)
+    return err_status(UHDR_CODEC_INVALID_PARAM, "sdr intent resolution %ux%u and hdr intent resolution %ux%u do not match", w, h, hdr->w, hdr->h);
+  if (cfg.map_dimension_scale_factor < 1) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap scale factor %d is not positive", cfg.map_dimension_scale_factor);
+  unsigned scale = (unsigned)cfg.map_dimension_scale_factor;
+  if (w / scale == 0 || h / scale == 0) {  // jpegr.cpp:696-706 (fill_gen_params)
+    const unsigned s = w < h ? w : h;
+    scale = s >= 8 ? s / 8 : 1;
+  }
+  const unsigned mw = w / scale, mh = h / scale;
+  if (mw == 0 || mh == 0 || mw % 8 || mh % 8)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the API-3 chain needs map dimensions that are multiples of 8 (%ux%u at scale factor %u); use the operators", mw, mh, scale);
+  if (sdr_bytes == 0 || sdr_bytes > 0xFFFFFFF0ull) return err_status(UHDR_CODEC_INVALID_PARAM, "received no (or too much) entropy-coded data");
+  UHDR_TRY(validate_image(hdr, "hdr intent"));
+  HIP_TRY(hipSetDevice(c->device));
+  const int nch = cfg.use_multi_channel_gainmap ? 3 : 1;
+  uhdr_raw_image_t dh;
+  const uint8_t* data = sdr_data;
+  if (dev) {
+    dh = *hdr;
+  } else {
+    if (c->resident_on) UHDR_TRY(resident_write_back_all(c));
+    UHDR_TRY(stage_in(c, 1, hdr, &dh, true));
+    UHDR_TRY(ensure(c->jpg[0], sdr_bytes + 64));
+    UHDR_TRY(fast_h2d(c, c->jpg[0].p, sdr_data, sdr_bytes));
+    data = (const uint8_t*)c->jpg[0].p;
+  }
+  // 1. the SDR intent's coefficients
+  for (int i = 0; i < 3; i++) {
+    UHDR_TRY(ensure(c->jpg[1 + i], (size_t)sb.blocks_w[i] * sb.blocks_h[i] * 128));
+    sb.coef[i] = (const int16_t*)c->jpg[1 + i].p;
+  }
+  c->huff_serial_ok = false;  // a scan the parallel decoder declines goes back to the caller (UNSUPPORTED_FEATURE), not to one lane
+  const uhdr_error_info_t hs = uhdr_hip_huffman_decode_dev(c, &sb, tables_of(sdr_jpeg), data, sdr_bytes);
+  c->huff_serial_ok = true;
+  if (hs.error_code != UHDR_CODEC_OK) return hs;
+  // 2. generation: from the coefficients, or from planes
+  const int sampling = is444 ? 444 : (vsamp == 2 ? 420 : 422);
+  GenParams p;
+  CoefSrc cs;
+  int use_base_cg = 1;
+  float hdr_white_nits = 0;
+  bool fused = !is444 && !api3_route_staged(sampling);
+  if (fused) {
+    uhdr_hip_jpeg_coefficients_t jc;
+    memset(&jc, 0, sizeof jc);
+    for (int i = 0; i < 3; i++) {
+      jc.coef[i] = sb.coef[i];
+      jc.blocks_w[i] = sb.blocks_w[i];
+      jc.blocks_h[i] = sb.blocks_h[i];
+      memcpy(jc.qtable[i], sdr_jpeg->qtable[i], sizeof jc.qtable[i]);
+    }
+    const uhdr_error_info_t pr = prepare_gen_coef(c, &jc, w, h, sampling, sdr_cg, &dh, &cfg, &p, &cs, &use_base_cg, &hdr_white_nits);
+    if (pr.error_code == UHDR_CODEC_UNSUPPORTED_FEATURE) fused = false;  // a geometry the coefficient kernel does not take: the planes after all
+    else if (pr.error_code != UHDR_CODEC_OK) return pr;
+  }
+  if (!fused) {  // three IDCT launches into an image of the SDR intent's sampling
+    size_t ppitch[3], poff[3], total = 0;
+    for (int i = 0; i < 3; i++) {
+      ppitch[i] = ((size_t)sb.blocks_w[i] * 8 + 63) & ~(size_t)63;
+      poff[i] = total;
+      total += ppitch[i] * (size_t)sb.blocks_h[i] * 8;
+    }
+    UHDR_TRY(ensure(c->jpg[4], total));
+    uhdr_raw_image_t bi;
+    memset(&bi, 0, sizeof bi);
+    bi.fmt = is444 ? UHDR_IMG_FMT_24bppYCbCr444 : (vsamp == 2 ? UHDR_IMG_FMT_12bppYCbCr420 : UHDR_IMG_FMT_16bppYCbCr422);
+    bi.cg = sdr_cg; bi.ct = UHDR_CT_SRGB; bi.range = UHDR_CR_FULL_RANGE;
+    bi.w = w; bi.h = h;
+    for (int i = 0; i < 3; i++) {
+      uint8_t* d = (uint8_t*)c->jpg[4].p + poff[i];
+      UHDR_TRY(uhdr_hip_idct_dequant_dev(c, sb.coef[i], sb.blocks_w[i], sb.blocks_h[i], sdr_jpeg->qtable[i], d, ppitch[i]));
+      bi.planes[i] = d;
+      bi.stride[i] = (unsigned int)ppitch[i];
+    }
+    UHDR_TRY(fill_gen_params(c, &bi, &dh, &cfg, &p, &use_base_cg, &hdr_white_nits));
+  }
+  if (p.map_w != mw || p.map_h != mh) return err_status(UHDR_CODEC_ERROR, "internal: map dimensions %ux%u / %ux%u", p.map_w, p.map_h, mw, mh);
+  auto pass = [&](bool two_pass) -> hipError_t {
+    ProfScope ps(c, "generate_gainmap");
+    return fused ? launch_generate_gainmap_coef(p, cs, vsamp, two_pass, c->stream) : launch_generate_gainmap(p, two_pass, c->stream);
+  };
+  // 3. the map's coefficients
+  const size_t nm = (size_t)(mw / 8) * (mh / 8);
+  const size_t nblocks[3] = {nm, nm, nm};
+  int16_t* coef[3] = {nullptr, nullptr, nullptr};
+  UHDR_TRY(carve_coef_arrays(c->enc[0], nblocks, nch, coef));
+  const bool one = cfg.preset == UHDR_USAGE_REALTIME;
+  if (one) {  // the byte map in context scratch, then the FDCT operators
+    UHDR_TRY(fill_onepass_range(c, &cfg, hdr_white_nits, use_base_cg, &p, md));
+    UHDR_TRY(ensure(c->scratch[7], (size_t)mw * mh * nch));
+    p.out = (uint8_t*)c->scratch[7].p;
+    p.out_stride = mw;
+    HIP_TRY(pass(false));
+    if (nch == 3) {
+      uhdr_raw_image_t rgb;
+      memset(&rgb, 0, sizeof rgb);
+      rgb.fmt = UHDR_IMG_FMT_24bppRGB888;
+      rgb.w = mw; rgb.h = mh;
+      rgb.planes[0] = p.out;
+      rgb.stride[0] = mw;
+      UHDR_TRY(uhdr_hip_fdct_quant_rgb_dev(c, &rgb, qt_map[0], qt_map[1], coef[0], coef[1], coef[2]));
+    } else {
+      UHDR_TRY(uhdr_hip_fdct_quant_dev(c, p.out, mw, (int)(mw / 8), (int)(mh / 8), qt_map[0], coef[0]));
+    }
+  } else {  // pass 1 -> range + tables -> map blocks, as encode_api1_fused_impl runs them; the 8-bit map is not asked for
+    UHDR_TRY(ensure(c->scratch[7], (size_t)mw * mh * nch * sizeof(float)));
+    UHDR_TRY(ensure(c->minmax, (6 + 2048 * 6) * sizeof(float)));
+    UHDR_TRY(ensure(c->affine, kAffineDevBytes));
+    UHDR_TRY(ensure(c->exchange, 256));
+    if (!c->h_mm) HIP_TRY(hipHostMalloc((void**)&c->h_mm, 9 * sizeof(float), hipHostMallocDefault));
+    p.gain_log2 = (float*)c->scratch[7].p;
+    p.minmax = (float*)c->minmax.p;
+    HIP_TRY(pass(true));
+    float* final_mm = (float*)((char*)c->exchange.p + 192);
+    MinmaxTableParams t;
+    memset(&t, 0, sizeof t);
+    t.do_reduce = t.do_finalize = t.do_table = 1;
+    t.partials = p.minmax + 6;
+    t.n_partials = fused ? gen_coef_partials_count(p) : gen_partials_count(p);
+    t.mm6 = p.minmax;
+    fill_finalize(&t, &cfg);
+    t.out_mm = final_mm;
+    t.dev = (AffineDev*)c->affine.p;
+    t.math_tab = c->d_math;
+    {
+      ProfScope ps(c, "generate_gainmap");
+      HIP_TRY(launch_minmax_table(t, c->stream));
+    }
+    {
+      ProfScope ps(c, "fdct_quant");
+      HIP_TRY(launch_map_blocks(p.gain_log2, (const AffineDev*)c->affine.p, c->d_math, nch, (int)(mw / 8), (int)(mh / 8), qt_map[0], qt_map[1], coef, nullptr, 0,
+                                c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(c->h_mm, final_mm, 9 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  // 4. the map's scan
+  uhdr_hip_jpeg_scan_t sm;
+  fill_scan(&sm, mw, mh, nch, 8, coef);
+  if (map_capacity > 0xFFFFFFF0u) map_capacity = 0xFFFFFFF0u;
+  size_t nms = 0;
+  uint8_t* out = map_scan;
+  if (!dev) {
+    UHDR_TRY(ensure(c->enc[2], map_capacity + 64));
+    out = (uint8_t*)c->enc[2].p;
+  }
+  const uhdr_error_info_t he = uhdr_hip_huffman_encode_dev(c, &sm, out, map_capacity, &nms);
+  *map_bytes = nms;
+  if (he.error_code != UHDR_CODEC_OK) {
+    (void)hipStreamSynchronize(c->stream);
+    return he;
+  }
+  if (!dev) HIP_TRY(hipMemcpyAsync(map_scan, out, nms, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (gainmap_desc) {  // what generateGainMap's freshly allocated image would say (jpegr.cpp:714-716); planes untouched
+    gainmap_desc->fmt = nch == 3 ? UHDR_IMG_FMT_24bppRGB888 : UHDR_IMG_FMT_8bppYCbCr400;
+    gainmap_desc->cg = hdr->cg; gainmap_desc->ct = hdr->ct; gainmap_desc->range = hdr->range;
+    gainmap_desc->w = mw; gainmap_desc->h = mh;
+  }
+  if (one) return ok_status();
+  float mm[6];
+  memcpy(mm, c->h_mm, sizeof mm);
+  note_table_stats(c, &cfg);
+  return generate_gainmap_finalize_md(&cfg, hdr->ct, use_base_cg, mm, md);
+}
+
+uhdr_error_info_t uhdr_hip_encode_api3_scans(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* sdr_jpeg, const uint8_t* sdr_data, size_t sdr_bytes,
+                                             uhdr_color_gamut_t sdr_cg, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                             const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* map_scan,
+                                             size_t map_capacity, size_t* map_bytes) {
+  return encode_api3_scans_impl(c, sdr_jpeg, sdr_data, sdr_bytes, sdr_cg, hdr, cfg, qt_map, md, gainmap_desc, map_scan, map_capacity, map_bytes, false);
+}
+uhdr_error_info_t uhdr_hip_encode_api3_scans_dev(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* sdr_jpeg, const uint8_t* sdr_data, size_t sdr_bytes,
+                                                 uhdr_color_gamut_t sdr_cg, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                 const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* map_scan,
+                                                 size_t map_capacity, size_t* map_bytes) {
+  return encode_api3_scans_impl(c, sdr_jpeg, sdr_data, sdr_bytes, sdr_cg, hdr, cfg, qt_map, md, gainmap_desc, map_scan, map_capacity, map_bytes, true);
 }
 
 // Host helper: a complete baseline JFIF file around entropy-coded data (marker order of jcmarker.c: SOI, APP0, DQT,

@@ -1,0 +1,237 @@
+// generateGainMap with the SDR intent still in JPEG coefficient form: JpegR::encodeJPEGR API-3
+// (lib/src/jpegr.cpp:327-385 of the reference) decodes the compressed SDR intent and hands the planes to generateGainMap
+// (jpegr.cpp:530-1050).  Here JpegDecoderHelper's dequantize + IDCT stage (jpegdecoderhelper.cpp:468-535) runs inside pass 1
+// (or the whole one-pass generation): the 8-bit SDR planes never exist in HBM.  The mirror of apply_quad_body<..., SRC = 1>
+// (apply_gainmap.hip) on the encode side.
+//
+// A WAVE takes a 128 x 16 pixel tile: 32 luma + 8 + 8 chroma blocks at 4:2:0 (VSAMP 2), 32 + 16 + 16 at 4:2:2 (VSAMP 1).  It
+// dequantises and inverse-transforms them eight blocks at a time (idct_core.h) into its own LDS tile, then produces the tile's
+// map pixels with generate_kernel's sequence of operations (generate_gainmap.hip): the SDR sample is what fetch_pixel returns
+// for the byte the stand-alone IDCT would have stored, box sums run dy outer / dx inner from 0.0f with one divide, and
+// everything behind the sample is the shared code of encode_core.h.  Scale factors 1, 2 and 4 divide the tile, so a box
+// never leaves it (the host declines the others).  Pixels of the coefficient grid beyond w x h are transformed and never
+// sampled: a map pixel exists only where its whole box lies inside the image.
+//
+// LDS per 512-thread workgroup: 25 KB of tables (GenLds) + 5.25 KB (4:2:0) / 6.25 KB (4:2:2) per wave for the tile and the
+// IDCT workspace = 68 / 76 KB two pass -> two workgroups (16 waves) per CU; the one-pass step table adds 16 KB -> one.
+#include "encode_core.h"
+#include "idct_core.h"
+#include "lds_copy.h"
+
+namespace uhdr {
+namespace {
+
+constexpr int kCoefBlock = 512;
+constexpr int kCoefWaves = kCoefBlock / 64;
+constexpr int kCoefMaxGrid = 2048;  // the host layer sizes the partials buffer for this many workgroups
+
+struct GenLds {
+  float srgb[kSrgbN];
+  float hdr[kInvOetfN];
+  UnormTables unorm;  // x / 255.0f, x / 1023.0f
+};
+
+// the SDR sample at pixel (lx, ly) of the wave's tile, as fetch_pixel<4:2:0 / 4:2:2> returns it for the stored bytes
+template <int VSAMP>
+__device__ __forceinline__ Color3 fetch_tile_pixel(const uint8_t* yt, const uint8_t* cbt, const uint8_t* crt, uint32_t lx, uint32_t ly) {
+  const int yy = yt[ly * 128 + lx];
+  const int uu = cbt[(ly / VSAMP) * 64 + lx / 2];
+  const int vv = crt[(ly / VSAMP) * 64 + lx / 2];
+  Color3 c;
+  c.r = (float)yy * (1 / 255.0f);
+  c.g = (float)(uu - 128) * (1 / 255.0f);
+  c.b = (float)(vv - 128) * (1 / 255.0f);
+  return c;
+}
+// sample_box (pixel_io.h) over the tile: map pixel (lx, ly) of the tile at scale factor s
+template <int VSAMP>
+__device__ __forceinline__ Color3 sample_tile_box(const uint8_t* yt, const uint8_t* cbt, const uint8_t* crt, uint32_t s, uint32_t lx, uint32_t ly) {
+  if (s == 1) return fetch_tile_pixel<VSAMP>(yt, cbt, crt, lx, ly);
+  Color3 e = {0.0f, 0.0f, 0.0f};
+  for (uint32_t dy = 0; dy < s; ++dy)
+    for (uint32_t dx = 0; dx < s; ++dx) {
+      const Color3 q = fetch_tile_pixel<VSAMP>(yt, cbt, crt, lx * s + dx, ly * s + dy);
+      e.r += q.r;
+      e.g += q.g;
+      e.b += q.b;
+    }
+  const float d = (float)(s * s);
+  e.r /= d;
+  e.g /= d;
+  e.b /= d;
+  return e;
+}
+
+// VSAMP: 2 = 4:2:0, 1 = 4:2:2.  HDRF: the HDR format (as generate_kernel's).  QUAD (P010 at scale factor 1 with a layout that
+// passes quad_layout_ok): one lane per 2 x 2 quad, the HDR side read with fetch_quad_p010 as generate_quad_kernel does.
+template <int VSAMP, int HDRF, bool TWO_PASS, bool QUAD>
+__global__ __launch_bounds__(kCoefBlock) void generate_coef_kernel(const GenParams p, const CoefSrc cs, float* partials) {
+  static_assert(!QUAD || HDRF == UHDR_IMG_FMT_24bppYCbCrP010, "the quad fetch is P010's");
+  constexpr int CROWS = 16 / VSAMP;  // chroma rows of a tile
+  constexpr int NC = 2 / VSAMP;      // eight-block units per chroma component
+  __shared__ GenLds L;
+  __shared__ uint2 s_gain8[TWO_PASS ? 1 : kStepTabMax];  // one pass: clamped gain -> map byte (host_tables.cpp)
+  __shared__ int s_ws[kCoefWaves][8 * 8 * 9];
+  __shared__ int s_q[3][64];
+  __shared__ __attribute__((aligned(8))) uint8_t s_yt[kCoefWaves][16 * 128];
+  __shared__ __attribute__((aligned(8))) uint8_t s_ct[kCoefWaves][2][CROWS * 64];
+  static_assert(sizeof(GenLds) + sizeof s_gain8 + sizeof s_ws + sizeof s_q + sizeof s_yt + sizeof s_ct + 256 <= (TWO_PASS ? 80 : 160) * 1024,
+                "two-pass workgroups are sized for two per CU, one-pass workgroups for one");
+  const uint32_t tid = threadIdx.x;
+  if constexpr (!TWO_PASS) stage_step_tab(s_gain8, p.gain8, tid, kCoefBlock);
+  for (uint32_t i = tid; i < kSrgbN; i += kCoefBlock) L.srgb[i] = p.srgb_lut[i];
+  if (p.hdr_inv_lut)
+    for (uint32_t i = tid; i < (uint32_t)p.hdr_inv_n; i += kCoefBlock) L.hdr[i] = p.hdr_inv_lut[i];
+  fill_unorm_tables(L.unorm, tid, kCoefBlock);
+  if (tid < 192) s_q[tid >> 6][tid & 63] = cs.q[tid >> 6][tid & 63];
+  __syncthreads();
+
+  const bool hdr_lut = p.hdr_inv_lut != nullptr, hdr_lut_4096 = p.hdr_inv_n == kInvOetfN;
+  float mn[3] = {UHDR_RATIO_MIN_INIT, UHDR_RATIO_MIN_INIT, UHDR_RATIO_MIN_INIT}, mx[3] = {UHDR_RATIO_MAX_INIT, UHDR_RATIO_MAX_INIT, UHDR_RATIO_MAX_INIT};
+  // one map pixel from the two samples: generate_kernel's sequence (the SDR intent of API-3 is never RGB)
+  auto emit = [&](Color3 s, Color3 h, uint32_t x, uint32_t y) {
+    s = yuv_to_rgb(s.r, s.g, s.b, p.sdr_yuv);
+    Color3 sl = linearise_hdr(s, L.srgb, true, false);
+    if (p.sdr_gamut_on) {
+      sl = mat3_apply(sl, p.sdr_gamut);
+      sl.r = clip_neg(sl.r); sl.g = clip_neg(sl.g); sl.b = clip_neg(sl.b);
+    }
+    if (!p.hdr_is_rgb) h = yuv_to_rgb(h.r, h.g, h.b, p.hdr_yuv);
+    Color3 hl = linearise_hdr(h, L.hdr, hdr_lut, hdr_lut_4096);
+    if (p.hdr_gamut_on) {
+      hl = mat3_apply(hl, p.hdr_gamut);
+      hl.r = clip_neg(hl.r); hl.g = clip_neg(hl.g); hl.b = clip_neg(hl.b);
+    }
+    gain_of_pixel<TWO_PASS>(sl, hl, p, p.math_tab, x, y, mn, mx, TWO_PASS ? nullptr : s_gain8);
+  };
+
+  const uint32_t lane = tid & 63;
+  const int wv = (int)__builtin_amdgcn_readfirstlane(tid >> 6);
+  int* ws = s_ws[wv];
+  uint8_t* yt = s_yt[wv];
+  uint8_t* cbt = s_ct[wv][0];
+  uint8_t* crt = s_ct[wv][1];
+  const int rr = (int)lane >> 3, rb = (int)lane & 7;
+  const uint32_t w = p.sdr.w, h = p.sdr.h, mw = p.map_w, mh = p.map_h;
+  const uint32_t tiles_x = (w + 127) >> 7, tiles_y = (h + 15) >> 4, ntiles = tiles_x * tiles_y;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kCoefWaves + (tid >> 6));
+  const uint32_t nwaves = gridDim.x * kCoefWaves;
+  for (uint32_t t = wave; t < ntiles; t += nwaves) {
+    const uint32_t ty = t / tiles_x, tx = t - ty * tiles_x;
+    {  // luma: block rows 2 ty, 2 ty + 1 x two halves of sixteen blocks (all four loads issued up front)
+      int q[8], v[4][8], big[4] = {};
+#pragma unroll
+      for (int c = 0; c < 8; c++) q[c] = s_q[0][rr * 8 + c];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int by = (int)(2 * ty) + (u >> 1);
+        idct::load_dequant_row(cs.coef[0], cs.bw[0], by, (int)(tx * 16) + (u & 1) * 8 + rb, rr, q, v[u], big[u], by < cs.bh[0]);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        uint32_t sm8[8];
+        idct::idct_wave(ws, v[u], big[u], rr, rb, sm8);
+        *(uint2*)(yt + ((u >> 1) * 8 + rr) * 128 + ((u & 1) * 8 + rb) * 8) =
+            make_uint2(sm8[0] | (sm8[1] << 8) | (sm8[2] << 16) | (sm8[3] << 24), sm8[4] | (sm8[5] << 8) | (sm8[6] << 16) | (sm8[7] << 24));
+      }
+    }
+    {  // chroma: block row ty (4:2:0) or rows 2 ty, 2 ty + 1 (4:2:2) of eight blocks, Cb then Cr
+      int q[2][8], v[2 * NC][8], big[2 * NC] = {};
+#pragma unroll
+      for (int k = 0; k < 2; k++)
+#pragma unroll
+        for (int c = 0; c < 8; c++) q[k][c] = s_q[1 + k][rr * 8 + c];
+#pragma unroll
+      for (int u = 0; u < 2 * NC; u++) {
+        const int k = u / NC, by = VSAMP == 2 ? (int)ty : (int)(2 * ty) + (u % NC);
+        idct::load_dequant_row(cs.coef[1 + k], cs.bw[1 + k], by, (int)(tx * 8) + rb, rr, q[k], v[u], big[u], by < cs.bh[1 + k]);
+      }
+#pragma unroll
+      for (int u = 0; u < 2 * NC; u++) {
+        uint32_t sm8[8];
+        idct::idct_wave(ws, v[u], big[u], rr, rb, sm8);
+        *(uint2*)((u / NC ? crt : cbt) + ((u % NC) * 8 + rr) * 64 + rb * 8) =
+            make_uint2(sm8[0] | (sm8[1] << 8) | (sm8[2] << 16) | (sm8[3] << 24), sm8[4] | (sm8[5] << 8) | (sm8[6] << 16) | (sm8[7] << 24));
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the tile is complete in LDS
+    if constexpr (QUAD) {  // eight quad rows of 64 quads
+      const uint32_t qx = tx * 64 + lane;
+#pragma unroll 1
+      for (uint32_t qr = 0; qr < 8; qr++) {
+        const uint32_t qy = ty * 8 + qr;
+        if (qx >= w / 2 || qy >= h / 2) continue;
+        const QuadYuv hq = fetch_quad_p010(p.hdr, qx, qy, &L.unorm);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++)
+          emit(fetch_tile_pixel<VSAMP>(yt, cbt, crt, 2 * lane + (k & 1), 2 * qr + (k >> 1)), hq.px[k], 2 * qx + (k & 1), 2 * qy + (k >> 1));
+      }
+    } else {  // one lane per map pixel, 64 consecutive pixels of a tile row at a time
+      const uint32_t s = p.scale, sh = 7u - (s >> 1);  // a tile is 128 >> (s / 2) map pixels wide: 128, 64, 32
+      const uint32_t tw = 1u << sh, npx = tw * (16u / s);
+#pragma unroll 1
+      for (uint32_t i = lane; i < npx; i += 64) {
+        const uint32_t ly = i >> sh, lx = i & (tw - 1);
+        const uint32_t x = tx * tw + lx, y = ty * (16u / s) + ly;
+        if (x >= mw || y >= mh) continue;
+        emit(sample_tile_box<VSAMP>(yt, cbt, crt, s, lx, ly), sample_box<HDRF>(p.hdr, s, x, y, &L.unorm), x, y);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();  // the next tile overwrites the LDS tile
+  }
+  if constexpr (TWO_PASS) reduce_block_minmax<kCoefBlock>(mn, mx, partials);
+}
+
+int coef_grid(const GenParams& p, bool two_pass) {
+  static int cus_of[64] = {};  // per device id, as gen_grid (generate_gainmap.hip)
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (cus_of[dev] == 0) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    cus_of[dev] = cus;
+  }
+  const uint32_t tiles = ((p.sdr.w + 127) / 128) * ((p.sdr.h + 15) / 16);
+  const uint32_t resident = (uint32_t)cus_of[dev] * (two_pass ? 2u : 1u);  // workgroups per CU: the LDS budget at the head of this file
+  uint32_t g = (tiles + kCoefWaves - 1) / kCoefWaves;
+  if (g > resident) g = resident;
+  if (g > (uint32_t)kCoefMaxGrid) g = kCoefMaxGrid;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
+bool coef_quad_path(const GenParams& p) { return p.scale == 1 && p.hdr.fmt == UHDR_IMG_FMT_24bppYCbCrP010 && quad_layout_ok(p.hdr); }
+
+template <int VSAMP, int HDRF, bool QUAD>
+void launch_coef_p(const GenParams& p, const CoefSrc& cs, bool two_pass, int grid, float* partials, hipStream_t s) {
+  if (two_pass) hipLaunchKernelGGL((generate_coef_kernel<VSAMP, HDRF, true, QUAD>), dim3(grid), dim3(kCoefBlock), 0, s, p, cs, partials);
+  else hipLaunchKernelGGL((generate_coef_kernel<VSAMP, HDRF, false, QUAD>), dim3(grid), dim3(kCoefBlock), 0, s, p, cs, partials);
+}
+template <int VSAMP>
+void launch_coef_h(const GenParams& p, const CoefSrc& cs, bool two_pass, int grid, float* partials, hipStream_t s) {
+  if (coef_quad_path(p)) return launch_coef_p<VSAMP, UHDR_IMG_FMT_24bppYCbCrP010, true>(p, cs, two_pass, grid, partials, s);
+  switch (p.hdr.fmt) {
+    case UHDR_IMG_FMT_24bppYCbCrP010: return launch_coef_p<VSAMP, UHDR_IMG_FMT_24bppYCbCrP010, false>(p, cs, two_pass, grid, partials, s);
+    case UHDR_IMG_FMT_32bppRGBA1010102: return launch_coef_p<VSAMP, UHDR_IMG_FMT_32bppRGBA1010102, false>(p, cs, two_pass, grid, partials, s);
+    default: return launch_coef_p<VSAMP, -1, false>(p, cs, two_pass, grid, partials, s);
+  }
+}
+
+}  // namespace
+
+int gen_coef_partials_count(const GenParams& p) { return coef_grid(p, true); }
+
+// p.sdr carries the geometry of the image the coefficients decode to (its planes are never dereferenced); p.scale is 1, 2 or 4 and
+// w, h are even (the host layer declines everything else).  Two pass: the ratio plane p.gain_log2 and gen_coef_partials_count(p) x 6
+// ratio extrema at p.minmax + 6, the contract of launch_generate_gainmap.
+hipError_t launch_generate_gainmap_coef(const GenParams& p, const CoefSrc& cs, int vsamp, bool two_pass, hipStream_t s) {
+  if ((p.scale != 1 && p.scale != 2 && p.scale != 4) || (vsamp != 1 && vsamp != 2) || p.sdr.w % 2 || p.sdr.h % 2) return hipErrorInvalidValue;
+  float* partials = two_pass ? p.minmax + 6 : nullptr;
+  const int grid = coef_grid(p, two_pass);
+  if (vsamp == 2) launch_coef_h<2>(p, cs, two_pass, grid, partials, s);
+  else launch_coef_h<1>(p, cs, two_pass, grid, partials, s);
+  return hipGetLastError();
+}
+
+}  // namespace uhdr

@@ -181,6 +181,63 @@ class UltraHdr:
         gm.sync_meta_from_raw()
         return md, gm
 
+    def generateGainMapFromCoefficients(self, coefs, qtables, w: int, h: int, sdr_cg: int, hdr_intent: Image, sampling: str = "420",
+                                        sdr_is_601=False, use_luminance=True, gm: Image = None):
+        """generateGainMap on a 4:2:0 (sampling "420") or 4:2:2 ("422": uhdr_hip_generate_gainmap_coef422_dev) SDR intent still in
+        coefficient form -- the compressed intent of an API-3 encode (jpegr.cpp:327-385) after its Huffman decode: coefs = three
+        int16 [blocks_h, blocks_w, 64] CUDA tensors (Y, Cb, Cr), qtables = their three quantization tables; the dequantize + IDCT
+        stage runs inside the kernel (uhdr_hip_generate_gainmap_coef_dev).  gm: the device image to fill (a fresh 64-aligned one
+        when None).  Returns (metadata, gainmap Image) == idct_dequant x 3 + generateGainMap, bit for bit."""
+        assert all(c.is_cuda for c in coefs) and _is_dev(hdr_intent)
+        if sampling not in ("420", "422"):
+            raise ValueError(f"sampling is '420' or '422', received {sampling!r}")
+        fn = self.lib.uhdr_hip_generate_gainmap_coef_dev if sampling == "420" else self.lib.uhdr_hip_generate_gainmap_coef422_dev
+        jc = A.JpegCoefficients()
+        for i in range(3):
+            jc.coef[i] = coefs[i].data_ptr()
+            jc.blocks_h[i], jc.blocks_w[i] = int(coefs[i].shape[0]), int(coefs[i].shape[1])
+            for k in range(64):
+                jc.qtable[i][k] = int(qtables[i][k])
+        if gm is None:
+            gm = self._map_image(w, h, hdr_intent.device)
+        md = A.GainmapMetadata()
+        cfg = self.encode_cfg(sdr_is_601, use_luminance)
+        self._call(True, fn, self.ctx.handle, C.byref(jc), w, h, sdr_cg, C.byref(hdr_intent.raw), C.byref(cfg), C.byref(md), C.byref(gm.raw))
+        gm.sync_meta_from_raw()
+        return md, gm
+
+    def encodeApi3Scans(self, sdr_hdr: "A.JpegHeader", sdr_data, sdr_cg: int, hdr_intent: Image, qt_map, out_map, use_luminance=True):
+        """JpegR::encodeJPEGR API-3 (jpegr.cpp:327-385) without the container in ONE C call: a compressed SDR intent (its parsed header
+        sdr_hdr and its entropy-coded bytes sdr_data) and a raw HDR intent -> the gain map's entropy-coded scan; the base image of the
+        file stays the caller's JPEG.  Device data (uhdr_hip_encode_api3_scans_dev): sdr_data and out_map are uint8 CUDA tensors,
+        hdr_intent a device image; returns (bytes of the map scan, metadata, gain-map description).  Host data
+        (uhdr_hip_encode_api3_scans): sdr_data is bytes / a uint8 array, out_map the capacity in bytes; returns (map scan, metadata,
+        gain-map description).  A UhdrError for a capacity that is too small carries the needed size in .needed.
+        UHDR_HIP_API3_ROUTE=fused|staged forces the coefficient kernel or the planes route for 4:2:0 / 4:2:2 files."""
+        qm = self._qt_pair(qt_map)
+        md, desc = A.GainmapMetadata(), A.RawImage()
+        cfg = self.encode_cfg(True, use_luminance)
+        nm = C.c_size_t(0)
+        dev = _is_dev(hdr_intent)
+        if dev:
+            assert sdr_data.is_cuda and out_map.is_cuda
+            src, nsrc, dst, cap = sdr_data.data_ptr(), int(sdr_data.numel()), out_map.data_ptr(), int(out_map.numel())
+            fn = self.lib.uhdr_hip_encode_api3_scans_dev
+        else:
+            src_arr = np.ascontiguousarray(np.frombuffer(sdr_data, dtype=np.uint8) if isinstance(sdr_data, (bytes, bytearray)) else sdr_data)
+            om = np.empty(max(1, int(out_map)), np.uint8)
+            src, nsrc, dst, cap = src_arr.ctypes.data, int(src_arr.size), om.ctypes.data, int(out_map)
+            fn = self.lib.uhdr_hip_encode_api3_scans
+        try:
+            self._call(dev, fn, self.ctx.handle, C.byref(sdr_hdr), C.c_void_p(src), nsrc, sdr_cg, C.byref(hdr_intent.raw), C.byref(cfg),
+                       C.c_void_p(qm.ctypes.data), C.byref(md), C.byref(desc), C.c_void_p(dst), cap, C.byref(nm))
+        except A.UhdrError as e:
+            e.needed = int(nm.value)
+            raise
+        if dev:
+            return int(nm.value), md, desc
+        return om[:nm.value].tobytes(), md, desc
+
     def encodeApi0Fused(self, hdr_intent: Image, want_sdr_rgba=True, use_luminance=False):
         """MI355X extension: toneMap + generateGainMap + convert_raw_input_to_ycbcr(4:4:4) of an API-0 encode
         (jpegr.cpp:202-251) in one pass over a device-resident RGBA1010102 / RGBA-F16 image (scale factor 1).
