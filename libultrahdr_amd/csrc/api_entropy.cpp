@@ -98,8 +98,7 @@ uhdr_error_info_t uhdr_hip_huffman_encode_dev(uhdr_hip_ctx_t* c, const uhdr_hip_
   a.ri = stream ? huff_stream_segment_mcus(bpm) : sc->restart_interval;
   a.blocks_per_mcu = bpm;
   a.nseg = (a.total_mcus + a.ri - 1) / a.ri;
-  a.tables = c->d_huff;
-  a.zigzag = (const uint8_t*)(c->d_huff + host::kHuffTabWords);
+  a.tables = c->d_huff;  // (the zig-zag table behind them is the decoder's: the encoder's kernels compile the order in, huff_zigzag.h)
   if (stream) {
     // scratch[4]: the unstuffed stream (as many bytes as the caller's buffer holds: stuffing only adds bytes);
     // scratch[5]: segment starts (nseg + 1) | stuffed size | meta (4 words) | segment bit counts | chunk counts

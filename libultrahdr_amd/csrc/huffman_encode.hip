@@ -22,6 +22,7 @@
 //      prefix sum of the 0xFF counts) and written to the interval's slot in device memory.
 // Two launches of that kernel (size classes of the LDS bit buffer, see below), then a tiny kernel turns the interval
 // sizes into offsets and a gather kernel copies the slots into the final stream with the RSTn markers in between.
+#include "huff_zigzag.h"
 #include "lds_copy.h"
 #include "wg_scan.h"
 #include "uhdr_types.h"
@@ -42,64 +43,120 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
   return v;
 }
 
+// A lane stages its block's row in ZIG-ZAG order: halfword k of the row is zig-zag position k.  The block arrives in natural order in
+// eight 16-byte registers; with the order compiled in (huff_zigzag.h) every row word is one halfword select from two of them with constant
+// selectors, and neither the occupancy map nor the walk needs a position -> index lookup.  Returns the DC term.
+__device__ __forceinline__ int stage_row_zigzag(uint32_t* crow, const uint4* __restrict__ src) {
+  uint4 q[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) q[i] = src[i];
+  const auto word = [&](int n) -> uint32_t {  // natural-order word n (n is a constant after unrolling)
+    const uint4& v = q[n >> 2];
+    return (n & 3) == 0 ? v.x : (n & 3) == 1 ? v.y : (n & 3) == 2 ? v.z : v.w;
+  };
+#pragma unroll
+  for (int j = 0; j < 32; j++) {
+    const int lo = kHuffZigzag[2 * j], hi = kHuffZigzag[2 * j + 1];
+    const uint32_t l16 = (lo & 1) ? word(lo >> 1) >> 16 : word(lo >> 1) & 0xffffu;
+    const uint32_t h16 = (hi & 1) ? word(hi >> 1) & 0xffff0000u : word(hi >> 1) << 16;
+    crow[j] = l16 | h16;
+  }
+  return (int)(int16_t)(q[0].x & 0xffffu);
+}
+
 // Round 5: the walk visits the NON-ZERO coefficients only.  A lane used to step through all 63 AC positions of its block (a
 // zig-zag lookup and a coefficient read from LDS per step, twice: once for the lengths, once to emit) although a busy 4:2:0 q95
 // block has ~25 of them non-zero and a gain-map block three.  The wave first builds every block's 64-bit occupancy map in
-// zig-zag order cooperatively -- lane L reads zig-zag position L of block b, one v_cmp gives the whole map of block b as a wave
-// mask (64 x ~6 instructions for 64 blocks) -- and the walk then hops from set bit to set bit (run = distance - 1).
-// s_coef: the wave's staged blocks, kCoefRow words per block; zz_of_lane = natural index of zig-zag position `lane`.
-__device__ __forceinline__ uint64_t zigzag_nonzero_map(const uint32_t* s_coef, uint32_t zz_of_lane, uint32_t lane) {
+// zig-zag order cooperatively -- lane L reads zig-zag position L of block b (halfword L of its row), one v_cmp gives the whole map
+// of block b as a wave mask -- and the walk then hops from set bit to set bit (run = distance - 1).
+// s_coef: the wave's staged blocks, kCoefRow words per block.
+__device__ __forceinline__ uint64_t zigzag_nonzero_map(const uint32_t* s_coef, uint32_t lane) {
   uint64_t mine = 0;
-  const uint32_t word = zz_of_lane >> 1, sh = (zz_of_lane & 1u) * 16u;
-#pragma unroll 4
+  const uint16_t* col = (const uint16_t*)s_coef + lane;
+#pragma unroll 8
   for (uint32_t b = 0; b < (uint32_t)kSegBlocks; b++) {
-    const uint32_t v = (s_coef[b * kCoefRow + word] >> sh) & 0xffffu;
+    const uint32_t v = col[b * (2 * kCoefRow)];
     const uint64_t m = __builtin_amdgcn_ballot_w64(v != 0);
     if (lane == b) mine = m;
   }
   return mine;
 }
-// jchuff.c encode_one_block as a walk that reports every (code, length) pair to `put`; nz: the block's occupancy map (bit k =
-// zig-zag position k holds a non-zero coefficient)
+// jchuff.c encode_one_block as a walk that reports (code, length) pairs to `put`; nz: the block's occupancy map (bit k = zig-zag position
+// k holds a non-zero coefficient); coef_row: the block's row, zig-zag order.  A symbol and the value bits behind it are reported as ONE
+// pair (at most 16 + 10 bits for an AC term, 11 + 11 for the DC term, so a 64-bit accumulator that holds less than 32 bits takes it whole).
+// The AC terms are two dependent LDS reads each (the coefficient, then its run/size code), and a lane used to wait for both, one after
+// the other, before it touched the next term.  The walk is software-pipelined two stages deep instead: one step issues the coefficient
+// read of the term after next (its position comes from the map alone), issues the code read of the next term (whose coefficient has
+// arrived meanwhile) and consumes the code of the current term, read one step ago -- it only ever waits for loads of earlier steps.
+// Positions beyond the last term are clamped to 63 (inside the row); what is read there is never coded.
 template <typename Put>
 __device__ __forceinline__ void walk_block(const uint32_t* dct, const uint32_t* act, int dc_diff, bool real, const uint32_t* coef_row,
-                                           const uint8_t* zz, uint64_t nz, uint32_t& out_of_range, Put put) {
+                                           uint64_t nz, uint32_t& out_of_range, Put put) {
+  const uint16_t* row = (const uint16_t*)coef_row;
   int temp = dc_diff, temp2 = dc_diff;
   if (temp < 0) { temp = -temp; temp2--; }
-  uint32_t nbits = 32u - (uint32_t)__clz(temp);  // 0 for temp == 0
-  out_of_range |= nbits > 11u;                   // jchuff.c: ERREXIT(JERR_BAD_DCT_COEF) beyond MAX_COEF_BITS + 1
-  uint32_t e = dct[nbits & 15u];
-  put(e & 0xffffu, e >> 16);
-  if (nbits) put((uint32_t)temp2 & ((1u << nbits) - 1u), nbits);
-  uint32_t prev = 0;  // zig-zag position of the last coefficient coded (0: the DC term)
-  if (real) {
-    uint64_t m = nz & ~1ull;
-    while (m != 0) {
-      const uint32_t k = (uint32_t)__builtin_ctzll(m);
-      m &= m - 1ull;
-      uint32_t r = k - prev - 1u;  // zeros since the last coefficient
-      prev = k;
-      const uint32_t idx = zz[k];
-      const uint32_t wd = coef_row[idx >> 1];
-      temp = (idx & 1u) ? ((int)wd >> 16) : (int)(int16_t)(wd & 0xffffu);
-      while (r > 15) {
-        e = act[0xf0];
-        put(e & 0xffffu, e >> 16);
-        r -= 16;
-      }
-      temp2 = temp;
-      if (temp < 0) { temp = -temp; temp2--; }
-      nbits = 32u - (uint32_t)__clz(temp);
-      out_of_range |= nbits > 10u;  // MAX_COEF_BITS
-      e = act[((r << 4) + nbits) & 255u];
-      put(e & 0xffffu, e >> 16);
-      put((uint32_t)temp2 & ((1u << (nbits & 31u)) - 1u), nbits);
+  const uint32_t nbits = 32u - (uint32_t)__clz(temp);  // 0 for temp == 0
+  out_of_range |= nbits > 11u;                         // jchuff.c: ERREXIT(JERR_BAD_DCT_COEF) beyond MAX_COEF_BITS + 1
+  const uint32_t e = dct[nbits & 15u], e_eob = act[0];
+  uint64_t m = real ? nz & ~1ull : 0ull;
+  const bool eob = (m >> 63) == 0;                     // trailing zeros (a dummy block: all 63 AC terms): the last term is not at position 63
+  uint32_t left = (uint32_t)__builtin_popcountll(m);   // AC terms
+  const auto next_pos = [&]() -> uint32_t {            // (the bit at 63 only decides when the map has run out: the clamp)
+    const uint32_t k = (uint32_t)__builtin_ctzll(m | (1ull << 63));
+    m &= m - 1ull;
+    return k;
+  };
+  const auto size_of = [](uint16_t raw, uint32_t& bits) -> uint32_t {  // size category; bits = the value's low bits as jchuff.c sends them
+    int t = (int)(int16_t)raw, t2 = t;
+    if (t < 0) { t = -t; t2--; }
+    const uint32_t nb = 32u - (uint32_t)__clz(t);
+    bits = (uint32_t)t2 & ((1u << (nb & 31u)) - 1u);
+    return nb;
+  };
+  // prologue: term 0's coefficient and code, term 1's coefficient, term 2's position
+  uint32_t kA = 0, kB = 0, kC = 0, nbA = 0, bitsA = 0, rA = 0, e_zrl = 0, max_nb = 0;
+  uint16_t v0 = 0, v1 = 0;
+  uint32_t e0 = 0, e1 = 0;  // coefficients (raw halfwords) and codes in flight: the two steps below swap their roles
+  if (left) {
+    kA = next_pos();
+    const uint16_t vA = row[kA];
+    kB = next_pos();
+    v0 = row[kB];
+    kC = next_pos();
+    e_zrl = act[0xf0];
+    rA = kA - 1u;  // zeros since the DC term
+    nbA = size_of(vA, bitsA);
+    e0 = act[((rA << 4) + nbA) & 255u];
+  }
+  put(((e & 0xffffu) << (nbits & 31u)) | ((uint32_t)temp2 & ((1u << (nbits & 31u)) - 1u)), (e >> 16) + nbits);
+  // one term: v_next arrived (read one step ago), v_after and e_next are issued here and not waited for, e_cur was issued one step ago.
+  // (Two steps per loop trip with the registers' roles exchanged: with one, the hand-over "e_cur = e_next" at the end of the trip is a
+  // register copy that waits for the load just issued.)
+  const auto step = [&](uint16_t v_next, uint16_t& v_after, uint32_t e_cur, uint32_t& e_next) {
+    v_after = row[kC];  // the term after next
+    uint32_t bitsB;
+    const uint32_t rB = kB - kA - 1u, nbB = size_of(v_next, bitsB);  // the next term (beyond the last: discarded)
+    e_next = act[((rB << 4) + nbB) & 255u];
+    // the current term
+    uint32_t r = rA;  // zeros since the last coefficient
+    while (r > 15) {
+      put(e_zrl & 0xffffu, e_zrl >> 16);
+      r -= 16;
     }
+    max_nb = max(max_nb, nbA);
+    put(((e_cur & 0xffffu) << nbA) | bitsA, (e_cur >> 16) + nbA);
+    kA = kB; rA = rB; nbA = nbB; bitsA = bitsB;
+    kB = kC;
+    kC = next_pos();
+  };
+  while (left != 0) {
+    step(v0, v1, e0, e1);
+    if (--left == 0) break;
+    step(v1, v0, e1, e0);
+    --left;
   }
-  if (prev < 63u) {  // trailing zeros (a dummy block: all 63 AC terms): EOB
-    e = act[0];
-    put(e & 0xffffu, e >> 16);
-  }
+  out_of_range |= max_nb > 10u;  // MAX_COEF_BITS
+  if (eob) put(e_eob & 0xffffu, e_eob >> 16);
 }
 
 // Size classes: almost every interval of a real image needs a small fraction of the worst-case bit buffer, and LDS per
@@ -121,10 +178,8 @@ __global__ __launch_bounds__(64) void huff_encode_kernel(const HuffArgs a) {
   __shared__ int s_dc[kSegBlocks];
   __shared__ int s_real[kSegBlocks];
   __shared__ uint32_t s_gbits[kSegBlocks];  // bits of group g's interval
-  __shared__ uint8_t s_zz[64];
   const uint32_t lane = threadIdx.x;
   copy_words_to_lds<4>(s_tab, a.tables, 2 * (16 + 256), lane, 64);
-  s_zz[lane] = a.zigzag[lane];
   const int bpm = a.blocks_per_mcu;
   const int per = a.ri * bpm;                                // blocks per interval (<= 64, checked by the host)
   const int G = (RETRY || per > 32) ? 1 : 64 / per;          // intervals per wavefront
@@ -152,16 +207,10 @@ __global__ __launch_bounds__(64) void huff_encode_kernel(const HuffArgs a) {
     const int by = my * vs + yi, bx = mx * hs + xi;
     const bool real = active && by < a.bh[c] && bx < a.bw[c];
     uint32_t* crow = s_coef + lane * kCoefRow;
-    if (real) {
-      const uint4* src = (const uint4*)(a.coef[c] + ((size_t)by * a.bw[c] + bx) * 64);
-#pragma unroll
-      for (int i = 0; i < 8; i++) {
-        const uint4 q = src[i];
-        crow[4 * i] = q.x; crow[4 * i + 1] = q.y; crow[4 * i + 2] = q.z; crow[4 * i + 3] = q.w;
-      }
-    }
+    int dc0 = 0;
+    if (real) dc0 = stage_row_zigzag(crow, (const uint4*)(a.coef[c] + ((size_t)by * a.bw[c] + bx) * 64));
     s_real[lane] = real ? 1 : 0;
-    s_dc[lane] = real ? (int)(int16_t)(crow[0] & 0xffffu) : 0;
+    s_dc[lane] = dc0;
     __syncthreads();
     // dummy blocks (jctrans.c compress_output): DC of the previous block of the MCU; the first block of a component
     // inside an MCU is always real, so the search is bounded by the component's block count (and stays inside the MCU)
@@ -183,11 +232,11 @@ __global__ __launch_bounds__(64) void huff_encode_kernel(const HuffArgs a) {
     const uint32_t* dct = s_tab + (c ? (16 + 256) : 0);
     const uint32_t* act = dct + 16;
     const int diff = dcv - pred;
-    const uint64_t nz = zigzag_nonzero_map(s_coef, s_zz[lane], lane);  // (rows of lanes without a real block hold stale words: never walked)
+    const uint64_t nz = zigzag_nonzero_map(s_coef, lane);  // (rows of lanes without a real block hold stale words: never walked)
 
     // ---- pass 1: code lengths -> bit offsets inside the lane's interval ---------------------------------------------------
     uint32_t len = 0, oob = 0;
-    if (active) walk_block(dct, act, diff, real, crow, s_zz, nz, oob, [&](uint32_t, uint32_t n) { len += n; });
+    if (active) walk_block(dct, act, diff, real, crow, nz, oob, [&](uint32_t, uint32_t n) { len += n; });
     const uint32_t incl = wave_incl_scan(len, lane);
     // every lane takes part in both shuffles (a lane that sits out cannot be read from)
     const int first = g * per, last = min(first + per - 1, 63);
@@ -211,7 +260,7 @@ __global__ __launch_bounds__(64) void huff_encode_kernel(const HuffArgs a) {
     if (active && fits) {
       uint64_t acc = 0;
       uint32_t cnt = off & 31u, w = gbase + (off >> 5);
-      walk_block(dct, act, diff, real, crow, s_zz, nz, oob, [&](uint32_t code, uint32_t n) {
+      walk_block(dct, act, diff, real, crow, nz, oob, [&](uint32_t code, uint32_t n) {
         acc = (acc << n) | (uint64_t)code;
         cnt += n;
         if (cnt >= 32u) {
@@ -354,13 +403,11 @@ __global__ __launch_bounds__(64) void huff_stream_kernel(const HuffArgs a, const
   __shared__ uint32_t s_bits[PASS == 0 ? 1 : kSegBlocks * WORDS + 2];
   __shared__ int s_dc[kSegBlocks];
   __shared__ int s_real[kSegBlocks];
-  __shared__ uint8_t s_zz[64];
   const uint32_t lane = threadIdx.x;
   if constexpr (PASS == 2) {
     if (t.meta[3] == 0) return;  // no segment of the large size class (round 6: this launch used to stage its tables and walk the segment list for nothing)
   }
   copy_words_to_lds<4>(s_tab, a.tables, 2 * (16 + 256), lane, 64);
-  s_zz[lane] = a.zigzag[lane];
   const int bpm = a.blocks_per_mcu;
   constexpr uint32_t kCapBits = (uint32_t)(kSegBlocks * WORDS) * 32u;
   for (int seg = (int)blockIdx.x; seg < a.nseg; seg += (int)gridDim.x) {
@@ -388,20 +435,14 @@ __global__ __launch_bounds__(64) void huff_stream_kernel(const HuffArgs a, const
     const int by = my * vs + yi, bx = mx * hs + xi;
     const bool real = valid && by < a.bh[c] && bx < a.bw[c];
     uint32_t* crow = s_coef + lane * kCoefRow;
+    int dc0 = 0;
     if (real) {
       const uint4* src = (const uint4*)(a.coef[c] + ((size_t)by * a.bw[c] + bx) * 64);
-      if (emits) {
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-          const uint4 q = src[i];
-          crow[4 * i] = q.x; crow[4 * i + 1] = q.y; crow[4 * i + 2] = q.z; crow[4 * i + 3] = q.w;
-        }
-      } else {
-        crow[0] = *(const uint32_t*)src;  // the MCU in front of the segment: its DC values are all that matters
-      }
+      if (emits) dc0 = stage_row_zigzag(crow, src);
+      else dc0 = (int)(int16_t)(*(const uint32_t*)src & 0xffffu);  // the MCU in front of the segment: its DC values are all that matters
     }
     s_real[lane] = real ? 1 : 0;
-    s_dc[lane] = real ? (int)(int16_t)(crow[0] & 0xffffu) : 0;
+    s_dc[lane] = dc0;
     __syncthreads();
     int dcv = s_dc[lane];
     if (valid && !real) {  // dummy block (jctrans.c compress_output): DC of the previous block of the MCU
@@ -420,9 +461,9 @@ __global__ __launch_bounds__(64) void huff_stream_kernel(const HuffArgs a, const
     const uint32_t* dct = s_tab + (c ? (16 + 256) : 0);
     const uint32_t* act = dct + 16;
     const int diff = dcv - pred;
-    const uint64_t nz = zigzag_nonzero_map(s_coef, s_zz[lane], lane);  // (only rows of emitting lanes with a real block are ever walked)
+    const uint64_t nz = zigzag_nonzero_map(s_coef, lane);  // (only rows of emitting lanes with a real block are ever walked)
     uint32_t len = 0, oob = 0;
-    if (emits) walk_block(dct, act, diff, real, crow, s_zz, nz, oob, [&](uint32_t, uint32_t n) { len += n; });
+    if (emits) walk_block(dct, act, diff, real, crow, nz, oob, [&](uint32_t, uint32_t n) { len += n; });
     const uint32_t incl = wave_incl_scan(len, lane);
     const uint32_t total_bits = (uint32_t)__shfl((int)incl, 63, 64);
     if constexpr (PASS == 0) {
@@ -438,7 +479,7 @@ __global__ __launch_bounds__(64) void huff_stream_kernel(const HuffArgs a, const
         const uint32_t off = phase + incl - len;
         uint64_t acc = 0;
         uint32_t cnt = off & 31u, w = off >> 5;
-        walk_block(dct, act, diff, real, crow, s_zz, nz, oob, [&](uint32_t code, uint32_t n) {
+        walk_block(dct, act, diff, real, crow, nz, oob, [&](uint32_t code, uint32_t n) {
           acc = (acc << n) | (uint64_t)code;
           cnt += n;
           if (cnt >= 32u) {
@@ -485,11 +526,9 @@ __device__ __forceinline__ void wave_sync() {
 __global__ __launch_bounds__(64 * kWalkSegs) void huff_stream_walk_kernel(const HuffArgs a, const HuffStream t) {
   __shared__ __attribute__((aligned(16))) uint32_t s_tab[2 * (16 + 256)];
   __shared__ uint32_t s_coef_all[kWalkSegs][kSegBlocks * kCoefRow];
-  __shared__ uint32_t s_bits_all[kWalkSegs][kSlotWords];
-  __shared__ uint8_t s_zz[64];
+  __shared__ __attribute__((aligned(16))) uint32_t s_bits_all[kWalkSegs][kSlotWords];
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   copy_words_to_lds<4>(s_tab, a.tables, 2 * (16 + 256), threadIdx.x, 64 * kWalkSegs);
-  if (threadIdx.x < 64) s_zz[threadIdx.x] = a.zigzag[threadIdx.x];
   __syncthreads();  // (the only workgroup barrier)
   uint32_t* s_coef = s_coef_all[wv];
   uint32_t* s_bits = s_bits_all[wv];
@@ -506,7 +545,6 @@ __global__ __launch_bounds__(64 * kWalkSegs) void huff_stream_walk_kernel(const 
   const int pred_lane = (kk > 0 ? (int)lane - 1 : (int)lane - bpm + hs * vs - 1) & 63;
   const uint32_t* dct = s_tab + (c ? (16 + 256) : 0);
   const uint32_t* act = dct + 16;
-  const uint32_t zz_of_lane = s_zz[lane];
   uint32_t* crow = s_coef + lane * kCoefRow;
   for (int seg = (int)blockIdx.x * kWalkSegs + (int)wv; seg < a.nseg; seg += (int)gridDim.x * kWalkSegs) {
     wave_sync();  // the previous segment's LDS contents are dead
@@ -521,12 +559,7 @@ __global__ __launch_bounds__(64 * kWalkSegs) void huff_stream_walk_kernel(const 
     if (real) {
       const uint4* src = (const uint4*)(a.coef[c] + ((size_t)by * a.bw[c] + bx) * 64);
       if (emits) {
-        uint4 q[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) q[i] = src[i];
-#pragma unroll
-        for (int i = 0; i < 8; i++) { crow[4 * i] = q[i].x; crow[4 * i + 1] = q[i].y; crow[4 * i + 2] = q[i].z; crow[4 * i + 3] = q[i].w; }
-        dc0 = (int)(int16_t)(q[0].x & 0xffffu);
+        dc0 = stage_row_zigzag(crow, src);
       } else {
         dc0 = (int)(int16_t)(*(const uint32_t*)src & 0xffffu);  // the MCU in front of the segment: its DC values are all that matters
       }
@@ -543,9 +576,9 @@ __global__ __launch_bounds__(64 * kWalkSegs) void huff_stream_walk_kernel(const 
     const int pred_v = __shfl(dcv, pred_lane, 64);  // (0 in front of MCU 0: those lanes are not valid)
     const int diff = dcv - (emits ? pred_v : 0);
     wave_sync();  // the staged rows are visible to the whole wave
-    const uint64_t nz = zigzag_nonzero_map(s_coef, zz_of_lane, lane);  // (only rows of emitting lanes with a real block are ever walked)
+    const uint64_t nz = zigzag_nonzero_map(s_coef, lane);  // (only rows of emitting lanes with a real block are ever walked)
     uint32_t len = 0, oob = 0;
-    if (emits) walk_block(dct, act, diff, real, crow, s_zz, nz, oob, [&](uint32_t, uint32_t n) { len += n; });
+    if (emits) walk_block(dct, act, diff, real, crow, nz, oob, [&](uint32_t, uint32_t n) { len += n; });
     const uint32_t incl = wave_incl_scan(len, lane);
     const uint32_t total_bits = (uint32_t)__shfl((int)incl, 63, 64);
     const bool bad = __builtin_amdgcn_ballot_w64(oob != 0) != 0;
@@ -558,7 +591,7 @@ __global__ __launch_bounds__(64 * kWalkSegs) void huff_stream_walk_kernel(const 
       const uint32_t off = incl - len;
       uint64_t acc = 0;
       uint32_t cnt = off & 31u, w = off >> 5;
-      walk_block(dct, act, diff, real, crow, s_zz, nz, oob, [&](uint32_t code, uint32_t n) {
+      walk_block(dct, act, diff, real, crow, nz, oob, [&](uint32_t code, uint32_t n) {
         acc = (acc << n) | (uint64_t)code;
         cnt += n;
         if (cnt >= 32u) {
@@ -570,7 +603,7 @@ __global__ __launch_bounds__(64 * kWalkSegs) void huff_stream_walk_kernel(const 
     }
     wave_sync();
     uint32_t* slot = t.slots + (size_t)seg * (size_t)kSlotWords;
-    for (uint32_t i = lane; i < nwords; i += 64) slot[i] = s_bits[i];
+    copy_words_from_lds<4>(slot, s_bits, nwords, lane, 64);  // (up to three words behind nwords travel along: inside the slot, never read)
   }
 }
 

@@ -10,12 +10,9 @@
 
 namespace uhdr {
 
-// nwords % 4 == 0; src and dst 16-byte aligned
-template <int UNROLL = 8>
-__device__ __forceinline__ void copy_words_to_lds(uint32_t* dst, const uint32_t* __restrict__ src, uint32_t nwords, uint32_t tid, uint32_t nthreads) {
-  const uint4* s4 = (const uint4*)src;
-  uint4* d4 = (uint4*)dst;
-  const uint32_t nv = nwords >> 2;
+// nv 16-byte elements, either direction: UNROLL loads in flight, then UNROLL unconditional stores
+template <int UNROLL>
+__device__ __forceinline__ void copy_vec16(uint4* d4, const uint4* __restrict__ s4, uint32_t nv, uint32_t tid, uint32_t nthreads) {
   for (uint32_t i = tid; i < nv; i += UNROLL * nthreads) {
     uint4 v[UNROLL];
 #pragma unroll
@@ -32,6 +29,19 @@ __device__ __forceinline__ void copy_words_to_lds(uint32_t* dst, const uint32_t*
       d4[j < nv ? j : i] = v[u];
     }
   }
+}
+
+// nwords % 4 == 0; src and dst 16-byte aligned
+template <int UNROLL = 8>
+__device__ __forceinline__ void copy_words_to_lds(uint32_t* dst, const uint32_t* __restrict__ src, uint32_t nwords, uint32_t tid, uint32_t nthreads) {
+  copy_vec16<UNROLL>((uint4*)dst, (const uint4*)src, nwords >> 2, tid, nthreads);
+}
+
+// LDS -> global memory in the same form: all of a thread's LDS reads in flight before its first store.  The word count is rounded UP to
+// a multiple of four (both buffers 16-byte aligned and that much longer; the words behind nwords are whatever the LDS held).
+template <int UNROLL = 4>
+__device__ __forceinline__ void copy_words_from_lds(uint32_t* __restrict__ dst, const uint32_t* src, uint32_t nwords, uint32_t tid, uint32_t nthreads) {
+  copy_vec16<UNROLL>((uint4*)dst, (const uint4*)src, (nwords + 3u) >> 2, tid, nthreads);
 }
 
 // Any word count, any alignment: 16-byte loads when both sides allow it, else dword loads -- UNROLL of them in flight either way.

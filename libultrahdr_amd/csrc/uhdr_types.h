@@ -332,7 +332,6 @@ struct HuffArgs {
   int blocks_per_mcu;
   int nseg;                // restart intervals
   const uint32_t* tables;  // host::jpeg_huff_code_tables()
-  const uint8_t* zigzag;   // zig-zag position -> natural index
   uint8_t* slots;          // nseg x slot_stride bytes of scratch
   uint32_t slot_stride;
   uint32_t* seg_bytes;     // [nseg] stuffed bytes per interval (0xFFFFFFFF: coefficients outside the baseline range)

@@ -26,7 +26,7 @@ for i in (1, 2):
     acc = collections.OrderedDict()
     for r in rows:
         name = r[ik].replace("uhdr::(anonymous namespace)::", "").replace("void ", "").split("(")[0]
-        if not any(t in name for t in ("hyp_", "sync_write2", "huff_stream_kernel", "coef_place")):
+        if not any(t in name for t in ("hyp_", "sync_write2", "huff_st", "coef_place")):
             continue
         key = (name[:40], r[ig] if ig is not None else 0, r[ic])
         a = acc.setdefault(key, [0, 0.0]); a[0] += 1; a[1] += r[iv]
