@@ -601,7 +601,9 @@ uhdr_error_info_t uhdr_hip_generate_gainmap_coef422_dev(uhdr_hip_ctx_t* ctx, con
  * an MCU needs beyond the array are libjpeg's dummy blocks.  One component: non-interleaved scan (an MCU is a block).
  * out: DEVICE buffer; receives everything between the SOS header and EOI, RSTn markers included; *out_bytes its
  * length (UHDR_CODEC_MEM_ERROR with the needed size in *out_bytes when out_capacity is too small).  Synchronous.
- * Coefficients must be in the baseline range (as an 8-bit FDCT produces): UHDR_CODEC_INVALID_PARAM otherwise. */
+ * Coefficients must be in the baseline range (as an 8-bit FDCT produces): UHDR_CODEC_INVALID_PARAM otherwise.
+ * An MCU holds at most 10 blocks (T.81 B.2.3): all three components at 2x2 (12 blocks) is UHDR_CODEC_INVALID_PARAM at every entry
+ * point that takes a scan description, and uhdr_hip_jpeg_parse returns -7 for such a file. */
 typedef struct uhdr_hip_jpeg_scan {
   int num_components;     /* 1 or 3 */
   const int16_t* coef[3];

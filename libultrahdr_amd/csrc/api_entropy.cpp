@@ -25,6 +25,8 @@ uhdr_error_info_t uhdr_api::check_scan(const uhdr_hip_jpeg_scan_t* sc, bool need
       return err_status(UHDR_CODEC_INVALID_PARAM, "coefficient buffer %d is null or not 16-byte aligned", i);
     if (sc->blocks_w[i] < 1 || sc->blocks_h[i] < 1) return err_status(UHDR_CODEC_INVALID_PARAM, "component %d: empty block grid", i);
   }
+  // T.81 B.2.3: an interleaved MCU holds at most 10 blocks (all three components at 2x2 would be 12; libjpeg refuses such a file)
+  if (bpm > 10) return err_status(UHDR_CODEC_INVALID_PARAM, "an MCU holds at most 10 blocks (T.81 B.2.3), received %d", bpm);
   if (sc->num_components == 1) {  // non-interleaved: an MCU is one block (jcmaster.c per_scan_setup)
     *mcus_per_row = sc->blocks_w[0];
     *mcu_rows = sc->blocks_h[0];

@@ -74,6 +74,11 @@ int uhdr_hip_jpeg_parse(const uint8_t* file, size_t size, uhdr_hip_jpeg_header_t
         comp_tq[c] = seg[8 + 3 * c];
         if (out->scan.h_samp[c] < 1 || out->scan.h_samp[c] > 2 || out->scan.v_samp[c] < 1 || out->scan.v_samp[c] > 2 || comp_tq[c] > 3) return -7;
       }
+      if (nc == 3) {  // T.81 B.2.3: an interleaved MCU holds at most 10 blocks (libjpeg refuses such a file as well)
+        int bpm = 0;
+        for (int c = 0; c < 3; c++) bpm += out->scan.h_samp[c] * out->scan.v_samp[c];
+        if (bpm > 10) return -7;
+      }
       have_sof = true;
     } else if ((m >= 0xc1 && m <= 0xcf) && m != 0xc4 && m != 0xc8 && m != 0xcc) {
       return -8;  // extended / progressive / lossless / arithmetic: not this path

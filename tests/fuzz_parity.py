@@ -20,6 +20,8 @@ from libultrahdr_amd.images import Image
 from libultrahdr_amd.ultrahdr import Context, UltraHdr
 from oracle import loader as L
 
+from mcu_layouts import LAYOUTS
+
 F16, U32 = A.UHDR_IMG_FMT_64bppRGBAHalfFloat, A.UHDR_IMG_FMT_32bppRGBA1010102
 rng = np.random.default_rng(1)
 ctx = None
@@ -303,10 +305,20 @@ def fuzz_decode_fused():
     note("idct-rgb", np.array_equal(got, want_rgb), f"{mw}x{mh} bpp{bpp} v{variant}")
 
 
+def _sampling(ncomp):
+    """One component; of the three-component draws a quarter from all 63 layouts the codec accepts (tests/mcu_layouts.py: 3 .. 10 blocks
+    per MCU), the rest 4:2:0 / 4:2:2 / 4:4:4 -- the layouts the facade sends to the device -- as before."""
+    if ncomp == 1:
+        return [(1, 1)]
+    if rng.random() < 0.25:
+        return LAYOUTS[int(rng.integers(len(LAYOUTS)))]
+    return [(2, 2), (1, 1), (1, 1)] if rng.random() < 0.6 else ([(2, 1), (1, 1), (1, 1)] if rng.random() < 0.5 else [(1, 1)] * 3)
+
+
 def fuzz_huffman():
     """huffman_encode against the oracle's sequential restatement: random geometry / sampling / restart interval / density."""
     ncomp = int(rng.choice([1, 3]))
-    sampling = [(1, 1)] if ncomp == 1 else ([(2, 2), (1, 1), (1, 1)] if rng.random() < 0.6 else ([(2, 1), (1, 1), (1, 1)] if rng.random() < 0.5 else [(1, 1)] * 3))
+    sampling = _sampling(ncomp)
     bpm = sum(a * b for a, b in sampling)
     ri = int(rng.integers(1, 64 // bpm + 1))
     w, h = int(rng.integers(1, 400)), int(rng.integers(1, 120))
@@ -336,7 +348,7 @@ def fuzz_huffman_streams():
     -- what the reference writes -- or restart intervals of any length (long ones are spliced out and take the same decoder,
     short ones one lane each); the oracle's stream must come back as the coefficients that went in."""
     ncomp = int(rng.choice([1, 3]))
-    sampling = [(1, 1)] if ncomp == 1 else ([(2, 2), (1, 1), (1, 1)] if rng.random() < 0.6 else ([(2, 1), (1, 1), (1, 1)] if rng.random() < 0.5 else [(1, 1)] * 3))
+    sampling = _sampling(ncomp)
     w, h = int(rng.integers(200, 1100)), int(rng.integers(64, 420))
     hmax, vmax = max(s_[0] for s_ in sampling), max(s_[1] for s_ in sampling)
     mcus = -(-w // (8 * hmax)) * -(-h // (8 * vmax))

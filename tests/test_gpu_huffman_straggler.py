@@ -38,6 +38,8 @@ import pytest
 from libultrahdr_amd import capi as A
 from oracle import loader as L
 
+from mcu_layouts import photo_coefs
+
 pytestmark = pytest.mark.gpu
 
 W = H = 256
@@ -74,13 +76,7 @@ def _case(name, quality, short_tail=False, noise=None):
     noise: the noise's scale, None = AMP[quality] (tests/huff_tables.py asks for calmer and busier variants)."""
     sampling = SAMPLINGS[name]
     rng = np.random.default_rng(1000 * SEED[name, quality] + quality)
-    coefs = []
-    for c, (bw, bh) in enumerate(_grids(sampling)):
-        yy, xx = np.mgrid[0:bh * 8, 0:bw * 8]
-        amp = 0.3 + 7.0 * (0.5 + 0.5 * np.sin(xx / 23.0 + c) * np.cos(yy / 17.0)) ** 2
-        pl = 128 + 70 * np.sin(xx / (29.0 + 5 * c)) * np.cos(yy / (21.0 + 3 * c)) + rng.normal(0, 1, (bh * 8, bw * 8)) * amp * (AMP[quality] if noise is None else noise)
-        qt = L.quant_table_port(quality, c > 0)
-        coefs.append(L.fdct_quant_port(np.ascontiguousarray(np.clip(np.rint(pl), 0, 255).astype(np.uint8)), bw * 8, bw, bh, qt))
+    coefs = photo_coefs(rng, _grids(sampling), quality, AMP[quality] if noise is None else noise)  # (shared with the layouts of tests/mcu_layouts.py)
     scan = L.huffman_encode_port(coefs, W, H, sampling, 0)
     if short_tail:
         # clean length (stuffed zero bytes dropped) = 1 .. 7 bytes beyond a multiple of 64: the last 512-bit subsequence is shorter than

@@ -1,6 +1,6 @@
 """GPU: baseline Huffman decoding of scans WITHOUT restart markers -- every file the reference writes -- by the
 self-synchronising parallel decoder (csrc/huffman_decode_sync.hip), against the coefficients that went in / that libjpeg
-reads, for every sampling layout, sizes with dummy blocks, all coefficient statistics, several subsequence sizes, and the
+reads, for 4:4:4, 4:2:0, 4:2:2 and one-component scans (tests/test_gpu_mcu_layouts.py: every other layout), sizes with dummy blocks, all coefficient statistics, several subsequence sizes, and the
 serial kernel it replaces."""
 import ctypes as C
 import os

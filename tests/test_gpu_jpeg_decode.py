@@ -1,8 +1,9 @@
 """GPU: uhdr_hip_jpeg_decode_scan -- JpegDecoderHelper::decompressImage (jpegdecoderhelper.cpp:169-535) for baseline files
 with every stage on the device (entropy decode, dequantization, JDCT_ISLOW IDCT, ycc_rgb_convert).  Checked bit for bit
-against (a) the oracle's IDCT / colour conversion of the coefficients that went into the file, for every sampling layout,
-with and without restart markers, sizes with partial blocks, and (b) the real reference's decompressImage on files the
-real reference wrote (planar and RGB modes)."""
+against (a) the oracle's IDCT / colour conversion of the coefficients that went into the file, for 4:2:0, 4:4:4, 4:2:2 and
+one-component files (the layouts the facade sends to the device; tests/test_gpu_mcu_layouts.py runs the other layouts the
+entry points accept), with and without restart markers, sizes with partial blocks, and (b) the real reference's
+decompressImage on files the real reference wrote (planar and RGB modes)."""
 import ctypes as C
 
 import numpy as np

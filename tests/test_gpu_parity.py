@@ -708,7 +708,7 @@ def test_huffman_encode_of_a_real_frame_decodes_with_libjpeg(uhdr):
 @pytest.mark.parametrize("kind", ["sparse", "dense", "worst", "zero"])
 def test_huffman_decode_inverts_the_encoder(uhdr, kind):
     """One lane per restart interval: the oracle's streams (byte-identical to libjpeg's) decode to exactly the coefficients
-    that went in -- dummy blocks dropped, every sampling layout, restart intervals from 1 MCU to none at all."""
+    that went in -- dummy blocks dropped, 4:2:0 / 4:4:4 / 4:2:2 / one component (tests/test_gpu_mcu_layouts.py: every other layout), restart intervals from 1 MCU to none at all."""
     import torch
 
     rng = np.random.default_rng(97)
