@@ -17,6 +17,7 @@
 #include "lds_copy.h"
 #include <type_traits>
 
+#include "cu_count.h"
 #include "idct_core.h"
 #include "resize_core.h"
 #include "uhdr_types.h"
@@ -1153,9 +1154,8 @@ __global__ __launch_bounds__(quad_block<OUT>()) __attribute__((amdgpu_num_sgpr(9
 // quad kernels cap their SGPRs so the API's answer is exact -- MI355X_MICROARCH.md "Residency").
 template <typename K>
 int resident_blocks(K kernel, int block = kBlock, int sgprs = 80) {
-  int dev = 0, per_cu = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 2048;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const int cus = device_cu_count();
+  int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0) != hipSuccess || per_cu <= 0) per_cu = block == kBlock ? 4 : 1;
   // 256-thread workgroups of a kernel that uses 81 - 96 SGPRs: the hardware admits 7 per CU where the API says 8
   // (MI355X_MICROARCH.md, "Residency": min(API, 8, 800 / (ceil(sgpr / 16) * 16 + 16))); the quad kernels declare 96

@@ -20,153 +20,27 @@
 #include <string.h>
 #include "lds_copy.h"
 
+#include "cu_count.h"
 #include "encode_core.h"
+#include "fdct_core.h"
 
 namespace uhdr {
+using namespace fdct;
 namespace {
 
 constexpr int kBlock = 256;  // 4 waves
 
-#define FIX_0_298631336 2446
-#define FIX_0_390180644 3196
-#define FIX_0_541196100 4433
-#define FIX_0_765366865 6270
-#define FIX_0_899976223 7373
-#define FIX_1_175875602 9633
-#define FIX_1_501321110 12299
-#define FIX_1_847759065 15137
-#define FIX_1_961570560 16069
-#define FIX_2_053119869 16819
-#define FIX_2_562915447 20995
-#define FIX_3_072711026 25172
-
-__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-
-// libjpeg jfdctint.c, one 8-point pass (see fdct_quant.hip for the derivation and the 24-bit multiply argument)
-template <int PASS>
-__device__ __forceinline__ void fdct_1d(const int in[8], int out[8]) {
-  constexpr int sh = PASS == 0 ? 13 - 2 : 13 + 2;
-  int t0 = in[0] + in[7], t7 = in[0] - in[7], t1 = in[1] + in[6], t6 = in[1] - in[6];
-  int t2 = in[2] + in[5], t5 = in[2] - in[5], t3 = in[3] + in[4], t4 = in[3] - in[4];
-  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-  if (PASS == 0) {
-    out[0] = (t10 + t11) * 4;
-    out[4] = (t10 - t11) * 4;
-  } else {
-    out[0] = descale(t10 + t11, 2);
-    out[4] = descale(t10 - t11, 2);
-  }
-  int z1 = __mul24(t12 + t13, FIX_0_541196100);
-  out[2] = descale(z1 + __mul24(t13, FIX_0_765366865), sh);
-  out[6] = descale(z1 + __mul24(t12, -FIX_1_847759065), sh);
-  z1 = t4 + t7;
-  int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
-  const int z5 = __mul24(z3 + z4, FIX_1_175875602);
-  t4 = __mul24(t4, FIX_0_298631336);
-  t5 = __mul24(t5, FIX_2_053119869);
-  t6 = __mul24(t6, FIX_3_072711026);
-  t7 = __mul24(t7, FIX_1_501321110);
-  z1 = __mul24(z1, -FIX_0_899976223);
-  z2 = __mul24(z2, -FIX_2_562915447);
-  z3 = __mul24(z3, -FIX_1_961570560);
-  z4 = __mul24(z4, -FIX_0_390180644);
-  z3 += z5;
-  z4 += z5;
-  out[7] = descale(t4 + z1 + z3, sh);
-  out[5] = descale(t5 + z2 + z4, sh);
-  out[3] = descale(t6 + z2 + z3, sh);
-  out[1] = descale(t7 + z1 + z4, sh);
-}
-
-struct QuantPair {  // divisors (quantval << 3) and their reciprocals ceil(2^32 / q), natural order: luma table, chroma table
-  uint32_t qv[2][64], qm[2][64];
-};
-static void fill_quant(const uint16_t* qt_luma, const uint16_t* qt_chroma, QuantPair* q) {
-  for (int t = 0; t < 2; t++)
-    for (int i = 0; i < 64; i++) {
-      q->qv[t][i] = (uint32_t)(t ? qt_chroma : qt_luma)[i] << 3;
-      q->qm[t][i] = (uint32_t)((0x100000000ull + q->qv[t][i] - 1) / q->qv[t][i]);
-    }
-}
-
-// One wave, up to eight blocks: row pass results `out` of lane (row rr, block rb) -> transposed through the wave's LDS workspace
-// -> column pass + quantizer with lane (block cb, column cc) -> transposed back -> lane (rr, rb) holds one coefficient row of
-// its block in v[0..7].  `active`: the lane's block exists.  (jcdctmgr.c forward_DCT's quantizer, branch free: fdct_quant.hip)
-// q: this table's 64 {divisor, reciprocal} pairs in LDS (natural order) -- the lane's eight pairs of column cc are read where they
-// are used instead of living in 16 registers per table (map_blocks_kernel: 133 -> ~100 VGPRs)
-__device__ __forceinline__ void column_pass_and_quantize(int* ws, int lane, const int row_out[8], const uint2* q, int v[8]) {
-  const int cb = lane >> 3, cc = lane & 7, rr = lane >> 3, rb = lane & 7;
-  int in[8], out[8];
-#pragma unroll
-  for (int c = 0; c < 8; c++) ws[rb * 72 + rr * 9 + c] = row_out[c];
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): LDS writes of this wave have landed
-#pragma unroll
-  for (int r = 0; r < 8; r++) in[r] = ws[cb * 72 + r * 9 + cc];
-  fdct_1d<1>(in, out);
-#pragma unroll
-  for (int r = 0; r < 8; r++) {
-    const int x = out[r];
-    const int sgn = x >> 31;
-    const uint2 qe = q[r * 8 + cc];
-    const uint32_t a = (uint32_t)((x ^ sgn) - sgn) + (qe.x >> 1);
-    const uint32_t qq = __umulhi(a, qe.y);
-    out[r] = (int)(qq ^ (uint32_t)sgn) - sgn;
-  }
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int r = 0; r < 8; r++) ws[cb * 72 + r * 9 + cc] = out[r];
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-#pragma unroll
-  for (int c = 0; c < 8; c++) v[c] = ws[rb * 72 + rr * 9 + c];
-  __builtin_amdgcn_wave_barrier();
-}
-__device__ __forceinline__ void store_coef_row(int16_t* dst, const int v[8]) {
-  uint4 o;
-  o.x = (uint32_t)(v[0] & 0xffff) | ((uint32_t)v[1] << 16);
-  o.y = (uint32_t)(v[2] & 0xffff) | ((uint32_t)v[3] << 16);
-  o.z = (uint32_t)(v[4] & 0xffff) | ((uint32_t)v[5] << 16);
-  o.w = (uint32_t)(v[6] & 0xffff) | ((uint32_t)v[7] << 16);
-  *(uint4*)dst = o;
-}
-
-// The block side of a gain map, shared by map_blocks_kernel and map_blocks_onepass_kernel, in the halves of their strip loop.
-// An ACTIVE lane (row rr, block rb) holds the 8 * NCH map bytes of its row of its block in w, packed as they come:
-// map_row_samples: libjpeg's rgb_ycc_convert for three channels, level shift (the optional 8-byte stores of the map itself stay in the
-// kernels: inside a helper they cost map_blocks_kernel<3> 14 VGPRs and a workgroup per CU).
-// map_strip_transform: the NCH transforms of the strip; inactive lanes (blocks past bw) take part in the transposes only.
-#define FIX16(x) ((int)((x) * 65536.0 + 0.5))
+// The block side of a gain map, shared by map_blocks_kernel and map_blocks_onepass_kernel: an ACTIVE lane (row rr, block rb) holds the
+// 8 * NCH map bytes of its row of its block in w, packed as they come; libjpeg's rgb_ycc_convert for three channels, level shift.  Then
+// fdct_core.h's strip_transform.  (The optional 8-byte stores of the map itself stay in the kernels: inside a helper they cost
+// map_blocks_kernel<3> 14 VGPRs and a workgroup per CU.)
 template <int NCH>
 __device__ __forceinline__ void map_row_samples(const uint32_t (&w)[2 * NCH], int (&comp)[3][8]) {
   auto byte_at = [&](int e) -> int { return (int)((w[e >> 2] >> (8 * (e & 3))) & 0xffu); };
 #pragma unroll
   for (int k = 0; k < 8; k++) {
-    if (NCH == 3) {  // jccolor.c rgb_ycc_convert (fdct_quant.hip / jpeg_decode.hip: both published constant sets give these bytes)
-      const int r = byte_at(3 * k), gg = byte_at(3 * k + 1), bb = byte_at(3 * k + 2);
-      const int half = 1 << 15, off = 128 << 16;
-      comp[0][k] = ((__mul24(FIX16(0.29900), r) + __mul24(FIX16(0.58700), gg) + __mul24(FIX16(0.11400), bb) + half) >> 16) - 128;
-      comp[1][k] = ((__mul24(-FIX16(0.16874), r) + __mul24(-FIX16(0.33126), gg) + __mul24(FIX16(0.50000), bb) + off + half - 1) >> 16) - 128;
-      comp[2][k] = ((__mul24(FIX16(0.50000), r) + __mul24(-FIX16(0.41869), gg) + __mul24(-FIX16(0.08131), bb) + off + half - 1) >> 16) - 128;
-    } else {
-      comp[0][k] = byte_at(k) - 128;
-    }
-  }
-}
-template <int NCH>
-__device__ __forceinline__ void map_strip_transform(const int (&comp)[3][8], bool active, int16_t* const coef[3], int bw, int by, int bx, int lane, int* ws,
-                                                    const uint2 (*s_q)[64]) {
-#pragma unroll
-  for (int ci = 0; ci < NCH; ci++) {
-    int out[8], v[8];
-    if (active) {
-      fdct_1d<0>(comp[ci], out);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 8; c++) out[c] = 0;
-    }
-    column_pass_and_quantize(ws, lane, out, s_q[ci == 0 ? 0 : 1], v);
-    if (active) store_coef_row(coef[ci] + ((size_t)by * bw + bx) * 64 + (lane >> 3) * 8, v);
+    if (NCH == 3) rgb_ycc_level_shift(byte_at(3 * k), byte_at(3 * k + 1), byte_at(3 * k + 2), comp, k);
+    else comp[0][k] = byte_at(k) - 128;
   }
 }
 
@@ -179,17 +53,17 @@ struct MapBlocksParams {
   uint32_t out_stride;     // pixels
   int bw, bh;              // blocks (map_w / 8, map_h / 8)
   int16_t* coef[3];
-  QuantPair q;
+  QuantTables q;
 };
 
 constexpr int kMapBlock = 512;  // eight waves share one copy of the step tables (24 KB): three workgroups = 24 waves per CU
 template <int NCH>
 __global__ __launch_bounds__(kMapBlock) void map_blocks_kernel(const MapBlocksParams p) {
   constexpr int kBlock = kMapBlock;  // (shadows the file's 256 inside this kernel)
-  __shared__ int s_ws[kBlock / 64][8 * 8 * 9];
+  __shared__ int s_ws[kBlock / 64][kWsWords];
   __shared__ uint2 s_tab[NCH][kAffTabMax];
   __shared__ uint2 s_q[2][64];
-  if (threadIdx.x < 128) s_q[threadIdx.x >> 6][threadIdx.x & 63] = uint2{p.q.qv[threadIdx.x >> 6][threadIdx.x & 63], p.q.qm[threadIdx.x >> 6][threadIdx.x & 63]};
+  stage_quant_tables(s_q, p.q, threadIdx.x);
   StepTab st[3];
   bool tabs = true;
 #pragma unroll
@@ -262,7 +136,7 @@ __global__ __launch_bounds__(kMapBlock) void map_blocks_kernel(const MapBlocksPa
       }
       map_row_samples<NCH>(w, comp);
     }
-    map_strip_transform<NCH>(comp, active, p.coef, p.bw, by, bx, lane, ws, s_q);
+    strip_transform<NCH>(comp, active, p.coef, p.bw, by, bx, lane, ws, QuantLds{s_q[0]}, QuantLds{s_q[1]});
   }
 }
 
@@ -271,7 +145,7 @@ __global__ __launch_bounds__(kMapBlock) void map_blocks_kernel(const MapBlocksPa
 // wait between the pixel side and the block side: generate_kernel<.., TWO_PASS = false>'s pixel (generate_gainmap.hip) and
 // map_blocks_kernel's strip in one kernel.  Lane (row rr, block rb) computes the eight map pixels of row rr of block rb -- sample_box
 // over the s x s box of both intents, yuv -> rgb, the inverse-OETF tables, gamut matrix + clipNegatives, gain, byte through the gain8
-// step table -- packs them into the words map_blocks_kernel builds and goes on with map_row_samples / map_strip_transform.  The 8-bit map reaches HBM only when
+// step table -- packs them into the words map_blocks_kernel builds and goes on with map_row_samples / strip_transform.  The 8-bit map reaches HBM only when
 // the caller wants it (g.out != null).  A call without a gain8 table (host_tables.cpp declined the boost range) evaluates encode_gain's
 // float64 form per sample, as a rolled loop that parks its bytes in the wave's idle workspace, as map_blocks_kernel does.
 // FAST: 4:2:0 + P010 at scale 1 with rows the vector loads can take (map_onepass_fast_layout) -- a lane's row is one 8-byte luma load,
@@ -281,7 +155,7 @@ struct MapOnepassParams {
   GenParams g;             // g.out / g.out_stride: the optional 8-bit map
   int bw, bh;              // blocks (map_w / 8, map_h / 8)
   int16_t* coef[3];
-  QuantPair q;
+  QuantTables q;
 };
 struct OnepassLds {
   float srgb[kSrgbN];
@@ -325,12 +199,12 @@ __device__ __forceinline__ void onepass_codes(Color3 s, Color3 h, const GenParam
 template <int SDRF, int HDRF, int NCH, bool FAST>
 __global__ __launch_bounds__(kMapBlock, 4) void map_blocks_onepass_kernel(const MapOnepassParams p) {
   constexpr int kBlock = kMapBlock;
-  __shared__ int s_ws[kBlock / 64][8 * 8 * 9];
+  __shared__ int s_ws[kBlock / 64][kWsWords];
   __shared__ OnepassLds L;
   __shared__ alignas(16) uint2 s_gain8[kStepTabMax];
   __shared__ uint2 s_q[2][64];
   const uint32_t tid = threadIdx.x;
-  if (tid < 128) s_q[tid >> 6][tid & 63] = uint2{p.q.qv[tid >> 6][tid & 63], p.q.qm[tid >> 6][tid & 63]};
+  stage_quant_tables(s_q, p.q, tid);
   const GenParams& g = p.g;
   stage_step_tab(s_gain8, g.gain8, tid, kBlock);
   copy_to_lds(L.srgb, g.srgb_lut, (uint32_t)kSrgbN, tid, kBlock);
@@ -406,7 +280,7 @@ __global__ __launch_bounds__(kMapBlock, 4) void map_blocks_onepass_kernel(const 
       }
       map_row_samples<NCH>(w, comp);
     }
-    map_strip_transform<NCH>(comp, active, p.coef, p.bw, by, bx, lane, ws, s_q);
+    strip_transform<NCH>(comp, active, p.coef, p.bw, by, bx, lane, ws, QuantLds{s_q[0]}, QuantLds{s_q[1]});
   }
 }
 
@@ -420,13 +294,13 @@ struct BaseBlocksParams {
   int convert;             // 0: the planes go to the FDCT as they are
   Mat3 c;                  // convertYuv's coefficients (host_tables.cpp: yuv_encoding_matrix)
   int16_t* coef[3];
-  QuantPair q;
+  QuantTables q;
 };
 
 __device__ __forceinline__ uint32_t st8(float v) { return (uint32_t)__builtin_amdgcn_fmed3f(v, 0.0f, 255.0f); }  // static_cast<uint8_t>(CLIP3(v, 0, 255)), convert.hip
 
 __global__ __launch_bounds__(kBlock) void base_blocks_kernel(const BaseBlocksParams p) {
-  __shared__ int s_ws[kBlock / 64][8 * 8 * 9];
+  __shared__ int s_ws[kBlock / 64][kWsWords];
   // per wave: the converted samples of two MCUs -- luma 16 rows x 32, Cb and Cr 8 rows x 16 each
   __shared__ __attribute__((aligned(16))) uint8_t s_y[kBlock / 64][16 * 32];
   __shared__ __attribute__((aligned(16))) uint8_t s_c[kBlock / 64][2][8 * 16];
@@ -439,7 +313,7 @@ __global__ __launch_bounds__(kBlock) void base_blocks_kernel(const BaseBlocksPar
   const int gwave = blockIdx.x * (kBlock / 64) + wv, nwaves = gridDim.x * (kBlock / 64);
   const int rr = lane >> 3, rb = lane & 7;
   __shared__ uint2 s_q[2][64];
-  if (threadIdx.x < 128) s_q[threadIdx.x >> 6][threadIdx.x & 63] = uint2{p.q.qv[threadIdx.x >> 6][threadIdx.x & 63], p.q.qm[threadIdx.x >> 6][threadIdx.x & 63]};
+  stage_quant_tables(s_q, p.q, threadIdx.x);
   __syncthreads();
   const int bw_y = p.mcus_x * 2, bw_c = p.mcus_x;
   for (int t = gwave; t < total; t += nwaves) {
@@ -483,18 +357,13 @@ __global__ __launch_bounds__(kBlock) void base_blocks_kernel(const BaseBlocksPar
       int in[8], out[8], v[8];
       if (active) {
         const uint8_t* src = ty + (byy * 8 + rr) * 32 + m * 16 + bxx * 8;
-        const uint32_t lo = ((const uint32_t*)src)[0], hi = ((const uint32_t*)src)[1];
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-          in[c] = (int)((lo >> (8 * c)) & 0xff) - 128;
-          in[4 + c] = (int)((hi >> (8 * c)) & 0xff) - 128;
-        }
+        unpack8_level_shift(((const uint32_t*)src)[0], ((const uint32_t*)src)[1], in);
         fdct_1d<0>(in, out);
       } else {
 #pragma unroll
         for (int c = 0; c < 8; c++) out[c] = 0;
       }
-      column_pass_and_quantize(ws, lane, out, s_q[0], v);
+      column_pass_and_quantize(ws, lane, out, QuantLds{s_q[0]}, v);
       if (active) {
         const size_t bx = (size_t)(mx0 + m) * 2 + bxx, by = (size_t)my * 2 + byy;
         store_coef_row(p.coef[0] + (by * bw_y + bx) * 64 + rr * 8, v);
@@ -507,18 +376,13 @@ __global__ __launch_bounds__(kBlock) void base_blocks_kernel(const BaseBlocksPar
       int in[8], out[8], v[8];
       if (active) {
         const uint8_t* src = (comp ? tcr : tcb) + rr * 16 + m * 8;
-        const uint32_t lo = ((const uint32_t*)src)[0], hi = ((const uint32_t*)src)[1];
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-          in[c] = (int)((lo >> (8 * c)) & 0xff) - 128;
-          in[4 + c] = (int)((hi >> (8 * c)) & 0xff) - 128;
-        }
+        unpack8_level_shift(((const uint32_t*)src)[0], ((const uint32_t*)src)[1], in);
         fdct_1d<0>(in, out);
       } else {
 #pragma unroll
         for (int c = 0; c < 8; c++) out[c] = 0;
       }
-      column_pass_and_quantize(ws, lane, out, s_q[1], v);
+      column_pass_and_quantize(ws, lane, out, QuantLds{s_q[1]}, v);
       if (active) store_coef_row(p.coef[1 + comp] + ((size_t)my * bw_c + (mx0 + m)) * 64 + rr * 8, v);
     }
     __builtin_amdgcn_wave_barrier();
@@ -543,17 +407,17 @@ struct BaseBlocksRgbaParams {
   Rgb2Yuv k;               // the intent's gamut (host_tables.cpp: rgb2yuv_coeffs)
   Mat3 c;                  // convertYuv's coefficients (host_tables.cpp: yuv_encoding_matrix)
   int16_t* coef[3];
-  QuantPair q;
+  QuantTables q;
 };
 
 __device__ __forceinline__ float clipf255(float v) { return (v < 0.0f) ? 0.0f : ((v > 255.0f) ? 255.0f : v); }  // convert.hip: clipf
 
 template <bool VEC>
 __global__ __launch_bounds__(kBlock) void base_blocks_rgba_kernel(const BaseBlocksRgbaParams p) {
-  __shared__ int s_ws[kBlock / 64][8 * 8 * 9];
+  __shared__ int s_ws[kBlock / 64][kWsWords];
   __shared__ uint2 s_q[2][64];
   __shared__ float s_u8[256];  // i / 255.0f, the device's correctly rounded division (pixel_io.h: UnormTables)
-  if (threadIdx.x < 128) s_q[threadIdx.x >> 6][threadIdx.x & 63] = uint2{p.q.qv[threadIdx.x >> 6][threadIdx.x & 63], p.q.qm[threadIdx.x >> 6][threadIdx.x & 63]};
+  stage_quant_tables(s_q, p.q, threadIdx.x);
   for (uint32_t i = threadIdx.x; i < 256; i += kBlock) s_u8[i] = (float)i / 255.0f;
   __syncthreads();
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -596,6 +460,8 @@ __global__ __launch_bounds__(kBlock) void base_blocks_rgba_kernel(const BaseBloc
         comp[2][j] = vv - 128;
       }
     }
+    // fdct_core.h's strip_transform, spelled out: behind the helper call the compiler packs the conversion above into v_pk_* pairs
+    // with 36 more register moves, and the 4K launch went from 34.1 to 36.4 us
 #pragma unroll
     for (int ci = 0; ci < 3; ci++) {
       int out[8], v[8];
@@ -605,15 +471,14 @@ __global__ __launch_bounds__(kBlock) void base_blocks_rgba_kernel(const BaseBloc
 #pragma unroll
         for (int c = 0; c < 8; c++) out[c] = 0;
       }
-      column_pass_and_quantize(ws, lane, out, s_q[ci == 0 ? 0 : 1], v);
+      column_pass_and_quantize(ws, lane, out, QuantLds{s_q[ci == 0 ? 0 : 1]}, v);
       if (active) store_coef_row(p.coef[ci] + ((size_t)by * p.bw + bx) * 64 + rr * 8, v);
     }
   }
 }
 
 int resident_grid(int total_wave_items, int per_cu) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const int cus = device_cu_count();
   int grid = (total_wave_items + kBlock / 64 - 1) / (kBlock / 64);
   if (grid > cus * per_cu) grid = cus * per_cu;
   return grid < 1 ? 1 : grid;
@@ -629,7 +494,8 @@ hipError_t launch_map_blocks(const float* ratio, const AffineDev* dev, const dou
   memset(&p, 0, sizeof p);
   p.ratio = ratio; p.dev = dev; p.math_tab = math_tab; p.map_out = map_out; p.out_stride = out_stride; p.bw = bw; p.bh = bh;
   for (int i = 0; i < nch; i++) p.coef[i] = coef[i];
-  fill_quant(qt_luma, qt_chroma, &p.q);
+  fill_quant_table(qt_luma, &p.q.luma);
+  fill_quant_table(qt_chroma, &p.q.chroma);
   int grid = (((bw + 7) / 8) * bh + kMapBlock / 64 - 1) / (kMapBlock / 64);
   const int cap = resident_grid(1 << 30, 3);  // 44 KB of LDS (tables + workspaces) per 512 threads: three workgroups per CU
   if (grid > cap) grid = cap;
@@ -664,7 +530,8 @@ hipError_t launch_map_blocks_onepass(const GenParams& g, int nch, const uint16_t
   p.g.out = map_out; p.g.out_stride = out_stride;
   p.bw = (int)(g.map_w / 8); p.bh = (int)(g.map_h / 8);
   for (int i = 0; i < nch; i++) p.coef[i] = coef[i];
-  fill_quant(qt_luma, qt_chroma, &p.q);
+  fill_quant_table(qt_luma, &p.q.luma);
+  fill_quant_table(qt_chroma, &p.q.chroma);
   int grid = (((p.bw + 7) / 8) * p.bh + kMapBlock / 64 - 1) / (kMapBlock / 64);
   const int cap = resident_grid(1 << 30, 2);  // 60 KB of LDS (tables + workspaces) per 512 threads: two workgroups per CU
   if (grid > cap) grid = cap;
@@ -696,7 +563,8 @@ hipError_t launch_base_blocks(const ImageView& yuv420, const Mat3* c, const uint
   p.convert = c ? 1 : 0;
   if (c) p.c = *c;
   for (int i = 0; i < 3; i++) p.coef[i] = coef[i];
-  fill_quant(qt_luma, qt_chroma, &p.q);
+  fill_quant_table(qt_luma, &p.q.luma);
+  fill_quant_table(qt_chroma, &p.q.chroma);
   const int grid = resident_grid(((p.mcus_x + 1) / 2) * p.mcus_y, 8);
   hipLaunchKernelGGL(base_blocks_kernel, dim3(grid), dim3(kBlock), 0, s, p);
   return hipGetLastError();
@@ -715,7 +583,8 @@ hipError_t launch_base_blocks_rgba(const ImageView& rgba, const Rgb2Yuv& k, cons
   p.convert = c ? 1 : 0;
   if (c) p.c = *c;
   for (int i = 0; i < 3; i++) p.coef[i] = coef[i];
-  fill_quant(qt_luma, qt_chroma, &p.q);
+  fill_quant_table(qt_luma, &p.q.luma);
+  fill_quant_table(qt_chroma, &p.q.chroma);
   const int grid = resident_grid(((p.bw + 7) / 8) * p.bh, 7);  // 66 VGPRs: seven waves per SIMD, i.e. seven 4-wave workgroups per CU are resident
   const bool vec = ((uintptr_t)rgba.p[0] % 16) == 0 && rgba.stride[0] % 4 == 0;
   if (vec) hipLaunchKernelGGL((base_blocks_rgba_kernel<true>), dim3(grid), dim3(kBlock), 0, s, p);

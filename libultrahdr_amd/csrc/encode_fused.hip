@@ -13,6 +13,7 @@
 // bytes exactly as generateGainMap would read them back.  tests/test_gpu_parity.py checks the fused
 // outputs against tone_map -> generate_gainmap -> convert_raw_input_to_ycbcr, bit for bit.
 // Conditions: RGB HDR input (RGBA1010102 / RGBA-F16), gain map at full resolution (scale 1).
+#include "cu_count.h"
 #include "encode_core.h"
 #include "lds_copy.h"
 
@@ -622,12 +623,7 @@ bool scaled_gamut_ok(const FusedParams& p) {
 }  // namespace
 
 int fused_grid(uint32_t tiles, int per_cu) {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
+  const int cus = device_cu_count();
   const int resident = cus * per_cu;  // 512-thread workgroups: 48 KB of LDS tables (RGBA1010102) -> 3 per CU, 60 KB (RGBA-F16) -> 2
   uint32_t g = tiles < (uint32_t)resident ? tiles : (uint32_t)resident;
   if (g > 2048) g = 2048;  // the host layer sizes the min/max partials buffer for 2048 workgroups

@@ -14,6 +14,7 @@
 //
 // LDS per 512-thread workgroup: 25 KB of tables (GenLds) + 5.25 KB (4:2:0) / 6.25 KB (4:2:2) per wave for the tile and the
 // IDCT workspace = 68 / 76 KB two pass -> two workgroups (16 waves) per CU; the one-pass step table adds 16 KB -> one.
+#include "cu_count.h"
 #include "encode_core.h"
 #include "idct_core.h"
 #include "lds_copy.h"
@@ -184,16 +185,9 @@ __global__ __launch_bounds__(kCoefBlock) void generate_coef_kernel(const GenPara
 }
 
 int coef_grid(const GenParams& p, bool two_pass) {
-  static int cus_of[64] = {};  // per device id, as gen_grid (generate_gainmap.hip)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (cus_of[dev] == 0) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    cus_of[dev] = cus;
-  }
+  const int cus = device_cu_count();
   const uint32_t tiles = ((p.sdr.w + 127) / 128) * ((p.sdr.h + 15) / 16);
-  const uint32_t resident = (uint32_t)cus_of[dev] * (two_pass ? 2u : 1u);  // workgroups per CU: the LDS budget at the head of this file
+  const uint32_t resident = (uint32_t)cus * (two_pass ? 2u : 1u);  // workgroups per CU: the LDS budget at the head of this file
   uint32_t g = (tiles + kCoefWaves - 1) / kCoefWaves;
   if (g > resident) g = resident;
   if (g > (uint32_t)kCoefMaxGrid) g = kCoefMaxGrid;

@@ -18,6 +18,7 @@
 // No per-pixel logarithm is left, and nothing was approximated: every table entry is the exact composite's value.
 // Across GPUs the six log2 extrema are all-reduced by the host layer (one RCCL min over {min, -max}) between the
 // reduce and the finalize halves of that kernel.
+#include "cu_count.h"
 #include "encode_core.h"
 #include "lds_copy.h"
 
@@ -401,17 +402,8 @@ __global__ __launch_bounds__(kBlock) void affine_exact_kernel(const AffineParams
 }
 
 int gen_grid(uint32_t tiles) {
-  // residency of the CURRENT device (the entry points make their context's device current first), cached per device id: a
-  // process that drives contexts on different devices must not inherit the first one's CU count
-  static int resident_of[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (resident_of[dev] == 0) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    resident_of[dev] = cus * 3;  // 512-thread workgroups, 25 KB of LDS tables each: three are resident per CU (24 waves, the VGPR limit)
-  }
-  const int resident = resident_of[dev];
+  const int cus = device_cu_count();  // of the CURRENT device, not the first one's
+  const int resident = cus * 3;  // 512-thread workgroups, 25 KB of LDS tables each: three are resident per CU (24 waves, the VGPR limit)
   uint32_t g = tiles < (uint32_t)resident ? tiles : (uint32_t)resident;
   if (g > kMaxGrid) g = kMaxGrid;
   if (g < 1) g = 1;

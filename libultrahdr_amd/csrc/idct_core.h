@@ -3,23 +3,11 @@
 // modulo 1024).  Shared by the stand-alone decode kernels (jpeg_decode.hip) and the applyGainMap variant that
 // consumes the base image in coefficient form (apply_gainmap.hip).  See jpeg_decode.hip for the provenance notes.
 #pragma once
+#include "jdct_fix.h"
 #include "uhdr_types.h"
 
 namespace uhdr {
 namespace idct {
-
-#define FIX_0_298631336 2446
-#define FIX_0_390180644 3196
-#define FIX_0_541196100 4433
-#define FIX_0_765366865 6270
-#define FIX_0_899976223 7373
-#define FIX_1_175875602 9633
-#define FIX_1_501321110 12299
-#define FIX_1_847759065 15137
-#define FIX_1_961570560 16069
-#define FIX_2_053119869 16819
-#define FIX_2_562915447 20995
-#define FIX_3_072711026 25172
 
 template <bool M24>
 __device__ __forceinline__ int mulc(int a, int c) {

@@ -9,7 +9,7 @@
 // column pass from the dequantized coefficients, row pass, descale by 2^18, +128, range-limit
 // table indexed modulo 1024) and jccolor.c / jdcolor.c's 16-bit fixed-point colour transforms.
 //
-// IDCT mapping (mirror image of fdct_quant.hip): one wavefront = 8 horizontally adjacent blocks.
+// IDCT mapping (mirror image of fdct_core.h): one wavefront = 8 horizontally adjacent blocks.
 // Lane (row r, block b) loads one coefficient row (8 x int16 = 16 bytes: a wave reads 1 KiB of
 // contiguous JBLOCKs), dequantizes it and parks it in LDS (rows padded to 9 words); lane
 // (block, column) runs the column pass; lane (row, block) runs the row pass on its workspace row,

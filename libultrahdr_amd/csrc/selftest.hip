@@ -8,6 +8,7 @@
 //      index) == srgb_oetf_table (round-1 form: nearest-of-65 table, degree 5) for every float in [0, 1]
 //   4  the device-built ratio -> byte step table of two-pass generation against the per-sample evaluation, for a given
 //      (min, max) range: every bit pattern of the table's domain and a margin on both sides (generate_gainmap.hip)
+#include "cu_count.h"
 #include "encode_core.h"
 
 namespace uhdr {
@@ -114,9 +115,7 @@ __global__ __launch_bounds__(256) void sweep_affine(unsigned long long* out, con
 // out: 8 zero-initialised device words.  which 4: dev = the AffineDev + tables to check (built by launch_minmax_table), arg0 = channel
 hipError_t launch_selftest(int which, unsigned long long* out, uint32_t arg0, uint32_t arg1, uint32_t seed, const double* math_tab, const AffineDev* dev,
                            hipStream_t s) {
-  int cus = 256, devid = 0;
-  if (hipGetDevice(&devid) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, devid);
-  const dim3 grid(cus * 8), block(256);
+  const dim3 grid(device_cu_count() * 8), block(256);
   switch (which) {
     case 0: hipLaunchKernelGGL(sweep_rpi, grid, block, 0, s, out); break;
     case 1: hipLaunchKernelGGL(sweep_rcp, grid, block, 0, s, out); break;

@@ -10,6 +10,7 @@
 // behind srgbOetf's pow (exact_math.h: the direct table, 18 KB) are staged in LDS.  A workgroup walks tiles of 256
 // consecutive quads / pixels of one row.  Round 4: Markstein divisions, v_cvt_rpi table indices and the direct pow
 // table (encode_core.h) -- P010 4K 51 -> see DESIGN.md 5.2.
+#include "cu_count.h"
 #include "encode_core.h"
 #include "lds_copy.h"
 
@@ -155,12 +156,7 @@ __global__ __launch_bounds__(kBlock) void tonemap_pixel_kernel(const ToneMapPara
 
 // per_cu: resident workgroups per CU (39 KB of LDS tables each): four, of 512 threads (P010 kernel) or of 256 (pixel kernel)
 int tone_grid(uint32_t tiles, int per_cu) {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
+  const int cus = device_cu_count();
   const int resident = cus * per_cu;
   const uint32_t g = tiles < (uint32_t)resident ? tiles : (uint32_t)resident;
   return (int)(g < 1 ? 1 : g);

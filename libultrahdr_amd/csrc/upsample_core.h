@@ -2,6 +2,7 @@
 // libjpeg 9's scaled IDCTs, libjpeg's ycc_rgb_convert of one pixel with its family's green constants, the packed store of
 // eight pixels, the wave-private LDS fence and the resident grid size.
 #pragma once
+#include "cu_count.h"
 #include "idct_core.h"
 #include "uhdr_types.h"
 
@@ -173,17 +174,7 @@ __device__ __forceinline__ void store_px8(uint8_t* dst, const uint32_t px[8], ui
   }
 }
 
-// host: the grid of a persistent kernel, per_cu workgroups on each CU (CU count, or 256 when the device does not say) or one
-// per tile when there are fewer
-inline int device_cu_count() {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
-  return cus;
-}
+// host: the grid of a persistent kernel, per_cu workgroups on each CU (cu_count.h) or one per tile when there are fewer
 inline int resident_grid(uint32_t tiles, int per_cu) {
   const uint32_t r = (uint32_t)(device_cu_count() * per_cu);
   return (int)(tiles < r ? (tiles ? tiles : 1u) : r);

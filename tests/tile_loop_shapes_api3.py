@@ -16,7 +16,7 @@ MIRRORED = [
     ("generate_coef.hip", "constexpr int kCoefWaves = kCoefBlock / 64;"),
     ("generate_coef.hip", "constexpr int kCoefMaxGrid = 2048;"),
     ("generate_coef.hip", "const uint32_t tiles = ((p.sdr.w + 127) / 128) * ((p.sdr.h + 15) / 16);"),
-    ("generate_coef.hip", "const uint32_t resident = (uint32_t)cus_of[dev] * (two_pass ? 2u : 1u);"),
+    ("generate_coef.hip", "const uint32_t resident = (uint32_t)cus * (two_pass ? 2u : 1u);"),
     ("generate_coef.hip", "uint32_t g = (tiles + kCoefWaves - 1) / kCoefWaves;"),
     ("generate_coef.hip", "if (g > resident) g = resident;"),
     ("generate_coef.hip", "if (g > (uint32_t)kCoefMaxGrid) g = kCoefMaxGrid;"),
@@ -32,7 +32,7 @@ def coef_walk(cus, w, h, two_pass=True):
     tiles_x = (w + 127) >> 7                  # const uint32_t tiles_x = (w + 127) >> 7, tiles_y = (h + 15) >> 4, ntiles = tiles_x * tiles_y;
     tiles = tiles_x * ((h + 15) >> 4)         # ... and coef_grid: const uint32_t tiles = ((p.sdr.w + 127) / 128) * ((p.sdr.h + 15) / 16);
     waves = COEF_BLOCK // 64                  # constexpr int kCoefWaves = kCoefBlock / 64;
-    resident = cus * (2 if two_pass else 1)   # const uint32_t resident = (uint32_t)cus_of[dev] * (two_pass ? 2u : 1u);
+    resident = cus * (2 if two_pass else 1)   # const uint32_t resident = (uint32_t)cus * (two_pass ? 2u : 1u);
     g = (tiles + waves - 1) // waves          # uint32_t g = (tiles + kCoefWaves - 1) / kCoefWaves;
     if g > resident:                          # if (g > resident) g = resident;
         g = resident
