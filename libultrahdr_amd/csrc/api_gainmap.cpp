@@ -394,6 +394,18 @@ static uhdr_error_info_t fill_coef_src(const uhdr_hip_jpeg_coefficients_t* base,
   return ok_status();
 }
 
+// Geometry-only view of the w x h image the coefficients decode to: the kernels take sizes, sampling and colour aspects from it and
+// never dereference its planes
+static uhdr_raw_image_t coef_image_view(const uhdr_hip_jpeg_coefficients_t* base, unsigned int w, unsigned int h, int sampling, uhdr_color_gamut_t cg) {
+  uhdr_raw_image_t img;
+  memset(&img, 0, sizeof img);
+  img.fmt = sampling == 420 ? UHDR_IMG_FMT_12bppYCbCr420 : (sampling == 422 ? UHDR_IMG_FMT_16bppYCbCr422 : UHDR_IMG_FMT_24bppYCbCr444);
+  img.cg = cg; img.ct = UHDR_CT_SRGB; img.range = UHDR_CR_FULL_RANGE;
+  img.w = w; img.h = h;
+  for (int i = 0; i < 3; i++) { img.planes[i] = (void*)base->coef[i]; img.stride[i] = (unsigned int)base->blocks_w[i] * 8; }
+  return img;
+}
+
 // applyGainMap with the base image still in coefficient form: JpegDecoderHelper's dequantize + IDCT stage
 // (jpegdecoderhelper.cpp:468-535) runs inside the applyGainMap kernel, the 8-bit planes never exist in memory.
 // All three samplings share this body (and the context's descriptor slots); a uhdr_hip_jpeg_coefficients_t cannot say which
@@ -405,13 +417,7 @@ static uhdr_error_info_t apply_gainmap_coef_impl(uhdr_hip_ctx_t* c, const uhdr_h
   CoefSrc cs;
   UHDR_TRY(fill_coef_src(base, w, h, sampling, &cs));
   HIP_TRY(hipSetDevice(c->device));
-  // geometry-only view of the image the coefficients decode to (the kernel never dereferences these planes)
-  uhdr_raw_image_t sdr;
-  memset(&sdr, 0, sizeof sdr);
-  sdr.fmt = sampling == 420 ? UHDR_IMG_FMT_12bppYCbCr420 : (sampling == 422 ? UHDR_IMG_FMT_16bppYCbCr422 : UHDR_IMG_FMT_24bppYCbCr444);
-  sdr.cg = base_cg; sdr.ct = UHDR_CT_SRGB; sdr.range = UHDR_CR_FULL_RANGE;
-  sdr.w = w; sdr.h = h;
-  for (int i = 0; i < 3; i++) { sdr.planes[i] = (void*)base->coef[i]; sdr.stride[i] = (unsigned int)base->blocks_w[i] * 8; }
+  const uhdr_raw_image_t sdr = coef_image_view(base, w, h, sampling, base_cg);
   ApplyParams p;
   UHDR_TRY(build_apply_params(c, &sdr, gm, md, out_ct, max_display_boost, dest, 0, 0, &p));
   if (apply_quad_mode(p) < 0)
@@ -810,13 +816,7 @@ uhdr_error_info_t uhdr_api::prepare_gen_coef(uhdr_hip_ctx* c, const uhdr_hip_jpe
   if (scale && scale != 1 && scale != 2 && scale != 4)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "generate_gainmap_coef covers gain-map scale factors 1, 2 and 4 (%u for %ux%u at the configured %d); %s", scale, w, h,
                       cfg->map_dimension_scale_factor, kStaged);
-  // geometry-only description of the image the coefficients decode to (the kernel never dereferences these planes)
-  uhdr_raw_image_t img;
-  memset(&img, 0, sizeof img);
-  img.fmt = sampling == 420 ? UHDR_IMG_FMT_12bppYCbCr420 : UHDR_IMG_FMT_16bppYCbCr422;
-  img.cg = sdr_cg; img.ct = UHDR_CT_SRGB; img.range = UHDR_CR_FULL_RANGE;
-  img.w = w; img.h = h;
-  for (int i = 0; i < 3; i++) { img.planes[i] = (void*)sdr->coef[i]; img.stride[i] = (unsigned int)sdr->blocks_w[i] * 8; }
+  const uhdr_raw_image_t img = coef_image_view(sdr, w, h, sampling, sdr_cg);
   HIP_TRY(hipSetDevice(c->device));
   UHDR_TRY(fill_gen_params(c, &img, hdr, cfg, p, use_base_cg, hdr_white_nits, /*sdr_in_registers=*/true));
   if (p->scale != scale) return err_status(UHDR_CODEC_ERROR, "internal: scale factor %u / %u", p->scale, scale);

@@ -18,7 +18,7 @@
 #include <type_traits>
 
 #include "cu_count.h"
-#include "idct_core.h"
+#include "coef_tile.h"
 #include "resize_core.h"
 #include "uhdr_types.h"
 
@@ -464,8 +464,9 @@ struct QuadRaw {
 // SRC 1 (BASE 0 / 3 / 1): the base image arrives as JPEG coefficient blocks (p.coef_src, what jpeg_read_coefficients()
 // yields) and never exists as planes in HBM.  A wave then owns 128 x 16 pixel tiles (one 4:2:0 MCU row of sixteen
 // luma blocks): it dequantizes and inverse-transforms the tile's 32 + 8 + 8 blocks into its private LDS tile
-// (idct_core.h, six eight-block passes) and feeds the same per-quad arithmetic from there; the gain map is still
-// read from memory.  3 B/px of coefficients in instead of 3 in + 1.5 out + 1.5 in over four launches.
+// (coef_tile.h, six eight-block units laid out by coef_tile::Geom) and feeds the same per-quad arithmetic from there (this
+// file keeps the order -- all loads, the first gain-map fetch, all transforms -- and the quad-row loop); the gain map is
+// still read from memory.  3 B/px of coefficients in instead of 3 in + 1.5 out + 1.5 in over four launches.
 // A 4:2:2 image (BASE 3) has two chroma block rows per tile: 32 + 16 + 16 blocks, eight passes (Y x 4, Cb x 2, Cr x 2), a
 // chroma tile of 16 rows x 64 bytes per component, and each row of a quad reads its own chroma row.  4 B/px in instead of
 // 4 in + 2 out + 2 in.
@@ -988,110 +989,68 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
     else rows(G0{});
     if (touched == 0x9e3779b9u && p.n_frames == 0xffffffffu) dp[0] = 0;  // never true: keeps the sweep's loads alive
   } else {
-    // ---- coefficient input: 128 x 16 pixel tiles (128 x 8 for 4:4:4), IDCT into the wave's LDS tile, then eight (four) quad rows -------
+    // ---- coefficient input: 128 x 16 pixel tiles (128 x 8 for 4:4:4) through the stage of coef_tile.h into the wave's LDS tiles, then
+    // eight (four) quad rows -------
     stage_tables();
+    constexpr int SAMPLING = BASE == 0 ? 420 : (BASE == 3 ? 422 : 444);
+    using G = coef_tile::Geom<SAMPLING>;
+    constexpr int QROWS = G::TROWS / 2;  // quad rows of a tile
     __shared__ int s_ws[BLK / 64][8 * 8 * 9];
     __shared__ int s_q[3][64];
-    constexpr int TROWS = BASE == 1 ? 8 : 16;  // pixel rows of a tile: a 4:4:4 MCU row is eight rows high
-    constexpr int QROWS = TROWS / 2;           // its quad rows
-    __shared__ __attribute__((aligned(8))) uint8_t s_yt[BLK / 64][TROWS * 128];
-    constexpr int CROWS = BASE == 3 ? 16 : 8;  // chroma rows of a tile: 4:2:2 chroma is not subsampled vertically
-    constexpr int CPITCH = BASE == 1 ? 128 : 64;  // bytes of a chroma row: 4:4:4 chroma is not subsampled at all
-    constexpr int NU = BASE == 3 ? 8 : 6;      // eight-block units of a tile
-    __shared__ __attribute__((aligned(8))) uint8_t s_ct[BLK / 64][2][CROWS * CPITCH];
+    __shared__ __attribute__((aligned(8))) uint8_t s_yt[BLK / 64][G::TROWS * 128];
+    __shared__ __attribute__((aligned(8))) uint8_t s_ct[BLK / 64][2][G::CROWS * G::CPITCH];
     // one workgroup's tables and tiles must fit a CU's LDS (the 768-thread HLG / PQ workgroups carry twelve tiles next to the
     // output-code buckets)
     static_assert(sizeof s_srgb + sizeof s_gain + sizeof s_u8f + sizeof s_tap + sizeof s_fac + sizeof s_cv + sizeof s_cu + sizeof s_code + sizeof s_idw +
                       sizeof s_ws + sizeof s_q + sizeof s_yt + sizeof s_ct <= 160 * 1024,
                   "the coefficient-input workgroup exceeds the 160 KB of LDS of a CU");
     const CoefSrc* __restrict__ cs = p.coef_src;
-    if (tid < 192) s_q[tid >> 6][tid & 63] = cs->q[tid >> 6][tid & 63];
+    coef_tile::stage_q(s_q, cs->q, tid);
     __syncthreads();
     const int wv = (int)__builtin_amdgcn_readfirstlane(tid >> 6);
     int* ws = s_ws[wv];
-    uint8_t* yt = s_yt[wv];
-    uint8_t* cbt = s_ct[wv][0];
-    uint8_t* crt = s_ct[wv][1];
+    uint8_t* const yt = s_yt[wv];
+    uint8_t* const cbt = s_ct[wv][0];
+    uint8_t* const crt = s_ct[wv][1];
+    uint8_t* const tile[3] = {yt, cbt, crt};
     const int rr = (int)lane >> 3, rb = (int)lane & 7;
-    const int16_t* cy = cs->coef[0];
-    const int16_t* ccb = cs->coef[1];
-    const int16_t* ccr = cs->coef[2];
-    const int bw0 = cs->bw[0], bh0 = cs->bh[0], bw1 = cs->bw[1], bh1 = cs->bh[1], bw2 = cs->bw[2], bh2 = cs->bh[2];
-    const uint32_t tiles_x = (p.sdr.w + 127) >> 7, tiles_y = (p.sdr.h + TROWS - 1) / TROWS, ntiles = tiles_x * tiles_y;
+    const int16_t* const coef[3] = {cs->coef[0], cs->coef[1], cs->coef[2]};
+    const int bw[3] = {cs->bw[0], cs->bw[1], cs->bw[2]}, bh[3] = {cs->bh[0], cs->bh[1], cs->bh[2]};
+    const uint32_t tiles_x = (p.sdr.w + 127) >> 7, tiles_y = (p.sdr.h + G::TROWS - 1) / G::TROWS, ntiles = tiles_x * tiles_y;
     const uint32_t nwaves = gridDim.x * (BLK / 64);
     auto tiles = [&](auto GM) {
     for (uint32_t t = wave; t < ntiles; t += nwaves) {
       const uint32_t ty = t / tiles_x, tx = t - ty * tiles_x;
-      // the tile's eight-block units: Y rows 2ty, 2ty+1 x two halves, then Cb, Cr (4:2:0) or Cb rows 2ty, 2ty+1, Cr rows 2ty,
-      // 2ty+1 (4:2:2) (all loads issued up front); 4:4:4: block row ty of Y, Cb, Cr x two halves
-      int v[NU][8];
-      int big[NU] = {};
+      int v[G::NU][8];
+      int big[G::NU] = {};
+      // all loads issued up front.  The 4:4:4 tile keeps its own loop here and at the stores (block row ty of Y, Cb, Cr x two halves):
+      // through load_units / transform_units its linear F16 kernel measured up to 0.19 us of 36.7 slower (profiles/README.md)
       if constexpr (BASE == 1) {
-        const int16_t* const cc[3] = {cy, ccb, ccr};
-        const int bwc[3] = {bw0, bw1, bw2}, bhc[3] = {bh0, bh1, bh2};
 #pragma unroll
         for (int u = 0; u < 6; u++) {
           int q[8];
 #pragma unroll
           for (int c = 0; c < 8; c++) q[c] = s_q[u >> 1][rr * 8 + c];
-          idct::load_dequant_row(cc[u >> 1], bwc[u >> 1], (int)ty, (int)(tx * 16) + (u & 1) * 8 + rb, rr, q, v[u], big[u], (int)ty < bhc[u >> 1]);
+          idct::load_dequant_row(coef[u >> 1], bw[u >> 1], (int)ty, (int)(tx * 16) + (u & 1) * 8 + rb, rr, q, v[u], big[u], (int)ty < bh[u >> 1]);
         }
       } else {
-        int q[8];
-#pragma unroll
-        for (int c = 0; c < 8; c++) q[c] = s_q[0][rr * 8 + c];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const int by = (int)(2 * ty) + (u >> 1);
-          idct::load_dequant_row(cy, bw0, by, (int)(tx * 16) + (u & 1) * 8 + rb, rr, q, v[u], big[u], by < bh0);
-        }
-#pragma unroll
-        for (int c = 0; c < 8; c++) q[c] = s_q[1][rr * 8 + c];
-        if constexpr (BASE == 3) {
-#pragma unroll
-          for (int k = 0; k < 2; k++) {
-            const int by = (int)(2 * ty) + k;
-            idct::load_dequant_row(ccb, bw1, by, (int)(tx * 8) + rb, rr, q, v[4 + k], big[4 + k], by < bh1);
-          }
-        } else {
-          idct::load_dequant_row(ccb, bw1, (int)ty, (int)(tx * 8) + rb, rr, q, v[4], big[4], (int)ty < bh1);
-        }
-#pragma unroll
-        for (int c = 0; c < 8; c++) q[c] = s_q[2][rr * 8 + c];
-        if constexpr (BASE == 3) {
-#pragma unroll
-          for (int k = 0; k < 2; k++) {
-            const int by = (int)(2 * ty) + k;
-            idct::load_dequant_row(ccr, bw2, by, (int)(tx * 8) + rb, rr, q, v[6 + k], big[6 + k], by < bh2);
-          }
-        } else {
-          idct::load_dequant_row(ccr, bw2, (int)ty, (int)(tx * 8) + rb, rr, q, v[5], big[5], (int)ty < bh2);
-        }
+        coef_tile::load_units<SAMPLING, 0, G::NU>(s_q, coef, bw, bh, tx, ty, rr, rb, v, big);
       }
       const uint32_t xraw = tx * 128 + lane * 2;
       const bool lane_ok = xraw < p.sdr.w;
       col[0] = make_col(min(xraw, p.sdr.w - 2));
       Raw a = fetch(ty * QROWS, H0{});  // the first quad row's gain-map bytes are in flight during the transforms
+      if constexpr (BASE == 1) {
 #pragma unroll
-      for (int u = 0; u < NU; u++) {
-        uint32_t sm8[8];
-        idct::idct_wave(ws, v[u], big[u], rr, rb, sm8);
-        const uint32_t lo = sm8[0] | (sm8[1] << 8) | (sm8[2] << 16) | (sm8[3] << 24);
-        const uint32_t hi = sm8[4] | (sm8[5] << 8) | (sm8[6] << 16) | (sm8[7] << 24);
-        uint8_t* d;
-        if constexpr (BASE == 1) {
-          d = (u < 2 ? yt : (u < 4 ? cbt : crt)) + rr * 128 + ((u & 1) * 8 + rb) * 8;
-        } else if constexpr (BASE == 3) {
-          d = (u < 4) ? yt + ((u >> 1) * 8 + rr) * 128 + ((u & 1) * 8 + rb) * 8
-                      : (u < 6 ? cbt : crt) + ((u & 1) * 8 + rr) * 64 + rb * 8;
-        } else {
-          d = (u < 4) ? yt + ((u >> 1) * 8 + rr) * 128 + ((u & 1) * 8 + rb) * 8
-                      : (u == 4 ? cbt : crt) + rr * 64 + rb * 8;
+        for (int u = 0; u < 6; u++) {
+          uint32_t sm8[8];
+          idct::idct_wave(ws, v[u], big[u], rr, rb, sm8);
+          *(uint2*)((u < 2 ? yt : (u < 4 ? cbt : crt)) + rr * 128 + ((u & 1) * 8 + rb) * 8) = coef_tile::pack8(sm8);
         }
-        *(uint2*)d = make_uint2(lo, hi);
+      } else {
+        coef_tile::transform_units<SAMPLING, 0, G::NU>(ws, tile, rr, rb, v, big);
       }
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the tile is complete in LDS
+      coef_tile::tile_ready();
 #pragma unroll 1
       for (uint32_t qr = 0; qr < QROWS; qr++) {
         const uint32_t qy = ty * QROWS + qr;
@@ -1239,8 +1198,7 @@ template <int OUT, int MAPFMT, int SMODE, int BASE>
 hipError_t launch_quad_coef(const ApplyParams& p, hipStream_t s) {
   constexpr int BLK = quad_block<OUT>();
   static const int resident = resident_blocks(apply_quad_kernel_s96<OUT, MAPFMT, SMODE, BASE, 1>, BLK, 96);
-  constexpr uint32_t trows = BASE == 1 ? 8 : 16;
-  const uint32_t ntiles = ((p.sdr.w + 127) / 128) * ((p.sdr.h + trows - 1) / trows);
+  const uint32_t ntiles = coef_tile::tiles_of(p.sdr.w, p.sdr.h, BASE == 0 ? 420 : (BASE == 3 ? 422 : 444));
   uint32_t grid = (ntiles + BLK / 64 - 1) / (BLK / 64);
   if (grid > (uint32_t)resident) grid = (uint32_t)resident;
   ApplyParams q = p;
@@ -1250,48 +1208,44 @@ hipError_t launch_quad_coef(const ApplyParams& p, hipStream_t s) {
   hipLaunchKernelGGL((apply_quad_kernel_s96<OUT, MAPFMT, SMODE, BASE, 1>), dim3(grid), dim3(BLK), 0, s, q);
   return hipGetLastError();
 }
-template <int OUT, int MAPFMT, int BASE>
-hipError_t launch_quad_coef_s(const ApplyParams& p, int smode, hipStream_t s) {
-  return smode == 0 ? launch_quad_coef<OUT, MAPFMT, 0, BASE>(p, s) : launch_quad_coef<OUT, MAPFMT, 1, BASE>(p, s);
+// The template ladder of both inputs: SRC 0 planes (launch_quad), 1 coefficients (launch_quad_coef: 4:2:0, 4:4:4 and 4:2:2 bases only)
+template <int SRC, int OUT, int MAPFMT, int BASE>
+hipError_t launch_quad_s(const ApplyParams& p, int smode, hipStream_t s) {
+  if constexpr (SRC == 1) return smode == 0 ? launch_quad_coef<OUT, MAPFMT, 0, BASE>(p, s) : launch_quad_coef<OUT, MAPFMT, 1, BASE>(p, s);
+  else return smode == 0 ? launch_quad<OUT, MAPFMT, 0, BASE>(p, s) : launch_quad<OUT, MAPFMT, 1, BASE>(p, s);
 }
-template <int OUT, int BASE>
-hipError_t launch_quad_coef_m(const ApplyParams& p, int mapfmt, int smode, hipStream_t s) {
+template <int SRC, int OUT, int BASE>
+hipError_t launch_quad_m(const ApplyParams& p, int mapfmt, int smode, hipStream_t s) {
   switch (mapfmt) {
-    case 0: return launch_quad_coef_s<OUT, 0, BASE>(p, smode, s);
-    case 1: return launch_quad_coef_s<OUT, 1, BASE>(p, smode, s);
-    default: return launch_quad_coef_s<OUT, 2, BASE>(p, smode, s);
+    case 0: return launch_quad_s<SRC, OUT, 0, BASE>(p, smode, s);
+    case 1: return launch_quad_s<SRC, OUT, 1, BASE>(p, smode, s);
+    default: return launch_quad_s<SRC, OUT, 2, BASE>(p, smode, s);
   }
 }
-template <int BASE>
-hipError_t launch_quad_coef_o(const ApplyParams& p, int out, int mapfmt, int smode, hipStream_t s) {
+template <int SRC, int OUT>
+hipError_t launch_quad_b(const ApplyParams& p, int base, int mapfmt, int smode, hipStream_t s) {
+  switch (base) {
+    case 0: return launch_quad_m<SRC, OUT, 0>(p, mapfmt, smode, s);
+    case 1: return launch_quad_m<SRC, OUT, 1>(p, mapfmt, smode, s);
+    case 3: return launch_quad_m<SRC, OUT, 3>(p, mapfmt, smode, s);
+    default:
+      if constexpr (SRC == 1) return hipErrorInvalidValue;
+      else return launch_quad_m<SRC, OUT, 2>(p, mapfmt, smode, s);
+  }
+}
+template <int SRC>
+hipError_t launch_quad_o(const ApplyParams& p, int out, int base, int mapfmt, int smode, hipStream_t s) {
   switch (out) {
-    case 0: return launch_quad_coef_m<0, BASE>(p, mapfmt, smode, s);
-    case 1: return launch_quad_coef_m<1, BASE>(p, mapfmt, smode, s);
-    default: return launch_quad_coef_m<2, BASE>(p, mapfmt, smode, s);
+    case 0: return launch_quad_b<SRC, 0>(p, base, mapfmt, smode, s);
+    case 1: return launch_quad_b<SRC, 1>(p, base, mapfmt, smode, s);
+    default: return launch_quad_b<SRC, 2>(p, base, mapfmt, smode, s);
   }
 }
 
-template <int OUT, int MAPFMT, int BASE>
-hipError_t launch_quad_s(const ApplyParams& p, int smode, hipStream_t s) {
-  return smode == 0 ? launch_quad<OUT, MAPFMT, 0, BASE>(p, s) : launch_quad<OUT, MAPFMT, 1, BASE>(p, s);
-}
-template <int OUT, int BASE>
-hipError_t launch_quad_m(const ApplyParams& p, int mapfmt, int smode, hipStream_t s) {
-  switch (mapfmt) {
-    case 0: return launch_quad_s<OUT, 0, BASE>(p, smode, s);
-    case 1: return launch_quad_s<OUT, 1, BASE>(p, smode, s);
-    default: return launch_quad_s<OUT, 2, BASE>(p, smode, s);
-  }
-}
-template <int OUT>
-hipError_t launch_quad_b(const ApplyParams& p, int base, int mapfmt, int smode, hipStream_t s) {
-  switch (base) {
-    case 0: return launch_quad_m<OUT, 0>(p, mapfmt, smode, s);
-    case 1: return launch_quad_m<OUT, 1>(p, mapfmt, smode, s);
-    case 3: return launch_quad_m<OUT, 3>(p, mapfmt, smode, s);
-    default: return launch_quad_m<OUT, 2>(p, mapfmt, smode, s);
-  }
-}
+// the kernels' template indices of a request: OUT (linear / HLG / PQ), MAPFMT (Y400 / RGB888 / RGBA8888), BASE (4:2:0 / 4:4:4 / RGBA8888 / 4:2:2)
+inline int out_index(const ApplyParams& p) { return p.out_ct == UHDR_CT_LINEAR ? 0 : (p.out_ct == UHDR_CT_HLG ? 1 : 2); }
+inline int mapfmt_index(const ApplyParams& p) { return p.gm.fmt == UHDR_IMG_FMT_8bppYCbCr400 ? 0 : (p.gm.fmt == UHDR_IMG_FMT_24bppRGB888 ? 1 : 2); }
+inline int base_index(const ApplyParams& p) { return p.sdr.fmt == UHDR_IMG_FMT_12bppYCbCr420 ? 0 : (p.sdr.fmt == UHDR_IMG_FMT_24bppYCbCr444 ? 1 : (p.sdr.fmt == UHDR_IMG_FMT_16bppYCbCr422 ? 3 : 2)); }
 
 inline bool aligned_to(const void* ptr, size_t a) { return ((uintptr_t)ptr % a) == 0; }
 
@@ -1300,8 +1254,7 @@ inline bool aligned_to(const void* ptr, size_t a) { return ((uintptr_t)ptr % a) 
 // Does the quad kernel's layout contract hold?  Returns its SMODE (0 / 1) or -1.
 int apply_quad_mode(const ApplyParams& p) {
   if (p.resize_on) return -1;  // the resizing sampler exists in the generic kernel only
-  const int out = p.out_ct == UHDR_CT_LINEAR ? 0 : (p.out_ct == UHDR_CT_HLG ? 1 : 2);
-  const int mapfmt = p.gm.fmt == UHDR_IMG_FMT_8bppYCbCr400 ? 0 : (p.gm.fmt == UHDR_IMG_FMT_24bppRGB888 ? 1 : 2);
+  const int out = out_index(p), mapfmt = mapfmt_index(p);
   const size_t out_bytes = out == 0 ? 8 : 4;
   // base layouts the quad kernel reads: 4:2:0, 4:2:2, 4:4:4 (chroma pairs as 16-bit loads), packed RGBA8888 (8-byte loads)
   bool base_ok = false;
@@ -1343,32 +1296,18 @@ int apply_quad_mode(const ApplyParams& p) {
 // 4:2:2 or 4:4:4 -- of the image the coefficients decode to).  Only the quad kernel has this input: hipErrorInvalidValue when its
 // contract does not hold.
 hipError_t launch_apply_gainmap_coef(const ApplyParams& p, hipStream_t s) {
-  const int out = p.out_ct == UHDR_CT_LINEAR ? 0 : (p.out_ct == UHDR_CT_HLG ? 1 : 2);
-  const int mapfmt = p.gm.fmt == UHDR_IMG_FMT_8bppYCbCr400 ? 0 : (p.gm.fmt == UHDR_IMG_FMT_24bppRGB888 ? 1 : 2);
   const int smode = apply_quad_mode(p);
   if (smode < 0 || !p.coef_src || p.n_frames > 1) return hipErrorInvalidValue;
-  if (p.sdr.fmt == UHDR_IMG_FMT_12bppYCbCr420) return launch_quad_coef_o<0>(p, out, mapfmt, smode, s);
-  if (p.sdr.fmt == UHDR_IMG_FMT_16bppYCbCr422) return launch_quad_coef_o<3>(p, out, mapfmt, smode, s);
-  if (p.sdr.fmt == UHDR_IMG_FMT_24bppYCbCr444) return launch_quad_coef_o<1>(p, out, mapfmt, smode, s);
-  return hipErrorInvalidValue;
+  return launch_quad_o<1>(p, out_index(p), base_index(p), mapfmt_index(p), smode, s);  // a packed base: hipErrorInvalidValue
 }
 
 // Picks the quad kernel when its layout assumptions hold, otherwise the generic one.
 // Batch mode (p.n_frames > 1) exists on the quad path only; the host layer falls back to one
 // launch per frame when apply_quad_mode() says no.
 hipError_t launch_apply_gainmap(const ApplyParams& p, hipStream_t s) {
-  const int out = p.out_ct == UHDR_CT_LINEAR ? 0 : (p.out_ct == UHDR_CT_HLG ? 1 : 2);
-  const int mapfmt = p.gm.fmt == UHDR_IMG_FMT_8bppYCbCr400 ? 0 : (p.gm.fmt == UHDR_IMG_FMT_24bppRGB888 ? 1 : 2);
+  const int out = out_index(p);
   const int smode = apply_quad_mode(p);
-  if (smode >= 0) {
-    const int base = p.sdr.fmt == UHDR_IMG_FMT_12bppYCbCr420 ? 0 : (p.sdr.fmt == UHDR_IMG_FMT_24bppYCbCr444 ? 1 :
-                     (p.sdr.fmt == UHDR_IMG_FMT_16bppYCbCr422 ? 3 : 2));
-    switch (out) {
-      case 0: return launch_quad_b<0>(p, base, mapfmt, smode, s);
-      case 1: return launch_quad_b<1>(p, base, mapfmt, smode, s);
-      default: return launch_quad_b<2>(p, base, mapfmt, smode, s);
-    }
-  }
+  if (smode >= 0) return launch_quad_o<0>(p, out, base_index(p), mapfmt_index(p), smode, s);
   if (p.n_frames > 1) return hipErrorInvalidValue;
   const size_t total = (size_t)((p.sdr.w + kBlock - 1) / kBlock) * p.sdr.h;  // tiles
   int grid = (int)min(total, (size_t)2048);

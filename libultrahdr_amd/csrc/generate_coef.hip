@@ -5,7 +5,8 @@
 // (apply_gainmap.hip) on the encode side.
 //
 // A WAVE takes a 128 x 16 pixel tile: 32 luma + 8 + 8 chroma blocks at 4:2:0 (VSAMP 2), 32 + 16 + 16 at 4:2:2 (VSAMP 1).  It
-// dequantises and inverse-transforms them eight blocks at a time (idct_core.h) into its own LDS tile, then produces the tile's
+// dequantises and inverse-transforms them through the stage both kernels share (coef_tile.h: the unit layout, the loads, the
+// transforms and the stores into the wave's LDS tile; here the luma units, then the chroma units), then produces the tile's
 // map pixels with generate_kernel's sequence of operations (generate_gainmap.hip): the SDR sample is what fetch_pixel returns
 // for the byte the stand-alone IDCT would have stored, box sums run dy outer / dx inner from 0.0f with one divide, and
 // everything behind the sample is the shared code of encode_core.h.  Scale factors 1, 2 and 4 divide the tile, so a box
@@ -16,7 +17,7 @@
 // IDCT workspace = 68 / 76 KB two pass -> two workgroups (16 waves) per CU; the one-pass step table adds 16 KB -> one.
 #include "cu_count.h"
 #include "encode_core.h"
-#include "idct_core.h"
+#include "coef_tile.h"
 #include "lds_copy.h"
 
 namespace uhdr {
@@ -68,14 +69,14 @@ __device__ __forceinline__ Color3 sample_tile_box(const uint8_t* yt, const uint8
 template <int VSAMP, int HDRF, bool TWO_PASS, bool QUAD>
 __global__ __launch_bounds__(kCoefBlock) void generate_coef_kernel(const GenParams p, const CoefSrc cs, float* partials) {
   static_assert(!QUAD || HDRF == UHDR_IMG_FMT_24bppYCbCrP010, "the quad fetch is P010's");
-  constexpr int CROWS = 16 / VSAMP;  // chroma rows of a tile
-  constexpr int NC = 2 / VSAMP;      // eight-block units per chroma component
+  constexpr int SAMPLING = VSAMP == 2 ? 420 : 422;
+  using G = coef_tile::Geom<SAMPLING>;
   __shared__ GenLds L;
   __shared__ uint2 s_gain8[TWO_PASS ? 1 : kStepTabMax];  // one pass: clamped gain -> map byte (host_tables.cpp)
   __shared__ int s_ws[kCoefWaves][8 * 8 * 9];
   __shared__ int s_q[3][64];
-  __shared__ __attribute__((aligned(8))) uint8_t s_yt[kCoefWaves][16 * 128];
-  __shared__ __attribute__((aligned(8))) uint8_t s_ct[kCoefWaves][2][CROWS * 64];
+  __shared__ __attribute__((aligned(8))) uint8_t s_yt[kCoefWaves][G::TROWS * 128];
+  __shared__ __attribute__((aligned(8))) uint8_t s_ct[kCoefWaves][2][G::CROWS * G::CPITCH];
   static_assert(sizeof(GenLds) + sizeof s_gain8 + sizeof s_ws + sizeof s_q + sizeof s_yt + sizeof s_ct + 256 <= (TWO_PASS ? 80 : 160) * 1024,
                 "two-pass workgroups are sized for two per CU, one-pass workgroups for one");
   const uint32_t tid = threadIdx.x;
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(kCoefBlock) void generate_coef_kernel(const GenPara
   if (p.hdr_inv_lut)
     for (uint32_t i = tid; i < (uint32_t)p.hdr_inv_n; i += kCoefBlock) L.hdr[i] = p.hdr_inv_lut[i];
   fill_unorm_tables(L.unorm, tid, kCoefBlock);
-  if (tid < 192) s_q[tid >> 6][tid & 63] = cs.q[tid >> 6][tid & 63];
+  coef_tile::stage_q(s_q, cs.q, tid);
   __syncthreads();
 
   const bool hdr_lut = p.hdr_inv_lut != nullptr, hdr_lut_4096 = p.hdr_inv_n == kInvOetfN;
@@ -109,9 +110,10 @@ __global__ __launch_bounds__(kCoefBlock) void generate_coef_kernel(const GenPara
   const uint32_t lane = tid & 63;
   const int wv = (int)__builtin_amdgcn_readfirstlane(tid >> 6);
   int* ws = s_ws[wv];
-  uint8_t* yt = s_yt[wv];
-  uint8_t* cbt = s_ct[wv][0];
-  uint8_t* crt = s_ct[wv][1];
+  uint8_t* const yt = s_yt[wv];
+  uint8_t* const cbt = s_ct[wv][0];
+  uint8_t* const crt = s_ct[wv][1];
+  uint8_t* const tile[3] = {yt, cbt, crt};
   const int rr = (int)lane >> 3, rb = (int)lane & 7;
   const uint32_t w = p.sdr.w, h = p.sdr.h, mw = p.map_w, mh = p.map_h;
   const uint32_t tiles_x = (w + 127) >> 7, tiles_y = (h + 15) >> 4, ntiles = tiles_x * tiles_y;
@@ -119,44 +121,17 @@ __global__ __launch_bounds__(kCoefBlock) void generate_coef_kernel(const GenPara
   const uint32_t nwaves = gridDim.x * kCoefWaves;
   for (uint32_t t = wave; t < ntiles; t += nwaves) {
     const uint32_t ty = t / tiles_x, tx = t - ty * tiles_x;
-    {  // luma: block rows 2 ty, 2 ty + 1 x two halves of sixteen blocks (all four loads issued up front)
-      int q[8], v[4][8], big[4] = {};
-#pragma unroll
-      for (int c = 0; c < 8; c++) q[c] = s_q[0][rr * 8 + c];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int by = (int)(2 * ty) + (u >> 1);
-        idct::load_dequant_row(cs.coef[0], cs.bw[0], by, (int)(tx * 16) + (u & 1) * 8 + rb, rr, q, v[u], big[u], by < cs.bh[0]);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        uint32_t sm8[8];
-        idct::idct_wave(ws, v[u], big[u], rr, rb, sm8);
-        *(uint2*)(yt + ((u >> 1) * 8 + rr) * 128 + ((u & 1) * 8 + rb) * 8) =
-            make_uint2(sm8[0] | (sm8[1] << 8) | (sm8[2] << 16) | (sm8[3] << 24), sm8[4] | (sm8[5] << 8) | (sm8[6] << 16) | (sm8[7] << 24));
-      }
+    {  // luma, then chroma (Cb, then Cr): v[4][8] at a time, not v[8][8]
+      int v[G::NLUMA][8], big[G::NLUMA] = {};
+      coef_tile::load_units<SAMPLING, 0, G::NLUMA>(s_q, cs.coef, cs.bw, cs.bh, tx, ty, rr, rb, v, big);
+      coef_tile::transform_units<SAMPLING, 0, G::NLUMA>(ws, tile, rr, rb, v, big);
     }
-    {  // chroma: block row ty (4:2:0) or rows 2 ty, 2 ty + 1 (4:2:2) of eight blocks, Cb then Cr
-      int q[2][8], v[2 * NC][8], big[2 * NC] = {};
-#pragma unroll
-      for (int k = 0; k < 2; k++)
-#pragma unroll
-        for (int c = 0; c < 8; c++) q[k][c] = s_q[1 + k][rr * 8 + c];
-#pragma unroll
-      for (int u = 0; u < 2 * NC; u++) {
-        const int k = u / NC, by = VSAMP == 2 ? (int)ty : (int)(2 * ty) + (u % NC);
-        idct::load_dequant_row(cs.coef[1 + k], cs.bw[1 + k], by, (int)(tx * 8) + rb, rr, q[k], v[u], big[u], by < cs.bh[1 + k]);
-      }
-#pragma unroll
-      for (int u = 0; u < 2 * NC; u++) {
-        uint32_t sm8[8];
-        idct::idct_wave(ws, v[u], big[u], rr, rb, sm8);
-        *(uint2*)((u / NC ? crt : cbt) + ((u % NC) * 8 + rr) * 64 + rb * 8) =
-            make_uint2(sm8[0] | (sm8[1] << 8) | (sm8[2] << 16) | (sm8[3] << 24), sm8[4] | (sm8[5] << 8) | (sm8[6] << 16) | (sm8[7] << 24));
-      }
+    {
+      int v[G::NU - G::NLUMA][8], big[G::NU - G::NLUMA] = {};
+      coef_tile::load_units<SAMPLING, G::NLUMA, G::NU>(s_q, cs.coef, cs.bw, cs.bh, tx, ty, rr, rb, v, big);
+      coef_tile::transform_units<SAMPLING, G::NLUMA, G::NU>(ws, tile, rr, rb, v, big);
     }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the tile is complete in LDS
+    coef_tile::tile_ready();
     if constexpr (QUAD) {  // eight quad rows of 64 quads
       const uint32_t qx = tx * 64 + lane;
 #pragma unroll 1

@@ -1,7 +1,8 @@
 // The libjpeg JDCT_ISLOW inverse DCT as wave-level building blocks (jidctint.c: CONST_BITS 13, PASS1_BITS 2:
 // column pass from the dequantized coefficients, row pass, descale by 2^18, +128, range-limit table indexed
-// modulo 1024).  Shared by the stand-alone decode kernels (jpeg_decode.hip) and the applyGainMap variant that
-// consumes the base image in coefficient form (apply_gainmap.hip).  See jpeg_decode.hip for the provenance notes.
+// modulo 1024).  Used directly by the stand-alone decode kernels (jpeg_decode.hip, jpeg_upsample.hip) and, through the
+// coefficient-tile stage of coef_tile.h, by the kernels that consume an image in coefficient form (apply_gainmap.hip,
+// generate_coef.hip).  See jpeg_decode.hip for the provenance notes.
 #pragma once
 #include "jdct_fix.h"
 #include "uhdr_types.h"

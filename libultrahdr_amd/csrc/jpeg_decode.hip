@@ -18,7 +18,7 @@
 // coefficients that came out of an 8-bit forward DCT -- all butterfly operands are below 2^23 and
 // the multiplies are the full-rate 24-bit ones; otherwise (corrupt streams) the tile takes the
 // 32-bit multiply path, whose wrap-around equals libjpeg's INT32 arithmetic.
-#include "idct_core.h"
+#include "coef_tile.h"
 #include "uhdr_types.h"
 #include "upsample_core.h"
 
@@ -26,7 +26,7 @@ namespace uhdr {
 namespace {
 
 using namespace idct;
-using namespace upsample;  // FIX16, ycc_px (jdcolor.c ycc_rgb_convert), ycc_green_constants, pack_rgb888, resident_grid
+using namespace upsample;  // FIX16, ycc_px (jdcolor.c ycc_rgb_convert), ycc_green_constants, pack_rgb888, store_px8, resident_grid
 
 constexpr int kBlock = 256;
 
@@ -57,14 +57,13 @@ __global__ __launch_bounds__(kBlock) void idct_dequant_kernel(const int16_t* __r
     uint32_t s[8];
     idct_wave(ws, v, big, rr, rb, s);
     if (bx < bw) {
-      const uint32_t lo = s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
-      const uint32_t hi = s[4] | (s[5] << 8) | (s[6] << 16) | (s[7] << 24);
+      const uint2 o = coef_tile::pack8(s);
       uint8_t* dst = plane + (size_t)(by * 8 + rr) * stride + (size_t)bx * 8;
       if (vec_store) {
-        *(uint2*)dst = make_uint2(lo, hi);
+        *(uint2*)dst = o;
       } else {
 #pragma unroll
-        for (int c = 0; c < 4; c++) { dst[c] = (uint8_t)(lo >> (8 * c)); dst[4 + c] = (uint8_t)(hi >> (8 * c)); }
+        for (int c = 0; c < 4; c++) { dst[c] = (uint8_t)(o.x >> (8 * c)); dst[4 + c] = (uint8_t)(o.y >> (8 * c)); }
       }
     }
   }
@@ -214,28 +213,7 @@ __global__ __launch_bounds__(kBlock) void idct_dequant_rgb_kernel(const IdctRgbA
       uint32_t px[8];
 #pragma unroll
       for (int c = 0; c < 8; c++) px[c] = ycc_px(sy[c], sb[c], sr[c], a.k_cr_g, a.k_cb_g);
-      uint8_t* dst = a.rgb + (size_t)y * a.pitch + (size_t)x0 * BPP;
-      if (vec_ok && x0 + 8 <= a.w) {
-        if constexpr (BPP == 4) {
-          *(uint4*)dst = make_uint4(px[0], px[1], px[2], px[3]);
-          *(uint4*)(dst + 16) = make_uint4(px[4], px[5], px[6], px[7]);
-        } else {
-          uint32_t d[6];
-          pack_rgb888(px, d);
-          pack_rgb888(px + 4, d + 3);
-          *(uint2*)dst = make_uint2(d[0], d[1]);
-          *(uint2*)(dst + 8) = make_uint2(d[2], d[3]);
-          *(uint2*)(dst + 16) = make_uint2(d[4], d[5]);
-        }
-      } else {
-#pragma unroll
-        for (int c = 0; c < 8; c++) {
-          if (x0 + c < a.w) {
-            dst[c * BPP] = (uint8_t)px[c]; dst[c * BPP + 1] = (uint8_t)(px[c] >> 8); dst[c * BPP + 2] = (uint8_t)(px[c] >> 16);
-            if constexpr (BPP == 4) dst[c * BPP + 3] = 255;
-          }
-        }
-      }
+      store_px8<BPP>(a.rgb + (size_t)y * a.pitch + (size_t)x0 * BPP, px, x0, a.w, vec_ok);
     }
   }
 }

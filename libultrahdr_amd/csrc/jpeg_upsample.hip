@@ -25,7 +25,7 @@
 //   variant 0: the chroma needs one sample of context across MCU edges; the 8x8 chroma planes come from idct_dequant_kernel
 //     (jpeg_decode.hip) through HBM (0.5 B/px written and read for 4:2:0, 1 B/px for 4:2:2), and the lane reads its 6 samples
 //     of each chroma row it needs (two for 4:2:0, ONE for 4:2:2) with clamped indices.
-#include "idct_core.h"
+#include "coef_tile.h"
 #include "uhdr_types.h"
 #include "upsample_core.h"
 
@@ -216,9 +216,7 @@ __global__ __launch_bounds__(kBlock) void idct_upsample_rgb_kernel(const Upsampl
       load_dequant_row(a.coef[0], a.bw[0], by, bx, rr, ql, v, big, by < a.bh[0]);
       uint32_t s[8];
       idct_wave(L.ws, v, big, rr, rb, s);
-      const uint32_t lo = s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
-      const uint32_t hi = s[4] | (s[5] << 8) | (s[6] << 16) | (s[7] << 24);
-      *(uint2*)&L.tile[0][lby * 8 + rr][lbx * 8] = make_uint2(lo, hi);
+      *(uint2*)&L.tile[0][lby * 8 + rr][lbx * 8] = coef_tile::pack8(s);
     }
     if constexpr (VARIANT == 1) {
       if constexpr (VSAMP == 2) chroma_idct_16x16(a, L, lane, ty, tx);

@@ -7,6 +7,7 @@ import functools
 import numpy as np
 import pytest
 
+from coef_cases import S420, S422, S444, grids, quality_tables, smooth_coefs as _smooth_coefs, wild_coefs
 from libultrahdr_amd import capi as A
 from libultrahdr_amd import synth
 from libultrahdr_amd.images import Image
@@ -14,7 +15,6 @@ from oracle import loader as L
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-S420, S422, S444 = [(2, 2), (1, 1), (1, 1)], [(2, 1), (1, 1), (1, 1)], [(1, 1)] * 3
 F16, P1010102 = A.UHDR_IMG_FMT_64bppRGBAHalfFloat, A.UHDR_IMG_FMT_32bppRGBA1010102
 Y422 = A.UHDR_IMG_FMT_16bppYCbCr422
 
@@ -34,22 +34,6 @@ def out_fmt(out_ct):
     return F16 if out_ct == A.UHDR_CT_LINEAR else P1010102
 
 
-def grids(w, h, sampling):
-    """[(blocks_w, blocks_h)] per component: libjpeg's width_in_blocks / height_in_blocks."""
-    hmax, vmax = max(s[0] for s in sampling), max(s[1] for s in sampling)
-    return [((-(-w * hs // hmax) + 7) // 8, (-(-h * vs // vmax) + 7) // 8) for hs, vs in sampling]
-
-
-def _smooth_coefs(dims, qts, rng):
-    """tests/test_gpu_parity.py::_coef_case's planes: a smooth field + noise, so that the decoded image is not just clipped garbage."""
-    coefs = []
-    for c, (bw, bh) in enumerate(dims):
-        yy, xx = np.mgrid[0:bh * 8, 0:bw * 8]
-        pl = 128 + 90 * np.sin(xx / (13.0 + 5 * c)) * np.cos(yy / (9.0 + 3 * c)) + rng.normal(0, 12, (bh * 8, bw * 8))
-        coefs.append(L.fdct_quant_port(np.ascontiguousarray(np.clip(pl, 0, 255).astype(np.uint8)), bw * 8, bw, bh, qts[c]))
-    return coefs
-
-
 def _decode422(coefs, qts, w, h):
     dec = Image(Y422, w, h, A.UHDR_CG_BT_709, A.UHDR_CT_SRGB, A.UHDR_CR_FULL_RANGE, align=2)
     for c in range(3):
@@ -66,9 +50,9 @@ def coef_case(w, h, quality, wild=False):
     dims = grids(w, h, S422)
     if wild:  # the full int16 range with all-255 tables: the 32-bit multiply path and the modulo-1024 range limit
         qts = [np.full(64, 255, dtype=np.uint16)] * 3
-        coefs = [rng.integers(-32768, 32768, (bh, bw, 64), dtype=np.int16) for bw, bh in dims]
+        coefs = wild_coefs(dims, rng)
     else:
-        qts = [L.quant_table_port(quality, False), L.quant_table_port(quality, True), L.quant_table_port(max(quality - 10, 1), True)]
+        qts = quality_tables(quality)
         coefs = _smooth_coefs(dims, qts, rng)
     return coefs, qts, _decode422(coefs, qts, w, h)
 
