@@ -581,6 +581,15 @@ uhdr_error_info_t uhdr_hip_generate_gainmap_coef422_dev(uhdr_hip_ctx_t* ctx, con
                                                         unsigned int w, unsigned int h, uhdr_color_gamut_t sdr_cg,
                                                         const uhdr_raw_image_t* hdr_intent, const uhdr_hip_encode_cfg_t* cfg,
                                                         uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_img);
+/* uhdr_hip_generate_gainmap_coef444_dev: arguments and behaviour as uhdr_hip_generate_gainmap_coef_dev; the SDR intent of the API-3
+ * encode (lib/src/jpegr.cpp:327-385) is a 4:4:4 frame (1x1 / 1x1 / 1x1, block grids as for uhdr_hip_apply_gainmap_coef444_dev) and a wave's
+ * tile is an MCU row of 128 x 8 pixels (16 + 16 + 16 blocks) through the same dequantize + IDCT stage (jpegdecoderhelper.cpp:468-535);
+ * the result is that of generateGainMap (lib/src/jpegr.cpp:530-1050) in the staged operators on the UHDR_IMG_FMT_24bppYCbCr444 image.
+ * uhdr_hip_generate_gainmap_coef_dev and _coef422_dev answer UHDR_CODEC_INVALID_PARAM for a 4:4:4 block grid, this one for theirs. */
+uhdr_error_info_t uhdr_hip_generate_gainmap_coef444_dev(uhdr_hip_ctx_t* ctx, const uhdr_hip_jpeg_coefficients_t* sdr,
+                                                        unsigned int w, unsigned int h, uhdr_color_gamut_t sdr_cg,
+                                                        const uhdr_raw_image_t* hdr_intent, const uhdr_hip_encode_cfg_t* cfg,
+                                                        uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_img);
 
 /* ---- JPEG entropy stage (the step after uhdr_hip_fdct_quant) ---------------------------------
  * Baseline Huffman coding of quantized coefficient blocks with the Annex K tables -- what libjpeg does behind
@@ -996,13 +1005,13 @@ uhdr_error_info_t uhdr_hip_decode_api1_scans_any_dev(uhdr_hip_ctx_t* ctx, const 
  * tables; scan.coef is ignored); sdr_data / sdr_bytes: its entropy-coded bytes, between the SOS header and the marker that ends them;
  * sdr_cg: its colour gamut; hdr, cfg as for uhdr_hip_generate_gainmap_dev with cfg->sdr_is_601 forced to 1 (lib/src/jpegr.cpp:377);
  * qt_map: the map's {luma, chroma} quantization tables.  Sequence: uhdr_hip_huffman_decode_dev into the context's coefficient arrays ->
- * generateGainMap (lib/src/jpegr.cpp:530-1050) straight from those coefficients (uhdr_hip_generate_gainmap_coef_dev / _coef422_dev; JpegDecoderHelper's
+ * generateGainMap (lib/src/jpegr.cpp:530-1050) straight from those coefficients (uhdr_hip_generate_gainmap_coef_dev / _coef422_dev / _coef444_dev; JpegDecoderHelper's
  * dequantize + IDCT stage, jpegdecoderhelper.cpp:468-535, inside the kernel) or from planes (three uhdr_hip_idct_dequant_dev launches +
- * uhdr_hip_generate_gainmap_dev: a 4:4:4 file, a geometry the coefficient operator declines, the staged route) -> the map's coefficients (two
+ * uhdr_hip_generate_gainmap_dev: a geometry the coefficient operator declines, the staged route) -> the map's coefficients (two
  * pass: the block kernel of the fused API-1 chain behind the range kernel; one pass: the byte map in context scratch through
  * uhdr_hip_fdct_quant_dev / _rgb_dev) -> uhdr_hip_huffman_encode_dev with restart_interval 0.  Map scan, metadata and gainmap_desc equal
- * those of the staged public chain (uhdr_hip_jpeg_decode_scan -> uhdr_hip_generate_gainmap_dev -> FDCT -> Huffman).  The route of a 4:2:0 /
- * 4:2:2 file is the measured default; UHDR_HIP_API3_ROUTE=fused|staged in the environment forces one.
+ * those of the staged public chain (uhdr_hip_jpeg_decode_scan -> uhdr_hip_generate_gainmap_dev -> FDCT -> Huffman).  The route of a 4:2:0,
+ * 4:2:2 or 4:4:4 file is the measured default of its sampling; UHDR_HIP_API3_ROUTE=fused|staged in the environment forces one.
  * uhdr_hip_encode_api3_scans: sdr_data, the HDR intent's planes and map_scan are HOST memory; _dev: all three DEVICE memory.  Synchronous.
  * UHDR_CODEC_MEM_ERROR with the needed size in *map_bytes when map_capacity is too small.  UHDR_CODEC_UNSUPPORTED_FEATURE before anything is
  * uploaded or launched: grayscale, 4:4:0 and 4:1:1 files (a progressive file has no uhdr_hip_jpeg_header_t: uhdr_hip_jpeg_parse returns -8),

@@ -280,6 +280,16 @@ class UltraHdr {
                                                                                                       gainmap_metadata, gainmap_img);
   }
 
+  // ... of a 4:4:4 frame (uhdr_hip_generate_gainmap_coef444_dev): all three components on the ceil(w/8) x ceil(h/8) block grid.
+  uhdr_error_info_t generateGainMapFromCoefficients444(const uhdr_hip_jpeg_coefficients_t* sdr, unsigned int w, unsigned int h, uhdr_color_gamut_t sdr_cg,
+                                                       uhdr_raw_image_t* hdr_intent, uhdr_gainmap_metadata_t* gainmap_metadata,
+                                                       uhdr_raw_image_t* gainmap_img, bool sdr_is_601 = false, bool use_luminance = true) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, sdr_is_601 ? 1 : 0, use_luminance ? 1 : 0};
+    return uhdr_hip_generate_gainmap_coef444_dev(mCtx, sdr, w, h, sdr_cg, hdr_intent, &cfg, gainmap_metadata, gainmap_img);
+  }
+
   // JpegR::encodeJPEGR API-3 (jpegr.cpp:327-385) without the container in one call (uhdr_hip_encode_api3_scans / _dev): the compressed SDR
   // intent's parsed header and entropy-coded bytes + the raw HDR intent -> the gain map's scan.  The base image stays the caller's JPEG.
   uhdr_error_info_t encodeApi3Scans(const uhdr_hip_jpeg_header_t* sdr_jpeg, const uint8_t* sdr_data, size_t sdr_bytes, uhdr_color_gamut_t sdr_cg,

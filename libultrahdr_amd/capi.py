@@ -271,6 +271,8 @@ _SIGS = {
                                                        _P(GainmapMetadata), _P(RawImage)]),
     "uhdr_hip_generate_gainmap_coef422_dev": (ErrorInfo, [C.c_void_p, _P(JpegCoefficients), C.c_uint, C.c_uint, C.c_int, _P(RawImage), _P(EncodeCfg),
                                                           _P(GainmapMetadata), _P(RawImage)]),
+    "uhdr_hip_generate_gainmap_coef444_dev": (ErrorInfo, [C.c_void_p, _P(JpegCoefficients), C.c_uint, C.c_uint, C.c_int, _P(RawImage), _P(EncodeCfg),
+                                                          _P(GainmapMetadata), _P(RawImage)]),
     "uhdr_hip_encode_api3_scans": (ErrorInfo, [C.c_void_p, _P(JpegHeader), C.c_void_p, C.c_size_t, C.c_int, _P(RawImage), _P(EncodeCfg), C.c_void_p,
                                                _P(GainmapMetadata), _P(RawImage), C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "uhdr_hip_encode_api3_scans_dev": (ErrorInfo, [C.c_void_p, _P(JpegHeader), C.c_void_p, C.c_size_t, C.c_int, _P(RawImage), _P(EncodeCfg), C.c_void_p,

@@ -119,6 +119,11 @@ constexpr bool kResizeDefaultStaged = true;
 // up to 28 us quicker through UHDR_HIP_API3_ROUTE=staged -- profiles/README.md.)
 constexpr bool kApi3DefaultStaged420 = false;
 constexpr bool kApi3DefaultStaged422 = false;
+// ... and of a 4:4:4 SDR intent, by the same rule in the same tool's 4:4:4 rows: the _dev call through the coefficient kernel is below the
+// staged chain of public entry points in all six rows that have a call (66 to 135 us against at most 22 us of the two spreads added).  Against
+// the planes route inside the same call it meets the bar in the two 4K two-pass rows (21 and 36 us) and is within the spreads in the other
+// four, never above it by the medians -- profiles/README.md.
+constexpr bool kApi3DefaultStaged444 = false;
 size_t input_bytes(const uhdr_raw_image_t* im) {
   size_t n = 0;
   const ImageView v = view_of(im);
@@ -247,13 +252,13 @@ bool resize_route_staged() {
 }  // namespace
 
 // uhdr_hip_encode_api3_scans / _dev: UHDR_HIP_API3_ROUTE=fused|staged forces the coefficient kernel (generate_coef.hip) or the planes route
-// (three IDCT launches + generate_gainmap) for a 4:2:0 / 4:2:2 SDR intent; otherwise the measured default of that sampling (profiles/README.md)
+// (three IDCT launches + generate_gainmap) for a 4:2:0 / 4:2:2 / 4:4:4 SDR intent; otherwise the measured default of that sampling (profiles/README.md)
 bool uhdr_api::api3_route_staged(int sampling) {
   if (const char* e = getenv("UHDR_HIP_API3_ROUTE")) {
     if (!strcmp(e, "staged")) return true;
     if (!strcmp(e, "fused")) return false;
   }
-  return sampling == 420 ? kApi3DefaultStaged420 : kApi3DefaultStaged422;
+  return sampling == 420 ? kApi3DefaultStaged420 : (sampling == 422 ? kApi3DefaultStaged422 : kApi3DefaultStaged444);
 }
 
 uhdr_error_info_t uhdr_hip_apply_gainmap_any_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
@@ -835,13 +840,12 @@ static uhdr_error_info_t generate_gainmap_coef_impl(uhdr_hip_ctx_t* c, const uhd
   UHDR_TRY(prepare_gen_coef(c, sdr, w, h, sampling, sdr_cg, hdr, cfg, &p, &cs, &use_base_cg, &hdr_white_nits));
   fill_gainmap_desc(hdr, p, gm);
   if (gm->stride[0] < gm->w) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap stride (%u) cannot be less than its width (%u)", gm->stride[0], gm->w);
-  const int vsamp = sampling == 420 ? 2 : 1;
   if (cfg->preset == UHDR_USAGE_REALTIME) {  // one pass: jpegr.cpp:724-737
     UHDR_TRY(fill_onepass_range(c, cfg, hdr_white_nits, use_base_cg, &p, md));
     p.out = (uint8_t*)gm->planes[0];
     p.out_stride = gm->stride[0];
     ProfScope ps(c, "generate_gainmap");
-    HIP_TRY(launch_generate_gainmap_coef(p, cs, vsamp, false, c->stream));
+    HIP_TRY(launch_generate_gainmap_coef(p, cs, sampling, false, c->stream));
     return ok_status();
   }
   const size_t nfl = (size_t)p.map_w * p.map_h * (p.multichannel ? 3 : 1);
@@ -851,9 +855,9 @@ static uhdr_error_info_t generate_gainmap_coef_impl(uhdr_hip_ctx_t* c, const uhd
   p.minmax = (float*)c->minmax.p;
   {
     ProfScope ps(c, "generate_gainmap");
-    HIP_TRY(launch_generate_gainmap_coef(p, cs, vsamp, true, c->stream));
+    HIP_TRY(launch_generate_gainmap_coef(p, cs, sampling, true, c->stream));
   }
-  UHDR_TRY(two_pass_tail(c, p, gen_coef_partials_count(p), cfg, gm));
+  UHDR_TRY(two_pass_tail(c, p, gen_coef_partials_count(p, sampling), cfg, gm));
   HIP_TRY(hipStreamSynchronize(c->stream));  // the only host synchronisation: the metadata needs the final range
   float mm[6];
   memcpy(mm, c->h_mm, sizeof mm);
@@ -872,6 +876,14 @@ uhdr_error_info_t uhdr_hip_generate_gainmap_coef422_dev(uhdr_hip_ctx_t* c, const
                                                         uhdr_color_gamut_t sdr_cg, const uhdr_raw_image_t* hdr_intent, const uhdr_hip_encode_cfg_t* cfg,
                                                         uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_img) {
   return generate_gainmap_coef_impl(c, sdr, w, h, 422, sdr_cg, hdr_intent, cfg, md, gainmap_img);
+}
+
+// ... and of a 4:4:4 SDR intent (1x1 / 1x1 / 1x1: what editors and render pipelines write at high quality); the kernel's tile is an
+// MCU row of eight pixel rows.
+uhdr_error_info_t uhdr_hip_generate_gainmap_coef444_dev(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_coefficients_t* sdr, unsigned int w, unsigned int h,
+                                                        uhdr_color_gamut_t sdr_cg, const uhdr_raw_image_t* hdr_intent, const uhdr_hip_encode_cfg_t* cfg,
+                                                        uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_img) {
+  return generate_gainmap_coef_impl(c, sdr, w, h, 444, sdr_cg, hdr_intent, cfg, md, gainmap_img);
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -290,11 +290,11 @@ void fill_gainmap_desc(const uhdr_raw_image_t* hdr, const GenParams& p, uhdr_raw
 uhdr_error_info_t generate_gainmap_finalize_md(const uhdr_hip_encode_cfg_t* cfg, uhdr_color_transfer_t hdr_ct, int use_base_cg, const float mm[6], uhdr_gainmap_metadata_t* md);
 void note_table_stats(uhdr_hip_ctx* c, const uhdr_hip_encode_cfg_t* cfg);
 uhdr_error_info_t two_pass_tail(uhdr_hip_ctx* c, const GenParams& p, int n_partials, const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* gm);
-// generateGainMap from coefficients (uhdr_hip_generate_gainmap_coef_dev / _coef422_dev and the API-3 chain): every check of the operator, then the
-// parameter block and the coefficient descriptor.  Launches nothing; sampling: 420 or 422.
+// generateGainMap from coefficients (uhdr_hip_generate_gainmap_coef_dev / _coef422_dev / _coef444_dev and the API-3 chain): every check of the operator, then the
+// parameter block and the coefficient descriptor.  Launches nothing; sampling: 420, 422 or 444.
 uhdr_error_info_t prepare_gen_coef(uhdr_hip_ctx* c, const uhdr_hip_jpeg_coefficients_t* sdr, unsigned int w, unsigned int h, int sampling, uhdr_color_gamut_t sdr_cg,
                                    const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg, GenParams* p, CoefSrc* cs, int* use_base_cg, float* hdr_white_nits);
-bool api3_route_staged(int sampling);  // UHDR_HIP_API3_ROUTE, else the measured default; sampling: 420 or 422
+bool api3_route_staged(int sampling);  // UHDR_HIP_API3_ROUTE, else the measured default; sampling: 420, 422 or 444
 uhdr_error_info_t fill_tone_map_params(uhdr_hip_ctx* c, const uhdr_raw_image_t* hdr, ToneMapParams* pp);
 // ---- api_stripes.cpp: THE collective of the hot path ----
 uhdr_error_info_t comm_all_reduce_min(uhdr_hip_ctx* c, float* buf, size_t n);

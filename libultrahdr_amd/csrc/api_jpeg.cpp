@@ -1622,8 +1622,8 @@ uhdr_error_info_t uhdr_hip_decode_api1_scans_any_dev(uhdr_hip_ctx_t* c, const uh
 // JpegR::encodeJPEGR API-3 (jpegr.cpp:327-385) behind its container: a raw HDR intent and a COMPRESSED SDR intent -> the gain map's scan
 // -------------------------------------------------------------------------------------------------
 // The SDR intent's entropy-coded bytes are decoded into the context's coefficient arrays; generateGainMap reads them as they are
-// (generate_coef.hip: 4:2:0 and 4:2:2) or through three IDCT launches (4:4:4, the staged route, and wherever the coefficient operator answers
-// UNSUPPORTED_FEATURE for geometry); the map's coefficients come from map_blocks_kernel behind the range kernel (two pass) or from the byte map
+// (generate_coef.hip: 4:2:0, 4:2:2 and 4:4:4) or through three IDCT launches (the staged route -- UHDR_HIP_API3_ROUTE or the measured default of
+// the sampling, api3_route_staged -- and wherever the coefficient operator answers UNSUPPORTED_FEATURE for geometry); the map's coefficients come from map_blocks_kernel behind the range kernel (two pass) or from the byte map
 // in context scratch through the FDCT operators (one pass); the marker-less Huffman coder writes the scan.  sdr_is_601 is forced to 1
 // (jpegr.cpp:377).  Only the map's scan comes back: the base image of the file is the caller's JPEG, byte for byte.
 static uhdr_error_info_t encode_api3_scans_impl(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* sdr_jpeg, const uint8_t* sdr_data, size_t sdr_bytes,
@@ -1687,7 +1687,7 @@ static uhdr_error_info_t encode_api3_scans_impl(uhdr_hip_ctx_t* c, const uhdr_hi
   CoefSrc cs;
   int use_base_cg = 1;
   float hdr_white_nits = 0;
-  bool fused = !is444 && !api3_route_staged(sampling);
+  bool fused = !api3_route_staged(sampling);
   if (fused) {
     uhdr_hip_jpeg_coefficients_t jc;
     memset(&jc, 0, sizeof jc);
@@ -1725,7 +1725,7 @@ static uhdr_error_info_t encode_api3_scans_impl(uhdr_hip_ctx_t* c, const uhdr_hi
   if (p.map_w != mw || p.map_h != mh) return err_status(UHDR_CODEC_ERROR, "internal: map dimensions %ux%u / %ux%u", p.map_w, p.map_h, mw, mh);
   auto pass = [&](bool two_pass) -> hipError_t {
     ProfScope ps(c, "generate_gainmap");
-    return fused ? launch_generate_gainmap_coef(p, cs, vsamp, two_pass, c->stream) : launch_generate_gainmap(p, two_pass, c->stream);
+    return fused ? launch_generate_gainmap_coef(p, cs, sampling, two_pass, c->stream) : launch_generate_gainmap(p, two_pass, c->stream);
   };
   // 3. the map's coefficients
   const size_t nm = (size_t)(mw / 8) * (mh / 8);
@@ -1764,7 +1764,7 @@ static uhdr_error_info_t encode_api3_scans_impl(uhdr_hip_ctx_t* c, const uhdr_hi
     memset(&t, 0, sizeof t);
     t.do_reduce = t.do_finalize = t.do_table = 1;
     t.partials = p.minmax + 6;
-    t.n_partials = fused ? gen_coef_partials_count(p) : gen_partials_count(p);
+    t.n_partials = fused ? gen_coef_partials_count(p, sampling) : gen_partials_count(p);
     t.mm6 = p.minmax;
     fill_finalize(&t, &cfg);
     t.out_mm = final_mm;

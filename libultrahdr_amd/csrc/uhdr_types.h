@@ -255,10 +255,11 @@ hipError_t launch_apply_gainmap(const ApplyParams& p, hipStream_t s);
 hipError_t launch_apply_gainmap_coef(const ApplyParams& p, hipStream_t s);
 int apply_quad_mode(const ApplyParams& p);  // >= 0: the quad kernel (and batch mode) applies
 hipError_t launch_generate_gainmap(const GenParams& p, bool two_pass, hipStream_t s);
-// generate_coef.hip: pass 1 / the one-pass generation with the SDR intent as the coefficient blocks of a 4:2:0 (vsamp 2) or 4:2:2 (vsamp 1)
-// JPEG; p.sdr carries the decoded image's geometry only.  gen_coef_partials_count: the workgroups (= partials) of its two-pass launch
-hipError_t launch_generate_gainmap_coef(const GenParams& p, const CoefSrc& cs, int vsamp, bool two_pass, hipStream_t s);
-int gen_coef_partials_count(const GenParams& p);
+// generate_coef.hip: pass 1 / the one-pass generation with the SDR intent as the coefficient blocks of a 4:2:0, 4:2:2 or 4:4:4 JPEG
+// (sampling 420 / 422 / 444); p.sdr carries the decoded image's geometry only.  gen_coef_partials_count: the workgroups (= partials) of
+// its two-pass launch
+hipError_t launch_generate_gainmap_coef(const GenParams& p, const CoefSrc& cs, int sampling, bool two_pass, hipStream_t s);
+int gen_coef_partials_count(const GenParams& p, int sampling);
 hipError_t launch_affine_map(const AffineParams& p, hipStream_t s);
 hipError_t launch_minmax_table(const MinmaxTableParams& p, hipStream_t s);
 // encode_api1_fused.hip

@@ -183,15 +183,16 @@ class UltraHdr:
 
     def generateGainMapFromCoefficients(self, coefs, qtables, w: int, h: int, sdr_cg: int, hdr_intent: Image, sampling: str = "420",
                                         sdr_is_601=False, use_luminance=True, gm: Image = None):
-        """generateGainMap on a 4:2:0 (sampling "420") or 4:2:2 ("422": uhdr_hip_generate_gainmap_coef422_dev) SDR intent still in
-        coefficient form -- the compressed intent of an API-3 encode (jpegr.cpp:327-385) after its Huffman decode: coefs = three
+        """generateGainMap on a 4:2:0 (sampling "420"), 4:2:2 ("422": uhdr_hip_generate_gainmap_coef422_dev) or 4:4:4 ("444":
+        uhdr_hip_generate_gainmap_coef444_dev) SDR intent still in coefficient form -- the compressed intent of an API-3 encode (jpegr.cpp:327-385) after its Huffman decode: coefs = three
         int16 [blocks_h, blocks_w, 64] CUDA tensors (Y, Cb, Cr), qtables = their three quantization tables; the dequantize + IDCT
         stage runs inside the kernel (uhdr_hip_generate_gainmap_coef_dev).  gm: the device image to fill (a fresh 64-aligned one
         when None).  Returns (metadata, gainmap Image) == idct_dequant x 3 + generateGainMap, bit for bit."""
         assert all(c.is_cuda for c in coefs) and _is_dev(hdr_intent)
-        if sampling not in ("420", "422"):
-            raise ValueError(f"sampling is '420' or '422', received {sampling!r}")
-        fn = self.lib.uhdr_hip_generate_gainmap_coef_dev if sampling == "420" else self.lib.uhdr_hip_generate_gainmap_coef422_dev
+        fns = {"420": "uhdr_hip_generate_gainmap_coef_dev", "422": "uhdr_hip_generate_gainmap_coef422_dev", "444": "uhdr_hip_generate_gainmap_coef444_dev"}
+        if sampling not in fns:
+            raise ValueError(f"sampling is '420', '422' or '444', received {sampling!r}")
+        fn = getattr(self.lib, fns[sampling])
         jc = A.JpegCoefficients()
         for i in range(3):
             jc.coef[i] = coefs[i].data_ptr()
@@ -213,7 +214,8 @@ class UltraHdr:
         hdr_intent a device image; returns (bytes of the map scan, metadata, gain-map description).  Host data
         (uhdr_hip_encode_api3_scans): sdr_data is bytes / a uint8 array, out_map the capacity in bytes; returns (map scan, metadata,
         gain-map description).  A UhdrError for a capacity that is too small carries the needed size in .needed.
-        UHDR_HIP_API3_ROUTE=fused|staged forces the coefficient kernel or the planes route for 4:2:0 / 4:2:2 files."""
+        UHDR_HIP_API3_ROUTE=fused|staged forces the coefficient kernel or the planes route for 4:2:0, 4:2:2 and 4:4:4 files (read on
+        every call; unset, the measured default of the file's sampling)."""
         qm = self._qt_pair(qt_map)
         md, desc = A.GainmapMetadata(), A.RawImage()
         cfg = self.encode_cfg(True, use_luminance)

@@ -1,13 +1,13 @@
 """The API-3 encode from JPEG coefficients against the staged route, device resident, at 3840 x 2176 and 1920 x 1080 with a P010 HLG
 BT.2100 intent and a BT.709 SDR intent in coefficient / compressed form:
 
-    4:2:0 and 4:2:2 SDR intents   x   three channels at S = 1, one channel at S = 4   x   both presets
+    4:2:0, 4:2:2 and 4:4:4 SDR intents   x   three channels at S = 1, one channel at S = 4   x   both presets
 
     python tools/api3_time.py [--iters 20] [--rounds 5] [--json profiles/api3_time.json]
 
 Per row, on the same device-resident data, into preallocated device buffers:
   (a) operators  inside the launches (the library's own event pair around each launch, uhdr_hip_profile_*):
-                 uhdr_hip_generate_gainmap_coef_dev / _coef422_dev  against  3 x uhdr_hip_idct_dequant_dev + uhdr_hip_generate_gainmap_dev.
+                 uhdr_hip_generate_gainmap_coef_dev / _coef422_dev / _coef444_dev  against  3 x uhdr_hip_idct_dequant_dev + uhdr_hip_generate_gainmap_dev.
                  One pass: that is the first launch alone on either side.  Two pass: both sides carry the same range kernel and pass 2
                  behind their first launch, so the difference is the first launches'.
   (b) calls      a host clock around calls that end synchronised: uhdr_hip_encode_api3_scans_dev with UHDR_HIP_API3_ROUTE=fused  against
@@ -36,7 +36,8 @@ from api0_p010_time import kernel_ms, wall_ms  # noqa: E402  (the same clocks)
 from api0_scaled_time import verdict  # noqa: E402  (medians, spreads, the bar)
 
 SIZES = [(3840, 2176), (1920, 1080)]
-SAMPLINGS = {"420": [(2, 2), (1, 1), (1, 1)], "422": [(2, 1), (1, 1), (1, 1)]}
+SAMPLINGS = {"420": [(2, 2), (1, 1), (1, 1)], "422": [(2, 1), (1, 1), (1, 1)], "444": [(1, 1), (1, 1), (1, 1)]}
+COEF_ENTRY = {"420": "uhdr_hip_generate_gainmap_coef_dev", "422": "uhdr_hip_generate_gainmap_coef422_dev", "444": "uhdr_hip_generate_gainmap_coef444_dev"}
 
 
 def grids(w, h, sampling):
@@ -72,12 +73,12 @@ def main():
     ctx = Context(0)  # raises without a GPU: there is nothing to time on a CPU
     lib, check, ordered = ctx.lib, A.check, ctx.ordered
     dev = "cuda:0"
-    fmts = {"420": A.UHDR_IMG_FMT_12bppYCbCr420, "422": A.UHDR_IMG_FMT_16bppYCbCr422}
+    fmts = {"420": A.UHDR_IMG_FMT_12bppYCbCr420, "422": A.UHDR_IMG_FMT_16bppYCbCr422, "444": A.UHDR_IMG_FMT_24bppYCbCr444}
     rows = []
     for (W, H) in SIZES:
         wp, hp = (W + 15) // 16 * 16, (H + 15) // 16 * 16
         dh = synth.make_hdr_p010(W, H, ct=A.UHDR_CT_HLG, cg=A.UHDR_CG_BT_2100).to(dev)
-        for sampling in ("420", "422"):
+        for sampling in SAMPLINGS:
             u0 = UltraHdr(ctx=ctx)
             qts = [u0.quant_table(92, False), u0.quant_table(92, True), u0.quant_table(92, True)]
             # the SDR intent: a synthetic image on the padded grid -> its coefficients on libjpeg's grids for W x H -> its scan
@@ -109,7 +110,7 @@ def main():
                         jc.blocks_h[i], jc.blocks_w[i] = int(dco[i].shape[0]), int(dco[i].shape[1])
                         for k in range(64):
                             jc.qtable[i][k] = int(qts[i][k])
-                    fn_coef = lib.uhdr_hip_generate_gainmap_coef_dev if sampling == "420" else lib.uhdr_hip_generate_gainmap_coef422_dev
+                    fn_coef = getattr(lib, COEF_ENTRY[sampling])
 
                     def op_fused():
                         with ordered():
@@ -184,7 +185,7 @@ def main():
                     print(json.dumps(row), flush=True)
     ctx.close()
     defaults = {}
-    for sampling in ("420", "422"):
+    for sampling in SAMPLINGS:
         have = [r["meets_bar"] for r in rows if r["sampling"] == sampling and r["meets_bar"] is not None]
         defaults[sampling] = "fused" if have and all(have) else "staged"
     print(json.dumps(dict(default_route=defaults)), flush=True)

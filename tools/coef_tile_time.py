@@ -5,8 +5,8 @@ kernel trace:
 
 At 3840 x 2160, device resident, `iters` launches each behind two warm-up launches:
   applyGainMapFromCoefficients, linear F16 output, a one-channel map at scale factor 4, for 4:2:0, 4:2:2 and 4:4:4 bases;
-  generateGainMapFromCoefficients from a P010 HLG intent, a one-channel map at scale factor 4, for 4:2:0 and 4:2:2 SDR intents and
-  both presets (best quality: two passes; real time: one).
+  generateGainMapFromCoefficients from a P010 HLG intent, a one-channel map at scale factor 4, for 4:2:0, 4:2:2 and 4:4:4 SDR intents
+  and both presets (best quality: two passes; real time: one).
 The coefficients are small random values with flat tables (every dequantised value below 2^13: the 24-bit multiply path, as for any
 image that came out of an 8-bit forward DCT).  To trace two builds in turn, exchange libultrahdr_amd/lib/libuhdr_hip.so between
 runs, each run its own process; tools/read_prof.py summarises the databases."""
@@ -64,7 +64,7 @@ def main():
     hdr = synth.make_hdr_p010(W, H, ct=A.UHDR_CT_HLG, cg=A.UHDR_CG_BT_2100).to(dev)
     for preset, name in ((A.UHDR_USAGE_BEST_QUALITY, "best"), (A.UHDR_USAGE_REALTIME, "realtime")):
         e = UltraHdr(ctx=ctx, preset=preset)
-        for s in ("420", "422"):
+        for s in ("420", "422", "444"):
             out = None
             for _ in range(args.iters + 2):
                 _, out = e.generateGainMapFromCoefficients(coefs[s], qts, W, H, A.UHDR_CG_BT_709, hdr, s, gm=out)
