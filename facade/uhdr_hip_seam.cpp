@@ -196,6 +196,13 @@ bool apply_gainmap(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* gainmap_img,
     const uhdr_gainmap_metadata_t md = *gainmap_metadata;  // slice off the version string
     // UHDR_HIP_SEAM_RESIZED_MAP: a gain map of another aspect ratio than the base image (jpegr.cpp:1651-1671) stays on the device
     // (uhdr_hip_apply_gainmap_any); without it the library refuses such a map and the reference's resize + loop run on the host
+    // UHDR_HIP_SEAM_GAMMA_TABLE: a gain-map gamma other than 1 is evaluated through the library's threshold table of the GainLUT
+    // index (gainmapmath.h:483-489, uhdr_hip_apply_gainmap_ex) -- the reference's bits, where the calls below use the device's pow
+    if (getenv("UHDR_HIP_SEAM_GAMMA_TABLE")) {
+      const unsigned int flags = UHDR_HIP_APPLY_GAMMA_TABLE | (getenv("UHDR_HIP_SEAM_RESIZED_MAP") ? UHDR_HIP_APPLY_RESIZED_MAP : 0u);
+      *st = uhdr_hip_apply_gainmap_ex(cur(), sdr_intent, gainmap_img, &md, output_ct, output_format, max_display_boost, dest, flags);
+      return handled(*st, "apply_gainmap");
+    }
     *st = getenv("UHDR_HIP_SEAM_RESIZED_MAP")
               ? uhdr_hip_apply_gainmap_any(cur(), sdr_intent, gainmap_img, &md, output_ct, output_format, max_display_boost, dest)
               : uhdr_hip_apply_gainmap(cur(), sdr_intent, gainmap_img, &md, output_ct, output_format, max_display_boost, dest);

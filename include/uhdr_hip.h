@@ -223,6 +223,33 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_any_dev(uhdr_hip_ctx_t* ctx, const uhdr
                                                  uhdr_img_fmt_t output_format, float max_display_boost,
                                                  uhdr_raw_image_t* dest, unsigned int y0,
                                                  unsigned int full_height);
+/* applyGainMap with flags.  flags 0 is uhdr_hip_apply_gainmap / _dev; UHDR_HIP_APPLY_RESIZED_MAP is uhdr_hip_apply_gainmap_any / _any_dev.
+ * UHDR_HIP_APPLY_GAMMA_TABLE: a gain-map gamma other than 1 at a map scale other than 1 without a pow per sample.
+ * GainLUT::getGainFactor (lib/include/ultrahdr/gainmapmath.h:483-489) raises the sampled gain to 1 / gamma, stores it to a float and
+ * takes int(gain * 1023 + 0.5) as the table index; that index is a step function of the gain, so per distinct gamma the host builds
+ * and checks -- with its own libm, the one the reference calls -- the 1023 smallest floats at which it steps, and the kernels look the
+ * index up there (an estimate from the hardware's log2 / exp2, settled and proven on four neighbouring thresholds, else a ten-step
+ * search).  Results are the reference's bit for bit, where the older entry points evaluate the device's pow and may differ by one
+ * half-float code on a few samples.  With one gamma for the three channels, even geometry and an even scale <= 8 the 2x2-quad kernel
+ * runs; every other case (per-channel gammas, odd or large scales, a non-integer scale, odd sizes) takes the one-pixel-per-thread
+ * kernel with the same thresholds.  A gamma that yields no verified table (0, negative, NaN, infinite, a non-monotone result) keeps the
+ * pow per sample: the call never guesses.  The tables are cached with the per-metadata tables of the context.
+ * Unknown flag bits: UHDR_CODEC_INVALID_PARAM.  Other parameters as uhdr_hip_apply_gainmap / _dev. */
+#define UHDR_HIP_APPLY_RESIZED_MAP 0x1u /* what uhdr_hip_apply_gainmap_any adds */
+#define UHDR_HIP_APPLY_GAMMA_TABLE 0x2u /* gamma != 1 at scale != 1 through the threshold table (gainmapmath.h:483-489) */
+uhdr_error_info_t uhdr_hip_apply_gainmap_ex(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr_intent,
+                                            const uhdr_raw_image_t* gainmap_img,
+                                            const uhdr_gainmap_metadata_t* gainmap_metadata,
+                                            uhdr_color_transfer_t output_ct,
+                                            uhdr_img_fmt_t output_format, float max_display_boost,
+                                            uhdr_raw_image_t* dest, unsigned int flags);
+uhdr_error_info_t uhdr_hip_apply_gainmap_ex_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr_intent,
+                                                const uhdr_raw_image_t* gainmap_img,
+                                                const uhdr_gainmap_metadata_t* gainmap_metadata,
+                                                uhdr_color_transfer_t output_ct,
+                                                uhdr_img_fmt_t output_format, float max_display_boost,
+                                                uhdr_raw_image_t* dest, unsigned int y0,
+                                                unsigned int full_height, unsigned int flags);
 /* resize_image, lib/src/editorhelper.cpp:88-146 (declared lib/include/ultrahdr/editorhelper.h): the interpolating resize
  * applyGainMap runs on a gain map of another aspect ratio, for UHDR_IMG_FMT_8bppYCbCr400, UHDR_IMG_FMT_24bppRGB888 and
  * UHDR_IMG_FMT_32bppRGBA8888 (alpha 255), with the reference's bytes.  dst: caller provides planes[0], stride[0], w, h and
@@ -368,6 +395,9 @@ int uhdr_hip_exact_math_eval(int fn, const float* in, float* out, size_t n);
  *            (log2 gains, as uhdr_hip_generate_gainmap_finalize returns it), channel arg0 of arg1 channels, against the
  *            per-sample evaluation over the table's whole domain and 2^20 bit patterns beyond either end
  *                                                                                      out = {mismatches, ratios swept, table entries, 1 if the range got no table}
+ *   which 5: the GainLUT index of gain-map gamma mm[0] (gainmapmath.h:483-489, UHDR_HIP_APPLY_GAMMA_TABLE): the kernels' estimate-and-settle
+ *            lookup against the binary search over the same host-built thresholds, every float from 0 to eight ulps past the last threshold
+ *                                                                                      out = {mismatches, floats swept, lanes whose estimate needed the search, 1 if the gamma got no table}
  * The reference has no counterpart: these pin the arithmetic of jpegr.cpp:753-1013, 1945-1983 and gainmapmath.cpp:127-148 as evaluated here. */
 uhdr_error_info_t uhdr_hip_selftest(uhdr_hip_ctx_t* ctx, int which, unsigned int arg0, unsigned int arg1, unsigned int seed, const float mm[6],
                                     unsigned long long out[8]);
@@ -383,6 +413,13 @@ uhdr_error_info_t uhdr_hip_selftest(uhdr_hip_ctx_t* ctx, int which, unsigned int
  * info (may be NULL) receives {verified exact, entries, shift, first bucket}.  Returns 0; 1 when the table could not be
  * verified exact for these parameters (the kernels then keep the arithmetic evaluation); -1 for a bad argument. */
 int uhdr_hip_step_table_eval(int which, float a, float b, const float* in, uint32_t* out, size_t n, uint32_t info[4]);
+/* Host utility (no GPU needed): GainLUT::getGainFactor's table index (gainmapmath.h:483-489: int(pow(x, 1 / gamma) * 1023 + 0.5) clipped
+ * to 0..1023) of n gain values through the threshold table of UHDR_HIP_APPLY_GAMMA_TABLE, by the device's lookup procedure restated on the
+ * host.  info (may be NULL) receives {verified exact, table steps + 1 (1024), microseconds the table's construction took, 0};
+ * thresholds (may be NULL) receives T[0..1024] (T[i]: the smallest float whose index is >= i; T[0] = 0, T[1024] = +inf); in / out may be
+ * NULL with n = 0.  Returns 0; 1 when this gamma has no verified table (0, negative, NaN, infinite, non-monotone: the kernels then keep
+ * the pow per sample) -- out and thresholds are then untouched. */
+int uhdr_hip_gamma_index_eval(float gamma, const float* in, uint32_t* out, size_t n, uint32_t info[4], float* thresholds);
 /* islow 8x8 FDCT + quantize of one 8-bit plane.  Reads blocks_w*8 x blocks_h*8 samples (the
  * caller pads to the MCU grid exactly as jpegencoderhelper.cpp:246-309 does); writes blocks in
  * raster order, 64 int16 each in natural order = libjpeg's JBLOCK layout, ready for
@@ -556,6 +593,22 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_coef444_dev(uhdr_hip_ctx_t* ctx,
                                                      uhdr_color_transfer_t output_ct,
                                                      uhdr_img_fmt_t output_format, float max_display_boost,
                                                      uhdr_raw_image_t* dest);
+/* uhdr_hip_apply_gainmap_coef_ex_dev: the three operators above behind one entry point -- sampling 420, 422 or 444 says which frame the
+ * coefficients are (anything else: UHDR_CODEC_INVALID_PARAM) -- with the flags of uhdr_hip_apply_gainmap_ex_dev.  With
+ * UHDR_HIP_APPLY_GAMMA_TABLE a gain-map gamma other than 1 (GainLUT::getGainFactor, lib/include/ultrahdr/gainmapmath.h:483-489; one gamma
+ * for the three channels) at an even map scale <= 8 stays on the coefficient kernel, which the three older entry points refuse with
+ * UHDR_CODEC_UNSUPPORTED_FEATURE; result == uhdr_hip_idct_dequant_dev x 3 followed by uhdr_hip_apply_gainmap_ex_dev with the same flag,
+ * bit for bit.  A gain map of another aspect ratio has no coefficient form: UHDR_HIP_APPLY_RESIZED_MAP and unknown flag bits answer
+ * UHDR_CODEC_INVALID_PARAM.  flags 0: the older entry point of that sampling. */
+uhdr_error_info_t uhdr_hip_apply_gainmap_coef_ex_dev(uhdr_hip_ctx_t* ctx,
+                                                     const uhdr_hip_jpeg_coefficients_t* base, int sampling,
+                                                     unsigned int w, unsigned int h,
+                                                     uhdr_color_gamut_t base_cg,
+                                                     const uhdr_raw_image_t* gainmap_img,
+                                                     const uhdr_gainmap_metadata_t* gainmap_metadata,
+                                                     uhdr_color_transfer_t output_ct,
+                                                     uhdr_img_fmt_t output_format, float max_display_boost,
+                                                     uhdr_raw_image_t* dest, unsigned int flags);
 
 /* The mirror on the encode side: generateGainMap (lib/src/jpegr.cpp:530-1050) with the SDR intent still in coefficient form -- the
  * compressed SDR intent of JpegR::encodeJPEGR API-3 (lib/src/jpegr.cpp:327-385) after its Huffman decode.  JpegDecoderHelper's
@@ -998,6 +1051,18 @@ uhdr_error_info_t uhdr_hip_decode_api1_scans_any_dev(uhdr_hip_ctx_t* ctx, const 
                                                      const uint8_t* map_data, size_t map_bytes, uhdr_color_gamut_t map_cg,
                                                      int libjpeg_variant, const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t output_ct,
                                                      uhdr_img_fmt_t output_format, float max_display_boost, uhdr_raw_image_t* dest);
+/* uhdr_hip_decode_api1_scans_ex_dev: uhdr_hip_decode_api1_scans_any_dev whose applyGainMap stage runs with apply_flags
+ * (uhdr_hip_apply_gainmap_coef_ex_dev, and uhdr_hip_apply_gainmap_ex_dev behind three IDCT launches where that answers
+ * UHDR_CODEC_UNSUPPORTED_FEATURE).  With UHDR_HIP_APPLY_GAMMA_TABLE a file whose gain-map gamma is not 1 (GainLUT::getGainFactor,
+ * lib/include/ultrahdr/gainmapmath.h:483-489) keeps the fused route at an even map scale <= 8, and the pixels are the reference's bit for
+ * bit.  UHDR_HIP_APPLY_RESIZED_MAP and unknown flag bits: UHDR_CODEC_INVALID_PARAM (the one-call decode refuses a map of another aspect
+ * ratio, as before). */
+uhdr_error_info_t uhdr_hip_decode_api1_scans_ex_dev(uhdr_hip_ctx_t* ctx, const uhdr_hip_jpeg_header_t* base, const uint8_t* base_data,
+                                                    size_t base_bytes, uhdr_color_gamut_t base_cg, const uhdr_hip_jpeg_header_t* map,
+                                                    const uint8_t* map_data, size_t map_bytes, uhdr_color_gamut_t map_cg,
+                                                    int libjpeg_variant, const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t output_ct,
+                                                    uhdr_img_fmt_t output_format, float max_display_boost, uhdr_raw_image_t* dest,
+                                                    unsigned int apply_flags);
 
 /* JpegR::encodeJPEGR API-3 (lib/src/jpegr.cpp:327-385) behind its container in ONE call: a raw HDR intent and a COMPRESSED SDR intent -- an
  * existing camera or phone JPEG that stays the file's base image, byte for byte -- to the gain map's entropy-coded scan (the transcoding

@@ -117,6 +117,16 @@ class UltraHdr {
     return uhdr_hip_apply_gainmap_any(mCtx, sdr_intent, gainmap_img, gainmap_metadata, output_ct, output_format, max_display_boost, dest);
   }
 
+  // applyGainMap with flags (uhdr_hip_apply_gainmap_ex): UHDR_HIP_APPLY_RESIZED_MAP is applyGainMapAny, UHDR_HIP_APPLY_GAMMA_TABLE
+  // evaluates a gain-map gamma other than 1 (GainLUT::getGainFactor, gainmapmath.h:483-489) through host-built thresholds
+  // instead of a pow per sample -- the reference's bits; 0 is applyGainMap.
+  uhdr_error_info_t applyGainMapEx(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* gainmap_img,
+                                   uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_color_transfer_t output_ct,
+                                   uhdr_img_fmt_t output_format, float max_display_boost, uhdr_raw_image_t* dest, unsigned int flags) {
+    if (!mCtx) return mCreateStatus;
+    return uhdr_hip_apply_gainmap_ex(mCtx, sdr_intent, gainmap_img, gainmap_metadata, output_ct, output_format, max_display_boost, dest, flags);
+  }
+
   // resize_image (editorhelper.cpp:88-146) for Y400 / RGB888 / RGBA8888 into a caller-provided image of the wanted size
   uhdr_error_info_t resizeImage(uhdr_raw_image_t* src, uhdr_raw_image_t* dst) {
     if (!mCtx) return mCreateStatus;
@@ -145,6 +155,29 @@ class UltraHdr {
     if (!mCtx) return mCreateStatus;
     return uhdr_hip_apply_gainmap_coef444_dev(mCtx, base, w, h, base_cg, gainmap_img, gainmap_metadata, output_ct, output_format,
                                               max_display_boost, dest);
+  }
+
+  // ... of any sampling (420, 422 or 444) with applyGainMapEx's flags (uhdr_hip_apply_gainmap_coef_ex_dev; gainmapmath.h:483-489):
+  // with UHDR_HIP_APPLY_GAMMA_TABLE a gamma other than 1 at an even map scale <= 8 stays on the coefficient kernel.
+  uhdr_error_info_t applyGainMapFromCoefficientsEx(const uhdr_hip_jpeg_coefficients_t* base, int sampling, unsigned int w, unsigned int h,
+                                                   uhdr_color_gamut_t base_cg, uhdr_raw_image_t* gainmap_img,
+                                                   uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_color_transfer_t output_ct,
+                                                   uhdr_img_fmt_t output_format, float max_display_boost, uhdr_raw_image_t* dest,
+                                                   unsigned int flags) {
+    if (!mCtx) return mCreateStatus;
+    return uhdr_hip_apply_gainmap_coef_ex_dev(mCtx, base, sampling, w, h, base_cg, gainmap_img, gainmap_metadata, output_ct, output_format,
+                                              max_display_boost, dest, flags);
+  }
+
+  // decodeApi1ScansAny below with applyGainMapEx's flags for its applyGainMap stage (uhdr_hip_decode_api1_scans_ex_dev; gainmapmath.h:483-489)
+  uhdr_error_info_t decodeApi1ScansEx(const uhdr_hip_jpeg_header_t* base, const uint8_t* base_data, size_t base_bytes,
+                                      uhdr_color_gamut_t base_cg, const uhdr_hip_jpeg_header_t* map, const uint8_t* map_data,
+                                      size_t map_bytes, uhdr_color_gamut_t map_cg, uhdr_gainmap_metadata_t* gainmap_metadata,
+                                      uhdr_color_transfer_t output_ct, uhdr_img_fmt_t output_format, float max_display_boost,
+                                      uhdr_raw_image_t* dest, unsigned int apply_flags, int libjpeg_variant = 0) {
+    if (!mCtx) return mCreateStatus;
+    return uhdr_hip_decode_api1_scans_ex_dev(mCtx, base, base_data, base_bytes, base_cg, map, map_data, map_bytes, map_cg, libjpeg_variant,
+                                             gainmap_metadata, output_ct, output_format, max_display_boost, dest, apply_flags);
   }
 
   // JpegR::decodeJPEGR behind its container parsing on device data in one call (uhdr_hip_decode_api1_scans_any_dev): two parsed

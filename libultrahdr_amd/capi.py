@@ -40,6 +40,8 @@ UHDR_CODEC_UNSUPPORTED_FEATURE = 6
 
 FLT_MIN = 1.1754943508222875e-38
 FLT_MAX = 3.4028234663852886e38
+# applyGainMap flags (uhdr_hip_apply_gainmap_ex and its siblings)
+UHDR_HIP_APPLY_RESIZED_MAP, UHDR_HIP_APPLY_GAMMA_TABLE = 0x1, 0x2
 
 
 class ErrorInfo(C.Structure):  # uhdr_error_info_t
@@ -196,6 +198,9 @@ _SIGS = {
     "uhdr_hip_apply_gainmap_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(GainmapMetadata), C.c_int, C.c_int, C.c_float, _P(RawImage), C.c_uint, C.c_uint]),
     "uhdr_hip_apply_gainmap_any": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(GainmapMetadata), C.c_int, C.c_int, C.c_float, _P(RawImage)]),
     "uhdr_hip_apply_gainmap_any_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(GainmapMetadata), C.c_int, C.c_int, C.c_float, _P(RawImage), C.c_uint, C.c_uint]),
+    "uhdr_hip_apply_gainmap_ex": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(GainmapMetadata), C.c_int, C.c_int, C.c_float, _P(RawImage), C.c_uint]),
+    "uhdr_hip_apply_gainmap_ex_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(GainmapMetadata), C.c_int, C.c_int, C.c_float, _P(RawImage), C.c_uint, C.c_uint,
+                                                  C.c_uint]),
     "uhdr_hip_resize_image": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage)]),
     "uhdr_hip_resize_image_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), C.c_uint, C.c_uint]),
     "uhdr_hip_apply_gainmap_batch_dev": (ErrorInfo, [C.c_void_p, C.c_uint, _P(RawImage), _P(RawImage), _P(GainmapMetadata), C.c_int, C.c_int, C.c_float, _P(RawImage)]),
@@ -243,6 +248,8 @@ _SIGS = {
                                                    C.c_int, _P(GainmapMetadata), C.c_int, C.c_int, C.c_float, _P(RawImage)]),
     "uhdr_hip_decode_api1_scans_any_dev": (ErrorInfo, [C.c_void_p, _P(JpegHeader), C.c_void_p, C.c_size_t, C.c_int, _P(JpegHeader), C.c_void_p, C.c_size_t, C.c_int,
                                                        C.c_int, _P(GainmapMetadata), C.c_int, C.c_int, C.c_float, _P(RawImage)]),
+    "uhdr_hip_decode_api1_scans_ex_dev": (ErrorInfo, [C.c_void_p, _P(JpegHeader), C.c_void_p, C.c_size_t, C.c_int, _P(JpegHeader), C.c_void_p, C.c_size_t, C.c_int,
+                                                      C.c_int, _P(GainmapMetadata), C.c_int, C.c_int, C.c_float, _P(RawImage), C.c_uint]),
     "uhdr_hip_comm_all_reduce_min_dev": (ErrorInfo, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "uhdr_hip_selftest": (ErrorInfo, [C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, _P(C.c_float), _P(C.c_ulonglong)]),
     "uhdr_hip_fdct_quant": (ErrorInfo, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, _P(C.c_uint16), C.c_void_p]),
@@ -267,6 +274,8 @@ _SIGS = {
                                                        C.c_int, C.c_int, C.c_float, _P(RawImage)]),
     "uhdr_hip_apply_gainmap_coef444_dev": (ErrorInfo, [C.c_void_p, _P(JpegCoefficients), C.c_uint, C.c_uint, C.c_int, _P(RawImage), _P(GainmapMetadata),
                                                        C.c_int, C.c_int, C.c_float, _P(RawImage)]),
+    "uhdr_hip_apply_gainmap_coef_ex_dev": (ErrorInfo, [C.c_void_p, _P(JpegCoefficients), C.c_int, C.c_uint, C.c_uint, C.c_int, _P(RawImage), _P(GainmapMetadata),
+                                                       C.c_int, C.c_int, C.c_float, _P(RawImage), C.c_uint]),
     "uhdr_hip_generate_gainmap_coef_dev": (ErrorInfo, [C.c_void_p, _P(JpegCoefficients), C.c_uint, C.c_uint, C.c_int, _P(RawImage), _P(EncodeCfg),
                                                        _P(GainmapMetadata), _P(RawImage)]),
     "uhdr_hip_generate_gainmap_coef422_dev": (ErrorInfo, [C.c_void_p, _P(JpegCoefficients), C.c_uint, C.c_uint, C.c_int, _P(RawImage), _P(EncodeCfg),
@@ -295,6 +304,7 @@ _SIGS = {
     "uhdr_hip_apply_effect": (ErrorInfo, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(RawImage), _P(RawImage)]),
     "uhdr_hip_apply_effect_dev": (ErrorInfo, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(RawImage), _P(RawImage)]),
     "uhdr_hip_step_table_eval": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uhdr_hip_gamma_index_eval": (C.c_int, [C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "uhdr_hip_comm_unique_id": (C.c_int, [C.c_void_p]),
     "uhdr_hip_comm_init": (ErrorInfo, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "uhdr_hip_comm_destroy": (None, [C.c_void_p]),

@@ -536,17 +536,43 @@ uhdr_error_info_t validate_apply(const uhdr_raw_image_t* sdr, const uhdr_raw_ima
 }
 
 // acquire a table slot holding the ApplyTables block for (metadata, weight, scale)
+// d_gamma non-null (UHDR_HIP_APPLY_GAMMA_TABLE): the block is followed by the three channels' GainLUT index thresholds
+// (host_tables.cpp: gamma_index_table) and *d_gamma points at them -- or is null when a channel with gamma != 1 has no verified
+// table.  Such a block has a key of its own, so the blocks of the older entry points are what they were.
 uhdr_error_info_t get_apply_tables(uhdr_hip_ctx* c, const uhdr_gainmap_metadata_t& md, float weight,
-                                   int idw_scale, const float** d_out) {
+                                   int idw_scale, const float** d_out, const float** d_gamma) {
   std::string key((const char*)&md, sizeof md);
   key.append((const char*)&weight, sizeof weight);
   key.append((const char*)&idw_scale, sizeof idw_scale);
+  if (d_gamma) key.append("g", 1);
   for (int i = 0; i < kTableSlots; i++)
-    if (c->tab_cap[i] && c->tab_key[i] == key) { *d_out = c->d_tab[i]; return ok_status(); }
+    if (c->tab_cap[i] && c->tab_key[i] == key) {
+      *d_out = c->d_tab[i];
+      if (d_gamma) *d_gamma = c->tab_gamma_off[i] ? c->d_tab[i] + c->tab_gamma_off[i] : nullptr;
+      return ok_status();
+    }
   const int slot = c->tab_next;
   c->tab_next = (c->tab_next + 1) % kTableSlots;
   std::vector<float> t;
   host::build_apply_tables(md, weight, idw_scale, &t);
+  size_t gamma_off = 0;
+  if (d_gamma) {
+    const bool single = host::metadata_channels_identical(md);
+    const host::GammaIndexTable* g[3] = {nullptr, nullptr, nullptr};
+    bool usable = true;
+    for (int ch = 0; ch < 3; ch++) {
+      const float gamma_inv = 1.0f / md.gamma[single ? 0 : ch];
+      if (gamma_inv == 1.0f) continue;  // the index of this channel needs no pow
+      g[ch] = &host::gamma_index_table(gamma_inv);
+      if (!g[ch]->exact) usable = false;
+    }
+    if (usable) {
+      gamma_off = t.size();
+      t.resize(gamma_off + 3 * (size_t)kGammaThrN, INFINITY);
+      for (int ch = 0; ch < 3; ch++)
+        if (g[ch]) memcpy(t.data() + gamma_off + (size_t)ch * kGammaThrN, g[ch]->thr.data(), sizeof(float) * kGammaThrN);
+    }
+  }
   const size_t bytes = t.size() * sizeof(float);
   if (c->tab_cap[slot]) HIP_TRY(hipEventSynchronize(c->tab_ev[slot]));  // previous upload from this slot done
   if (c->tab_cap[slot] < bytes) {
@@ -564,7 +590,9 @@ uhdr_error_info_t get_apply_tables(uhdr_hip_ctx* c, const uhdr_gainmap_metadata_
   HIP_TRY(hipMemcpyAsync(c->d_tab[slot], c->h_tab[slot], bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipEventRecord(c->tab_ev[slot], c->stream));
   c->tab_key[slot] = key;
+  c->tab_gamma_off[slot] = gamma_off;
   *d_out = c->d_tab[slot];
+  if (d_gamma) *d_gamma = gamma_off ? c->d_tab[slot] + gamma_off : nullptr;
   return ok_status();
 }
 }  // namespace uhdr_api

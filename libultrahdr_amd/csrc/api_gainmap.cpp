@@ -7,9 +7,12 @@
 static uhdr_error_info_t build_apply_params(uhdr_hip_ctx* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
                                             const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct,
                                             float max_display_boost, uhdr_raw_image_t* dest, unsigned int y0,
-                                            unsigned int full_height, ApplyParams* out, bool resize_in_kernel = false) {
+                                            unsigned int full_height, ApplyParams* out, bool resize_in_kernel = false,
+                                            bool gamma_table = false) {
   // resize_in_kernel: the _any entry points' fused route -- a map of another aspect ratio is resized by the sampler
   // (ApplyParams::resize_on) instead of being refused
+  // gamma_table (UHDR_HIP_APPLY_GAMMA_TABLE): the GainLUT index thresholds of the metadata's gammas travel with the table block
+  // (ApplyParams::gamma_thr; null when a gamma has no verified table -- the kernels then keep the pow per sample)
   UHDR_TRY(validate_apply(sdr, gm, md, out_ct, dest));
   // colour-space bookkeeping (jpegr.cpp:1616-1631)
   const int sdr_cg = sdr->cg == UHDR_CG_UNSPECIFIED ? UHDR_CG_BT_709 : sdr->cg;
@@ -53,7 +56,7 @@ static uhdr_error_info_t build_apply_params(uhdr_hip_ctx* c, const uhdr_raw_imag
     return err_status(UHDR_CODEC_INVALID_PARAM, "image dimensions beyond 65535 are not supported");
 
   const float weight = host::gainmap_weight(*md, max_display_boost);
-  UHDR_TRY(get_apply_tables(c, *md, weight, use_table ? (int)p.scale : msf_rnd, &p.tables));
+  UHDR_TRY(get_apply_tables(c, *md, weight, use_table ? (int)p.scale : msf_rnd, &p.tables, gamma_table ? &p.gamma_thr : nullptr));
   if (out_ct == UHDR_CT_HLG) {
     UHDR_TRY(upload_lut(&c->d_hlg_oetf, host::oetf_code_thresholds(UHDR_CT_HLG), c->stream));
     p.oetf_thr = c->d_hlg_oetf;
@@ -101,6 +104,7 @@ static uhdr_error_info_t build_apply_params(uhdr_hip_ctx* c, const uhdr_raw_imag
     p.offset_sdr[i] = md->offset_sdr[i];
     p.offset_hdr[i] = md->offset_hdr[i];
   }
+  p.gamma_same = (!memcmp(&p.gamma_inv[0], &p.gamma_inv[1], 4) && !memcmp(&p.gamma_inv[0], &p.gamma_inv[2], 4)) ? 1 : 0;
   p.yuv = host::yuv2rgb_coeffs(UHDR_CG_DISPLAY_P3);
   return ok_status();
 }
@@ -150,22 +154,25 @@ bool mall_touch(uhdr_hip_ctx* c, const void* key, size_t bytes) {
 }
 }  // namespace
 
+// the profile family of a launch: the table forms of gamma != 1 are recorded apart, so that a profile says which kernel ran
+static const char* apply_family(const ApplyParams& p) {
+  const int r = apply_gamma_route(p);
+  return r == 1 ? "apply_gainmap_gamma_quad" : (r == 2 ? "apply_gainmap_gamma_generic" : "apply_gainmap");
+}
+
+// One body for uhdr_hip_apply_gainmap_dev (flags 0), uhdr_hip_apply_gainmap_any_dev (UHDR_HIP_APPLY_RESIZED_MAP) and
+// uhdr_hip_apply_gainmap_ex_dev (any flags)
+static uhdr_error_info_t apply_gainmap_flags_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
+                                                 const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct, float max_display_boost,
+                                                 uhdr_raw_image_t* dest, unsigned int y0, unsigned int full_height, unsigned int flags);
+
 uhdr_error_info_t uhdr_hip_apply_gainmap_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr,
                                              const uhdr_raw_image_t* gm, const uhdr_gainmap_metadata_t* md,
                                              uhdr_color_transfer_t out_ct, uhdr_img_fmt_t out_fmt,
                                              float max_display_boost, uhdr_raw_image_t* dest, unsigned int y0,
                                              unsigned int full_height) {
   (void)out_fmt;
-  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
-  HIP_TRY(hipSetDevice(c->device));
-  ApplyParams p;
-  UHDR_TRY(build_apply_params(c, sdr, gm, md, out_ct, max_display_boost, dest, y0, full_height, &p));
-  p.inputs_hot = mall_touch(c, sdr->planes[0], input_bytes(sdr) + input_bytes(gm)) ? 1u : 0u;
-  {
-    ProfScope ps(c, "apply_gainmap");
-    HIP_TRY(launch_apply_gainmap(p, c->stream));
-  }
-  return ok_status();
+  return apply_gainmap_flags_dev(c, sdr, gm, md, out_ct, max_display_boost, dest, y0, full_height, 0u);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -261,12 +268,22 @@ bool uhdr_api::api3_route_staged(int sampling) {
   return sampling == 420 ? kApi3DefaultStaged420 : (sampling == 422 ? kApi3DefaultStaged422 : kApi3DefaultStaged444);
 }
 
-uhdr_error_info_t uhdr_hip_apply_gainmap_any_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
-                                                 const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct, uhdr_img_fmt_t out_fmt,
-                                                 float max_display_boost, uhdr_raw_image_t* dest, unsigned int y0, unsigned int full_height) {
+static uhdr_error_info_t apply_gainmap_flags_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
+                                                 const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct, float max_display_boost,
+                                                 uhdr_raw_image_t* dest, unsigned int y0, unsigned int full_height, unsigned int flags) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
-  if (!map_needs_resize(sdr, gm, y0, full_height))
-    return uhdr_hip_apply_gainmap_dev(c, sdr, gm, md, out_ct, out_fmt, max_display_boost, dest, y0, full_height);
+  const bool gamma_table = (flags & UHDR_HIP_APPLY_GAMMA_TABLE) != 0;
+  if (!(flags & UHDR_HIP_APPLY_RESIZED_MAP) || !map_needs_resize(sdr, gm, y0, full_height)) {
+    HIP_TRY(hipSetDevice(c->device));
+    ApplyParams p;
+    UHDR_TRY(build_apply_params(c, sdr, gm, md, out_ct, max_display_boost, dest, y0, full_height, &p, false, gamma_table));
+    p.inputs_hot = mall_touch(c, sdr->planes[0], input_bytes(sdr) + input_bytes(gm)) ? 1u : 0u;
+    {
+      ProfScope ps(c, apply_family(p));
+      HIP_TRY(launch_apply_gainmap(p, c->stream));
+    }
+    return ok_status();
+  }
   UHDR_TRY(validate_apply(sdr, gm, md, out_ct, dest));
   HIP_TRY(hipSetDevice(c->device));
   const DbgClock clk;
@@ -286,13 +303,13 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_any_dev(uhdr_hip_ctx_t* c, const uhdr_r
     stripe.h = sdr->h;
     stripe.planes[0] = (uint8_t*)c->scratch[3].p + (size_t)y0 * whole.stride[0] * bpp;
     UHDR_TRY(uhdr_hip_resize_image_dev(c, gm, &stripe, y0, whole_h));
-    UHDR_TRY(build_apply_params(c, sdr, &whole, md, out_ct, max_display_boost, dest, y0, full_height, &p));
+    UHDR_TRY(build_apply_params(c, sdr, &whole, md, out_ct, max_display_boost, dest, y0, full_height, &p, false, gamma_table));
   } else {
-    UHDR_TRY(build_apply_params(c, sdr, gm, md, out_ct, max_display_boost, dest, y0, full_height, &p, true));
+    UHDR_TRY(build_apply_params(c, sdr, gm, md, out_ct, max_display_boost, dest, y0, full_height, &p, true, gamma_table));
   }
   p.inputs_hot = mall_touch(c, sdr->planes[0], input_bytes(sdr) + input_bytes(gm)) ? 1u : 0u;
   {
-    ProfScope ps(c, "apply_gainmap");
+    ProfScope ps(c, apply_family(p));
     HIP_TRY(launch_apply_gainmap(p, c->stream));
   }
   clk.mark(staged ? "apply_gainmap_any: map of another aspect ratio, staged route (resize_image, then applyGainMap at scale 1)"
@@ -300,9 +317,33 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_any_dev(uhdr_hip_ctx_t* c, const uhdr_r
   return ok_status();
 }
 
-uhdr_error_info_t uhdr_hip_apply_gainmap_any(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
-                                             const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct, uhdr_img_fmt_t out_fmt,
-                                             float max_display_boost, uhdr_raw_image_t* dest) {
+uhdr_error_info_t uhdr_hip_apply_gainmap_any_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
+                                                 const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct, uhdr_img_fmt_t out_fmt,
+                                                 float max_display_boost, uhdr_raw_image_t* dest, unsigned int y0, unsigned int full_height) {
+  (void)out_fmt;
+  return apply_gainmap_flags_dev(c, sdr, gm, md, out_ct, max_display_boost, dest, y0, full_height, UHDR_HIP_APPLY_RESIZED_MAP);
+}
+
+static uhdr_error_info_t check_apply_flags(unsigned int flags) {
+  if (flags & ~(unsigned int)(UHDR_HIP_APPLY_RESIZED_MAP | UHDR_HIP_APPLY_GAMMA_TABLE))
+    return err_status(UHDR_CODEC_INVALID_PARAM, "unknown applyGainMap flag bits 0x%x", flags & ~(unsigned int)(UHDR_HIP_APPLY_RESIZED_MAP | UHDR_HIP_APPLY_GAMMA_TABLE));
+  return ok_status();
+}
+
+uhdr_error_info_t uhdr_hip_apply_gainmap_ex_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
+                                                const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct, uhdr_img_fmt_t out_fmt,
+                                                float max_display_boost, uhdr_raw_image_t* dest, unsigned int y0, unsigned int full_height,
+                                                unsigned int flags) {
+  (void)out_fmt;
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  UHDR_TRY(check_apply_flags(flags));
+  return apply_gainmap_flags_dev(c, sdr, gm, md, out_ct, max_display_boost, dest, y0, full_height, flags);
+}
+
+// host images: stage in, the device form, stage out -- uhdr_hip_apply_gainmap (flags 0), _any (UHDR_HIP_APPLY_RESIZED_MAP) and _ex
+static uhdr_error_info_t apply_gainmap_flags_host(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
+                                                  const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct, float max_display_boost,
+                                                  uhdr_raw_image_t* dest, unsigned int flags) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   UHDR_TRY(validate_apply(sdr, gm, md, out_ct, dest));
   HIP_TRY(hipSetDevice(c->device));
@@ -310,10 +351,26 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_any(uhdr_hip_ctx_t* c, const uhdr_raw_i
   UHDR_TRY(stage_in(c, 0, sdr, &dsdr, true));
   UHDR_TRY(stage_in(c, 1, gm, &dgm, true));
   UHDR_TRY(stage_in(c, 2, dest, &ddst, false));
-  uhdr_error_info_t st = uhdr_hip_apply_gainmap_any_dev(c, &dsdr, &dgm, md, out_ct, out_fmt, max_display_boost, &ddst, 0, 0);
+  uhdr_error_info_t st = apply_gainmap_flags_dev(c, &dsdr, &dgm, md, out_ct, max_display_boost, &ddst, 0, 0, flags);
   if (st.error_code != UHDR_CODEC_OK) return st;
   dest->cg = ddst.cg;
   return stage_out(c, &ddst, dest);
+}
+
+uhdr_error_info_t uhdr_hip_apply_gainmap_any(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
+                                             const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct, uhdr_img_fmt_t out_fmt,
+                                             float max_display_boost, uhdr_raw_image_t* dest) {
+  (void)out_fmt;
+  return apply_gainmap_flags_host(c, sdr, gm, md, out_ct, max_display_boost, dest, UHDR_HIP_APPLY_RESIZED_MAP);
+}
+
+uhdr_error_info_t uhdr_hip_apply_gainmap_ex(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm,
+                                            const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct, uhdr_img_fmt_t out_fmt,
+                                            float max_display_boost, uhdr_raw_image_t* dest, unsigned int flags) {
+  (void)out_fmt;
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  UHDR_TRY(check_apply_flags(flags));
+  return apply_gainmap_flags_host(c, sdr, gm, md, out_ct, max_display_boost, dest, flags);
 }
 
 // Batch of n frames with identical geometry, formats, colour aspects and metadata (burst / video
@@ -417,14 +474,18 @@ static uhdr_raw_image_t coef_image_view(const uhdr_hip_jpeg_coefficients_t* base
 // sampling a small block grid belongs to, hence one entry point each.  sampling: 420, 422 or 444.
 static uhdr_error_info_t apply_gainmap_coef_impl(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_coefficients_t* base, unsigned int w, unsigned int h, int sampling,
                                                  uhdr_color_gamut_t base_cg, const uhdr_raw_image_t* gm, const uhdr_gainmap_metadata_t* md,
-                                                 uhdr_color_transfer_t out_ct, float max_display_boost, uhdr_raw_image_t* dest) {
+                                                 uhdr_color_transfer_t out_ct, float max_display_boost, uhdr_raw_image_t* dest, bool gamma_table = false) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   CoefSrc cs;
   UHDR_TRY(fill_coef_src(base, w, h, sampling, &cs));
   HIP_TRY(hipSetDevice(c->device));
   const uhdr_raw_image_t sdr = coef_image_view(base, w, h, sampling, base_cg);
   ApplyParams p;
-  UHDR_TRY(build_apply_params(c, &sdr, gm, md, out_ct, max_display_boost, dest, 0, 0, &p));
+  UHDR_TRY(build_apply_params(c, &sdr, gm, md, out_ct, max_display_boost, dest, 0, 0, &p, false, gamma_table));
+  if (apply_quad_mode(p) < 0 && gamma_table)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "apply_gainmap_coef_ex covers the 2x2-quad kernel's cases (even dimensions, width >= 128, 16-byte "
+                      "aligned destination rows, gain map at scale 1 or an even scale <= 8, with one verified gamma for the three channels); decode with "
+                      "idct_dequant and call apply_gainmap_ex");
   if (apply_quad_mode(p) < 0)
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "%s the 2x2-quad kernel's cases (even dimensions, width >= 128, 16-byte "
                       "aligned destination rows, gain map at scale 1 or an even scale <= 8 with gamma 1); decode with idct_dequant and call apply_gainmap",
@@ -442,7 +503,7 @@ static uhdr_error_info_t apply_gainmap_coef_impl(uhdr_hip_ctx_t* c, const uhdr_h
   }
   p.coef_src = slot;
   {
-    ProfScope ps(c, "apply_gainmap");
+    ProfScope ps(c, apply_family(p));
     HIP_TRY(launch_apply_gainmap_coef(p, c->stream));
   }
   return ok_status();
@@ -475,21 +536,28 @@ uhdr_error_info_t uhdr_hip_apply_gainmap_coef444_dev(uhdr_hip_ctx_t* c, const uh
   return apply_gainmap_coef_impl(c, base, w, h, 444, base_cg, gm, md, out_ct, max_display_boost, dest);
 }
 
+// Any of the three samplings (420, 422 or 444) with the applyGainMap flags: UHDR_HIP_APPLY_GAMMA_TABLE keeps a gamma != 1 at an even
+// scale <= 8 on the coefficient kernel; a resized map has no coefficient form (UHDR_HIP_APPLY_RESIZED_MAP is refused).
+uhdr_error_info_t uhdr_hip_apply_gainmap_coef_ex_dev(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_coefficients_t* base, int sampling, unsigned int w,
+                                                     unsigned int h, uhdr_color_gamut_t base_cg, const uhdr_raw_image_t* gm,
+                                                     const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct,
+                                                     uhdr_img_fmt_t out_fmt, float max_display_boost, uhdr_raw_image_t* dest, unsigned int flags) {
+  (void)out_fmt;
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  UHDR_TRY(check_apply_flags(flags));
+  if (flags & UHDR_HIP_APPLY_RESIZED_MAP)
+    return err_status(UHDR_CODEC_INVALID_PARAM, "UHDR_HIP_APPLY_RESIZED_MAP does not apply to coefficient input: a gain map of another aspect ratio is refused here");
+  if (sampling != 420 && sampling != 422 && sampling != 444)
+    return err_status(UHDR_CODEC_INVALID_PARAM, "sampling is one of 420, 422, 444; received %d", sampling);
+  return apply_gainmap_coef_impl(c, base, w, h, sampling, base_cg, gm, md, out_ct, max_display_boost, dest, (flags & UHDR_HIP_APPLY_GAMMA_TABLE) != 0);
+}
+
 uhdr_error_info_t uhdr_hip_apply_gainmap(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr,
                                          const uhdr_raw_image_t* gm, const uhdr_gainmap_metadata_t* md,
                                          uhdr_color_transfer_t out_ct, uhdr_img_fmt_t out_fmt,
                                          float max_display_boost, uhdr_raw_image_t* dest) {
-  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
-  UHDR_TRY(validate_apply(sdr, gm, md, out_ct, dest));
-  HIP_TRY(hipSetDevice(c->device));
-  uhdr_raw_image_t dsdr, dgm, ddst;
-  UHDR_TRY(stage_in(c, 0, sdr, &dsdr, true));
-  UHDR_TRY(stage_in(c, 1, gm, &dgm, true));
-  UHDR_TRY(stage_in(c, 2, dest, &ddst, false));
-  uhdr_error_info_t st = uhdr_hip_apply_gainmap_dev(c, &dsdr, &dgm, md, out_ct, out_fmt, max_display_boost, &ddst, 0, 0);
-  if (st.error_code != UHDR_CODEC_OK) return st;
-  dest->cg = ddst.cg;
-  return stage_out(c, &ddst, dest);
+  (void)out_fmt;
+  return apply_gainmap_flags_host(c, sdr, gm, md, out_ct, max_display_boost, dest, 0u);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1165,6 +1233,22 @@ int uhdr_hip_step_table_eval(int which, float a, float b, const float* in, uint3
     const uint32_t thr = t->entries[off / 4], cc = t->entries[off / 4 + 1];
     out[i] = u >= thr ? cc >> 16 : cc & 0xffffu;
   }
+  return 0;
+}
+
+int uhdr_hip_gamma_index_eval(float gamma, const float* in, uint32_t* out, size_t n, uint32_t info[4], float* thresholds) {
+  const host::GammaIndexTable& t = host::gamma_index_table(1.0f / gamma);
+  if (info) {
+    info[0] = t.exact ? 1u : 0u;
+    info[1] = (uint32_t)kGainN;
+    info[2] = (uint32_t)(t.build_ms * 1000.0);  // microseconds the construction took
+    info[3] = 0;
+  }
+  if (!t.exact) return 1;
+  const float* T = t.thr.data() + 1;
+  if (thresholds) memcpy(thresholds, T, sizeof(float) * (kGainN + 1));
+  if (in && out)
+    for (size_t i = 0; i < n; i++) out[i] = host::gamma_index_lookup(in[i], T, t.gamma_inv);
   return 0;
 }
 

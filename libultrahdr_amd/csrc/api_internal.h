@@ -109,6 +109,7 @@ struct uhdr_hip_ctx {
   size_t tab_cap[kTableSlots] = {};
   hipEvent_t tab_ev[kTableSlots] = {};
   std::string tab_key[kTableSlots];
+  size_t tab_gamma_off[kTableSlots] = {};  // floats from the block's start to the GainLUT index thresholds behind it (0: the block has none)
   int tab_next = 0;
   // scratch for host-buffer entry points and two-pass generation; [3]: the gain map at the base image's size
   // (uhdr_hip_apply_gainmap_any, staged route)
@@ -280,7 +281,8 @@ uhdr_error_info_t validate_metadata(const uhdr_gainmap_metadata_t* m);
 bool is_rgb_fmt_host(int fmt);
 uhdr_error_info_t validate_apply(const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* gm, const uhdr_gainmap_metadata_t* md, uhdr_color_transfer_t out_ct,
                                  const uhdr_raw_image_t* dest);
-uhdr_error_info_t get_apply_tables(uhdr_hip_ctx* c, const uhdr_gainmap_metadata_t& md, float weight, int idw_scale, const float** d_out);
+uhdr_error_info_t get_apply_tables(uhdr_hip_ctx* c, const uhdr_gainmap_metadata_t& md, float weight, int idw_scale, const float** d_out,
+                                   const float** d_gamma = nullptr);
 // ---- api_gainmap.cpp: parameter blocks of the gain-map operators (shared with the striped and the fused entry points) ----
 uhdr_error_info_t fill_gen_params(uhdr_hip_ctx* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg, GenParams* p,
                                   int* use_base_cg, float* hdr_white_nits_out, bool sdr_in_registers = false);

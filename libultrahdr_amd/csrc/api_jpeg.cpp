@@ -16,7 +16,7 @@ int uhdr_hip_oetf_code_thresholds(uhdr_color_transfer_t ct, float thresholds[102
 uhdr_error_info_t uhdr_hip_selftest(uhdr_hip_ctx_t* c, int which, unsigned int arg0, unsigned int arg1, unsigned int seed, const float mm[6],
                                     unsigned long long out[8]) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
-  if (!out || which < 0 || which > 4 || (which == 4 && (!mm || arg0 > 2 || arg1 < 1 || arg1 > 3 || arg0 >= arg1)) || (which == 2 && (arg0 < 1 || arg1 > 254 || arg0 > arg1)))
+  if (!out || which < 0 || which > 5 || (which == 5 && !mm) || (which == 4 && (!mm || arg0 > 2 || arg1 < 1 || arg1 > 3 || arg0 >= arg1)) || (which == 2 && (arg0 < 1 || arg1 > 254 || arg0 > arg1)))
     return err_status(UHDR_CODEC_INVALID_PARAM, "bad self-test arguments");
   HIP_TRY(hipSetDevice(c->device));
   UHDR_TRY(upload_math(c));
@@ -34,6 +34,24 @@ uhdr_error_info_t uhdr_hip_selftest(uhdr_hip_ctx_t* c, int which, unsigned int a
     t.dev = (AffineDev*)c->affine.p;
     t.math_tab = c->d_math;
     HIP_TRY(launch_minmax_table(t, c->stream));
+  }
+  if (which == 5) {  // mm[0]: the gain-map gamma whose GainLUT index thresholds are swept
+    const host::GammaIndexTable& t = host::gamma_index_table(1.0f / mm[0]);
+    if (!t.exact) {
+      for (int i = 0; i < 8; i++) out[i] = 0;
+      out[3] = 1;  // no table for this gamma
+      return ok_status();
+    }
+    UHDR_TRY(ensure(c->scratch[7], sizeof(float) * kGammaThrN));
+    HIP_TRY(hipMemcpyAsync(c->scratch[7].p, t.thr.data(), sizeof(float) * kGammaThrN, hipMemcpyHostToDevice, c->stream));
+    uint32_t ginv_bits, last;
+    memcpy(&ginv_bits, &t.gamma_inv, 4);
+    memcpy(&last, &t.thr[1 + 1023], 4);
+    last += 8;  // a few ulps past the last threshold
+    HIP_TRY(launch_selftest(which, d_out, ginv_bits, last, seed, c->d_math, (const AffineDev*)c->scratch[7].p, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, d_out, 64, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return ok_status();
   }
   HIP_TRY(launch_selftest(which, d_out, arg0, arg1, seed, c->d_math, (const AffineDev*)c->affine.p, c->stream));
   HIP_TRY(hipMemcpyAsync(out, d_out, 64, hipMemcpyDeviceToHost, c->stream));
@@ -1506,8 +1524,16 @@ static uhdr_error_info_t decode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_hi
                                                 uhdr_color_gamut_t base_cg, const uhdr_hip_jpeg_header_t* map, const uint8_t* map_data, size_t map_bytes,
                                                 uhdr_color_gamut_t map_cg, int libjpeg_variant, const uhdr_gainmap_metadata_t* md,
                                                 uhdr_color_transfer_t output_ct, uhdr_img_fmt_t output_format, float max_display_boost,
-                                                uhdr_raw_image_t* dest, bool allow_444) {
+                                                uhdr_raw_image_t* dest, bool allow_444, bool ex = false, unsigned int apply_flags = 0) {
+  // ex (uhdr_hip_decode_api1_scans_ex_dev): applyGainMap runs through its _ex forms with apply_flags -- with UHDR_HIP_APPLY_GAMMA_TABLE a
+  // gamma != 1 at an even scale <= 8 stays on the coefficient kernel, and the planes fallback uses the threshold table as well
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  if (ex) {
+    if (apply_flags & ~(unsigned int)(UHDR_HIP_APPLY_RESIZED_MAP | UHDR_HIP_APPLY_GAMMA_TABLE))
+      return err_status(UHDR_CODEC_INVALID_PARAM, "unknown applyGainMap flag bits 0x%x", apply_flags & ~(unsigned int)(UHDR_HIP_APPLY_RESIZED_MAP | UHDR_HIP_APPLY_GAMMA_TABLE));
+    if (apply_flags & UHDR_HIP_APPLY_RESIZED_MAP)
+      return err_status(UHDR_CODEC_INVALID_PARAM, "UHDR_HIP_APPLY_RESIZED_MAP does not apply to the one-call decode: a gain map of another aspect ratio is refused here");
+  }
   if (!base || !base_data || !map || !map_data || !md || !dest) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument for decode_api1_scans");
   if (libjpeg_variant != 0 && libjpeg_variant != 1) return err_status(UHDR_CODEC_INVALID_PARAM, "unknown libjpeg variant %d", libjpeg_variant);
   uhdr_hip_jpeg_scan_t sb = base->scan, sm = map->scan;
@@ -1569,7 +1595,9 @@ static uhdr_error_info_t decode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_hi
     bc.blocks_h[i] = sb.blocks_h[i];
     memcpy(bc.qtable[i], base->qtable[i], sizeof bc.qtable[i]);
   }
-  uhdr_error_info_t ap = is444      ? uhdr_hip_apply_gainmap_coef444_dev(c, &bc, sb.w, sb.h, base_cg, &gm, md, output_ct, output_format, max_display_boost, dest)
+  uhdr_error_info_t ap = ex         ? uhdr_hip_apply_gainmap_coef_ex_dev(c, &bc, is444 ? 444 : (vsamp == 2 ? 420 : 422), sb.w, sb.h, base_cg, &gm, md, output_ct, output_format,
+                                                                          max_display_boost, dest, apply_flags)
+                         : is444    ? uhdr_hip_apply_gainmap_coef444_dev(c, &bc, sb.w, sb.h, base_cg, &gm, md, output_ct, output_format, max_display_boost, dest)
                          : vsamp == 2 ? uhdr_hip_apply_gainmap_coef_dev(c, &bc, sb.w, sb.h, base_cg, &gm, md, output_ct, output_format, max_display_boost, dest)
                                       : uhdr_hip_apply_gainmap_coef422_dev(c, &bc, sb.w, sb.h, base_cg, &gm, md, output_ct, output_format, max_display_boost, dest);
   if (ap.error_code != UHDR_CODEC_UNSUPPORTED_FEATURE) return ap;
@@ -1595,6 +1623,7 @@ static uhdr_error_info_t decode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_hi
     bi.planes[i] = d;
     bi.stride[i] = (unsigned int)ppitch[i];
   }
+  if (ex) return uhdr_hip_apply_gainmap_ex_dev(c, &bi, &gm, md, output_ct, output_format, max_display_boost, dest, 0, 0, apply_flags);
   return uhdr_hip_apply_gainmap_dev(c, &bi, &gm, md, output_ct, output_format, max_display_boost, dest, 0, 0);
 }
 
@@ -1616,6 +1645,16 @@ uhdr_error_info_t uhdr_hip_decode_api1_scans_any_dev(uhdr_hip_ctx_t* c, const uh
                                                      uhdr_raw_image_t* dest) {
   return decode_api1_scans_impl(c, base, base_data, base_bytes, base_cg, map, map_data, map_bytes, map_cg, libjpeg_variant, md, output_ct, output_format,
                                 max_display_boost, dest, true);
+}
+
+// uhdr_hip_decode_api1_scans_any_dev with applyGainMap's flags (UHDR_HIP_APPLY_GAMMA_TABLE; a resized map has no form here)
+uhdr_error_info_t uhdr_hip_decode_api1_scans_ex_dev(uhdr_hip_ctx_t* c, const uhdr_hip_jpeg_header_t* base, const uint8_t* base_data, size_t base_bytes,
+                                                    uhdr_color_gamut_t base_cg, const uhdr_hip_jpeg_header_t* map, const uint8_t* map_data, size_t map_bytes,
+                                                    uhdr_color_gamut_t map_cg, int libjpeg_variant, const uhdr_gainmap_metadata_t* md,
+                                                    uhdr_color_transfer_t output_ct, uhdr_img_fmt_t output_format, float max_display_boost,
+                                                    uhdr_raw_image_t* dest, unsigned int apply_flags) {
+  return decode_api1_scans_impl(c, base, base_data, base_bytes, base_cg, map, map_data, map_bytes, map_cg, libjpeg_variant, md, output_ct, output_format,
+                                max_display_boost, dest, true, true, apply_flags);
 }
 
 // -------------------------------------------------------------------------------------------------

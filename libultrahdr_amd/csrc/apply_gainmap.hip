@@ -19,6 +19,7 @@
 
 #include "cu_count.h"
 #include "coef_tile.h"
+#include "gain_index.h"
 #include "resize_core.h"
 #include "uhdr_types.h"
 
@@ -142,9 +143,17 @@ __device__ __forceinline__ typename OutPix<OUT>::type finish_pixel(Color3 lin, f
 }
 
 // gain value (0..1) -> factor through the GainLUT (gainmapmath.h:483-489)
-__device__ __forceinline__ float gain_factor(float gain, const float* gain_tab, int ch,
+// GTAB 1 (UHDR_HIP_APPLY_GAMMA_TABLE): the index int(pow(gain, 1 / gamma) * 1023 + 0.5) of a channel with gamma != 1 comes from
+// the host-built thresholds (host_tables.cpp: gamma_index_table; gthr: the three channels' blocks, T[i] at [1 + i]) by the
+// ten-step search of gain_index.h: index = max{ i : T[i] <= gain }.  No pow, no double.
+template <int GTAB>
+__device__ __forceinline__ float gain_factor(float gain, const float* gain_tab, const float* gthr, int ch,
                                              const ApplyParams& p) {
-  if (!p.gamma_is_one[ch]) gain = (float)pow((double)gain, (double)p.gamma_inv[ch]);
+  if constexpr (GTAB == 1) {
+    if (!p.gamma_is_one[ch]) return gain_tab[ch * kGainN + gain_index_search(gain, gthr + ch * kGammaThrN + 1)];
+  } else {
+    if (!p.gamma_is_one[ch]) gain = (float)pow((double)gain, (double)p.gamma_inv[ch]);
+  }
   return gain_tab[ch * kGainN + lut_index_f32<kGainN>(gain)];
 }
 
@@ -263,11 +272,13 @@ __device__ __forceinline__ void sample_map_resized(const ApplyParams& p, const f
 // live in LDS (the IDW weights, whose size depends on the scale, stay in global memory), a workgroup
 // walks tiles of 256 consecutive pixels of one row
 // ---------------------------------------------------------------------------------------------
-template <int OUT>
+template <int OUT, int GTAB = 0>
 __global__ __launch_bounds__(kBlock) void apply_generic_kernel(const ApplyParams p) {
   __shared__ float s_srgb[kSrgbN];
   __shared__ float s_gain[3 * kGainN];
   __shared__ float s_u8f[256];
+  __shared__ float s_gthr[GTAB == 1 ? 3 * kGammaThrN : 4];  // GTAB 1: the GainLUT index thresholds of the three channels
+  if constexpr (GTAB == 1) copy_to_lds(s_gthr, p.gamma_thr, 3u * kGammaThrN, threadIdx.x, kBlock);
   copy_to_lds(s_srgb, p.tables + ApplyTables::kSrgbOff, kSrgbN, threadIdx.x, kBlock);
   copy_to_lds(s_gain, p.tables + ApplyTables::kGainOff, 3 * kGainN, threadIdx.x, kBlock);
   copy_to_lds(s_u8f, p.tables + ApplyTables::kU8fOff, 256u, threadIdx.x, kBlock);
@@ -320,10 +331,10 @@ __global__ __launch_bounds__(kBlock) void apply_generic_kernel(const ApplyParams
       else if (p.scale) sample_map_table<3>(p, u8f, idw, x, yg, gn);
       else sample_map_float<3>(p, u8f, x, yg, gn);
     }
-    float f0 = gain_factor(gn[0], gain_tab, 0, p), f1 = f0, f2 = f0;
+    float f0 = gain_factor<GTAB>(gn[0], gain_tab, s_gthr, 0, p), f1 = f0, f2 = f0;
     if (p.map_ch != 1) {
-      f1 = gain_factor(gn[1], gain_tab, 1, p);
-      f2 = gain_factor(gn[2], gain_tab, 2, p);
+      f1 = gain_factor<GTAB>(gn[1], gain_tab, s_gthr, 1, p);
+      f2 = gain_factor<GTAB>(gn[2], gain_tab, s_gthr, 2, p);
     }
     auto px = finish_pixel<OUT>(lin, f0, f1, f2, p, p.map_ch);
     using T = typename OutPix<OUT>::type;
@@ -337,7 +348,9 @@ __global__ __launch_bounds__(kBlock) void apply_generic_kernel(const ApplyParams
 //   MAPFMT: 0 Y400, 1 RGB888, 2 RGBA8888.
 //   SMODE : 0 scale == 1 (byte -> factor table, no interpolation),
 //           1 even integer scale (the four taps are shared by the whole 2x2 quad; only the
-//             weights differ per pixel).
+//             weights differ per pixel),
+//           2 as 1 with a gain-map gamma != 1, the same for the three channels: the GainLUT index comes from the threshold
+//             table (gain_index_pair) instead of one multiply-add.
 // One lane = one chroma sample = a 2x2 luma quad.  The two pixels of a row are carried as a
 // 2-vector so the float pipeline maps onto the packed v_pk_{mul,add}_f32 instructions (each packed
 // op is still one IEEE mul / add per element: bit-identical to scalar code).  All addressing is
@@ -399,6 +412,16 @@ __device__ __forceinline__ f2 lds_gather(const float* base, uint2 byte_off) {
   const char* b = (const char*)base;
   return (f2){*(const float*)(b + byte_off.x), *(const float*)(b + byte_off.y)};
 }
+// the GainLUT index of a pixel pair for a gamma != 1 (gain_index.h), as byte offsets into the GainLUT; one ballot for both
+__device__ __forceinline__ uint2 gain_index_pair(f2 g, const float* T, float ginv) {
+  bool ok0, ok1;
+  uint32_t i0 = gain_index_try(g.x, T, ginv, ok0), i1 = gain_index_try(g.y, T, ginv, ok1);
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(!(ok0 && ok1)) != 0, 0)) {
+    if (!ok0) i0 = gain_index_search(g.x, T);
+    if (!ok1) i1 = gain_index_search(g.y, T);
+  }
+  return (uint2){i0 << 2, i1 << 2};
+}
 // the smallest float whose floatToHalf lands in the normal-half range: bits + 0x1000 >= 113 << 23
 #define UHDR_HALF_FAST_MIN_BITS ((113u << 23) - 0x1000u)
 
@@ -447,8 +470,8 @@ struct QuadRaw {
   uint32_t y0, y1;  // BASE 0/1: two luma bytes of row 0 / row 1; BASE 2: unused
   uint32_t u, v;    // BASE 0: the quad's chroma bytes; BASE 1: row-0 chroma pairs (two bytes each); BASE 3: row-0 chroma bytes
   uint32_t c[(BASE == 0) ? 1 : 4];  // BASE 1 / 3: {.., .., u row 1, v row 1}; BASE 2: the four RGBA8888 pixels {r0p0, r0p1, r1p0, r1p1}
-  uint32_t m[(SMODE == 0) ? 4 : 4 * NCH];  // SMODE 0: map bytes {row0 lo, row0 hi, row1 lo, row1 hi}; SMODE 1: tap bytes [tap][ch]
-  uint32_t wrow;    // SMODE 1: row part of the weight-table index (wave-uniform)
+  uint32_t m[(SMODE == 0) ? 4 : 4 * NCH];  // SMODE 0: map bytes {row0 lo, row0 hi, row1 lo, row1 hi}; SMODE 1 / 2: tap bytes [tap][ch]
+  uint32_t wrow;    // SMODE 1 / 2: row part of the weight-table index (wave-uniform)
   uint32_t y;       // first row of the quad (wave-uniform)
 };
 
@@ -501,7 +524,8 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
   __shared__ __attribute__((aligned(16))) float s_srgb[kSrgbPad];
   __shared__ __attribute__((aligned(16))) float s_gain[(SMODE == 0) ? 4 : NCH * kGainN];
   __shared__ __attribute__((aligned(16))) float s_u8f[(BASE == 2) ? 256 : 4];  // byte / 255.0f: RGBA8888 base samples (BASE 2)
-  __shared__ __attribute__((aligned(16))) float s_tap[(SMODE == 1) ? 512 : 4];  // map taps (SMODE 1): byte / 255.0f, pre-splatted {x, x}
+  __shared__ __attribute__((aligned(16))) float s_tap[(SMODE != 0) ? 512 : 4];  // map taps (SMODE 1 / 2): byte / 255.0f, pre-splatted {x, x}
+  __shared__ __attribute__((aligned(16))) float s_gthr[(SMODE == 2) ? kGammaThrN : 4];  // SMODE 2: the GainLUT index thresholds, T[i] at [1 + i]
   __shared__ __attribute__((aligned(16))) float s_fac[(SMODE == 0) ? NCH * 256 : 4];
   // chroma byte -> p3YuvToRgb's products {cr * vf, gcr * vf} / {gcb * uf, cb * uf} (host_tables.cpp): two 8-byte LDS reads per
   // chroma sample replace two integer subtractions, two conversions and six multiplications.  (Entries pre-splatted to
@@ -542,6 +566,7 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
       copy16(s_gain, p.tables + ApplyTables::kGainOff, NCH * kGainN);
       copy16(s_tap, p.tables + ApplyTables::kTapOff, 512);
       copy16(s_idw, p.tables + ApplyTables::idw_pair_off((int)p.scale), 4 * p.scale * p.scale * 4);
+      if constexpr (SMODE == 2) copy16(s_gthr, p.gamma_thr, kGammaThrN);
     }
     __syncthreads();
   };
@@ -630,6 +655,8 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
   const f2 off_s2 = splat(p.offset_sdr[NCH == 1 ? 0 : 2]), off_h2 = splat(p.offset_hdr[NCH == 1 ? 0 : 2]);
   const uint32_t scale = p.scale, half_scale = p.scale >> 1, magic = p.scale_magic;
   const uint32_t gmh1 = p.gm.h - 1, y0g = p.y0;
+  const float gamma_inv = p.gamma_inv[0];  // SMODE 2: the three channels share it (apply_gamma_route)
+  (void)gamma_inv;
   // LDS byte address of the code table minus its first bucket's offset (wraps modulo 2^32, as does the add that uses it)
   const uint32_t code_rel = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)s_code - p.oetf_base8;
   const uint32_t code_lo = p.oetf_lo_bits, code_hi = p.oetf_hi_bits;
@@ -651,7 +678,7 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
     Col c;
     c.xc = xc;
     c.col_l = c.col_u = c.wcol = 0;
-    if constexpr (SMODE == 1) {
+    if constexpr (SMODE != 0) {
       const uint32_t gmw1 = p.gm.w - 1;
       uint32_t xl = __umulhi(xc, magic);
       const uint32_t ox = xc - xl * scale;
@@ -776,7 +803,7 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
     const uint32_t xdst = col[hq].xc * OPX, wcol = col[hq].wcol;
     (void)wcol;
     f2 tap[(SMODE == 0) ? 1 : 4][NCH];
-    if constexpr (SMODE == 1) {
+    if constexpr (SMODE != 0) {
 #pragma unroll
       for (int k = 0; k < 4; k++)
 #pragma unroll
@@ -850,12 +877,17 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
         const f2 w0 = {wa.x, wa.y}, w1 = {wa.z, wa.w}, w2 = {wb.x, wb.y}, w3 = {wb.z, wb.w};
         // sampleMap: e1*w0 + e2*w1 + e3*w2 + e4*w3, left to right (gainmapmath.cpp:955, 1079)
         const f2 g0 = tap[0][0] * w0 + tap[1][0] * w1 + tap[2][0] * w2 + tap[3][0] * w3;
-        f0 = lds_gather(s_gain, lut_off_1024(g0));  // weights sum to 1 +- 1ulp: the index stays <= 1023
+        // the GainLUT index: one multiply-add when gamma == 1, the threshold lookup otherwise (SMODE 2)
+        auto gain_off = [&](f2 g) {
+          if constexpr (SMODE == 2) return gain_index_pair(g, s_gthr + 1, gamma_inv);
+          else return lut_off_1024(g);
+        };
+        f0 = lds_gather(s_gain, gain_off(g0));  // weights sum to 1 +- 1ulp: the index stays <= 1023
         if constexpr (NCH == 3) {
           const f2 g1 = tap[0][1] * w0 + tap[1][1] * w1 + tap[2][1] * w2 + tap[3][1] * w3;
           const f2 g2 = tap[0][2] * w0 + tap[1][2] * w1 + tap[2][2] * w2 + tap[3][2] * w3;
-          f1 = lds_gather(s_gain + kGainN, lut_off_1024(g1));
-          f2_ = lds_gather(s_gain + 2 * kGainN, lut_off_1024(g2));
+          f1 = lds_gather(s_gain + kGainN, gain_off(g1));
+          f2_ = lds_gather(s_gain + 2 * kGainN, gain_off(g2));
         } else {
           f1 = f0; f2_ = f0;
         }
@@ -1001,7 +1033,7 @@ __device__ __forceinline__ void apply_quad_body(const ApplyParams& p) {
     __shared__ __attribute__((aligned(8))) uint8_t s_ct[BLK / 64][2][G::CROWS * G::CPITCH];
     // one workgroup's tables and tiles must fit a CU's LDS (the 768-thread HLG / PQ workgroups carry twelve tiles next to the
     // output-code buckets)
-    static_assert(sizeof s_srgb + sizeof s_gain + sizeof s_u8f + sizeof s_tap + sizeof s_fac + sizeof s_cv + sizeof s_cu + sizeof s_code + sizeof s_idw +
+    static_assert(sizeof s_srgb + sizeof s_gain + sizeof s_u8f + sizeof s_tap + sizeof s_fac + sizeof s_cv + sizeof s_cu + sizeof s_code + sizeof s_idw + sizeof s_gthr +
                       sizeof s_ws + sizeof s_q + sizeof s_yt + sizeof s_ct <= 160 * 1024,
                   "the coefficient-input workgroup exceeds the 160 KB of LDS of a CU");
     const CoefSrc* __restrict__ cs = p.coef_src;
@@ -1105,7 +1137,7 @@ __global__ __launch_bounds__(quad_block<OUT>()) __attribute__((amdgpu_num_sgpr(9
 // arm is kept as tools/spill_exp.patch, not in the product).
 template <int OUT, int MAPFMT, int SMODE, int BASE, int SRC = 0>
 __global__ __launch_bounds__(quad_block<OUT>()) __attribute__((amdgpu_num_sgpr(96), amdgpu_waves_per_eu(3, 8))) void apply_quad_kernel_s96w3(const ApplyParams p) {
-  static_assert(quad_sgprs<SMODE, SRC>() == 96 && OUT != 0 && MAPFMT != 0 && SMODE == 1 && SRC == 0, "the spilling HLG / PQ variants only");
+  static_assert(quad_sgprs<SMODE, SRC>() == 96 && OUT != 0 && MAPFMT != 0 && SMODE != 0 && SRC == 0, "the spilling HLG / PQ variants only");
   apply_quad_body<OUT, MAPFMT, SMODE, BASE, SRC>(p);
 }
 
@@ -1131,7 +1163,7 @@ template <int OUT, int MAPFMT, int SMODE, int BASE>
 hipError_t launch_quad(const ApplyParams& p, hipStream_t s) {
   constexpr int BLK = quad_block<OUT>();
   constexpr bool k80 = quad_sgprs<SMODE, 0>() == 80;
-  constexpr bool kSpills = !k80 && OUT != 0 && MAPFMT != 0 && SMODE == 1;  // see apply_quad_kernel_s96w3
+  constexpr bool kSpills = !k80 && OUT != 0 && MAPFMT != 0 && SMODE != 0;  // see apply_quad_kernel_s96w3
   static const int resident = [] {
     if constexpr (k80) return resident_blocks(apply_quad_kernel<OUT, MAPFMT, SMODE, BASE>, BLK, 80);
     else if constexpr (kSpills) return resident_blocks(apply_quad_kernel_s96w3<OUT, MAPFMT, SMODE, BASE>, BLK, 96);
@@ -1156,7 +1188,7 @@ hipError_t launch_quad(const ApplyParams& p, hipStream_t s) {
   // (0: off).
   static const int pf_env = [] { const char* e = getenv("UHDR_HIP_PREFETCH_WGS"); return e ? atoi(e) : -1; }();
   uint32_t pf = 0;
-  if (BASE == 0 && SMODE == 1 && n_frames == 1 && (size_t)p.sdr.w * p.sdr.h >= (size_t)3840 * 2160 && p.sdr.stride[1] == p.sdr.stride[2] &&
+  if (BASE == 0 && SMODE != 0 && n_frames == 1 && (size_t)p.sdr.w * p.sdr.h >= (size_t)3840 * 2160 && p.sdr.stride[1] == p.sdr.stride[2] &&
       (!p.inputs_hot || pf_env > 0)) {
     // a prefetcher's rate is its CU's miss rate (about one 128-byte line per 7 cycles), so the sweep has to be spread over
     // many CUs to stay ahead of the consumers: 8K, 6 rotating buffer sets: 76 us without, 65 / 62 us with 160 / 320 of 1792
@@ -1211,8 +1243,9 @@ hipError_t launch_quad_coef(const ApplyParams& p, hipStream_t s) {
 // The template ladder of both inputs: SRC 0 planes (launch_quad), 1 coefficients (launch_quad_coef: 4:2:0, 4:4:4 and 4:2:2 bases only)
 template <int SRC, int OUT, int MAPFMT, int BASE>
 hipError_t launch_quad_s(const ApplyParams& p, int smode, hipStream_t s) {
-  if constexpr (SRC == 1) return smode == 0 ? launch_quad_coef<OUT, MAPFMT, 0, BASE>(p, s) : launch_quad_coef<OUT, MAPFMT, 1, BASE>(p, s);
-  else return smode == 0 ? launch_quad<OUT, MAPFMT, 0, BASE>(p, s) : launch_quad<OUT, MAPFMT, 1, BASE>(p, s);
+  if constexpr (SRC == 1)
+    return smode == 0 ? launch_quad_coef<OUT, MAPFMT, 0, BASE>(p, s) : (smode == 1 ? launch_quad_coef<OUT, MAPFMT, 1, BASE>(p, s) : launch_quad_coef<OUT, MAPFMT, 2, BASE>(p, s));
+  else return smode == 0 ? launch_quad<OUT, MAPFMT, 0, BASE>(p, s) : (smode == 1 ? launch_quad<OUT, MAPFMT, 1, BASE>(p, s) : launch_quad<OUT, MAPFMT, 2, BASE>(p, s));
 }
 template <int SRC, int OUT, int BASE>
 hipError_t launch_quad_m(const ApplyParams& p, int mapfmt, int smode, hipStream_t s) {
@@ -1251,7 +1284,16 @@ inline bool aligned_to(const void* ptr, size_t a) { return ((uintptr_t)ptr % a) 
 
 }  // namespace
 
-// Does the quad kernel's layout contract hold?  Returns its SMODE (0 / 1) or -1.
+// Which kernel serves a gamma != 1 at a scale other than 1 when the call brought the threshold tables (p.gamma_thr, which only the
+// _ex entry points set): 0 none of this (no tables, gamma 1, or the quad kernel at scale 1, whose byte -> factor table has the pow
+// folded in), 1 the quad kernel's SMODE 2 (an even scale <= 8, one gamma for the three channels), 2 the generic kernel's table form.
+int apply_gamma_route(const ApplyParams& p) {
+  if (!p.gamma_thr || (p.gamma_is_one[0] && p.gamma_is_one[1] && p.gamma_is_one[2])) return 0;
+  const int smode = apply_quad_mode(p);
+  return smode == 2 ? 1 : (smode < 0 ? 2 : 0);
+}
+
+// Does the quad kernel's layout contract hold?  Returns its SMODE (0 / 1 / 2) or -1.
 int apply_quad_mode(const ApplyParams& p) {
   if (p.resize_on) return -1;  // the resizing sampler exists in the generic kernel only
   const int out = out_index(p), mapfmt = mapfmt_index(p);
@@ -1289,6 +1331,8 @@ int apply_quad_mode(const ApplyParams& p) {
   if (p.scale >= 2 && p.scale % 2 == 0 && p.scale <= (uint32_t)kMaxIdwScaleLds && p.gamma_is_one[0] &&
       p.gamma_is_one[1] && p.gamma_is_one[2])
     return 1;  // gamma != 1 needs pow() per sample: generic kernel
+  // ... unless the call brought the threshold table and the three channels share one gamma
+  if (p.gamma_thr && p.gamma_same && !p.gamma_is_one[0] && !p.resize_on && p.scale >= 2 && p.scale % 2 == 0 && p.scale <= (uint32_t)kMaxIdwScaleLds) return 2;
   return -1;
 }
 
@@ -1312,6 +1356,14 @@ hipError_t launch_apply_gainmap(const ApplyParams& p, hipStream_t s) {
   const size_t total = (size_t)((p.sdr.w + kBlock - 1) / kBlock) * p.sdr.h;  // tiles
   int grid = (int)min(total, (size_t)2048);
   if (grid < 1) grid = 1;
+  if (apply_gamma_route(p) == 2) {  // gamma != 1 at a scale other than 1, through the threshold table
+    switch (out) {
+      case 0: hipLaunchKernelGGL((apply_generic_kernel<0, 1>), dim3(grid), dim3(kBlock), 0, s, p); break;
+      case 1: hipLaunchKernelGGL((apply_generic_kernel<1, 1>), dim3(grid), dim3(kBlock), 0, s, p); break;
+      default: hipLaunchKernelGGL((apply_generic_kernel<2, 1>), dim3(grid), dim3(kBlock), 0, s, p); break;
+    }
+    return hipGetLastError();
+  }
   switch (out) {
     case 0: hipLaunchKernelGGL((apply_generic_kernel<0>), dim3(grid), dim3(kBlock), 0, s, p); break;
     case 1: hipLaunchKernelGGL((apply_generic_kernel<1>), dim3(grid), dim3(kBlock), 0, s, p); break;

@@ -13,7 +13,9 @@
 #include "exact_math.h"
 
 #include <cfloat>
+#include <chrono>
 #include <cmath>
+#include <memory>
 #include <cstring>
 #include <functional>
 #include <mutex>
@@ -321,6 +323,113 @@ const OetfBuckets& oetf_code_buckets(int ct, bool prescaled) {
   static const OetfBuckets hlg = make_bucket_table(UHDR_CT_HLG, false), hlg_pre = make_bucket_table(UHDR_CT_HLG, true);
   static const OetfBuckets pq = make_bucket_table(UHDR_CT_PQ, false), pq_pre = make_bucket_table(UHDR_CT_PQ, true);
   return ct == UHDR_CT_HLG ? (prescaled ? hlg_pre : hlg) : (prescaled ? pq_pre : pq);
+}
+
+// ---- applyGainMap, gamma != 1: the GainLUT index as thresholds over the gain value ----------------------------------------
+// GainLUT::getGainFactor (gainmapmath.h:483-489): gain = pow(gain, mGammaInv) stored to a float, then
+// int(gain * 1023 + 0.5) clipped to 0..1023 -- written below with the casts build_apply_tables uses for the byte -> factor
+// table.  As a function of the gain value it is a staircase with at most 1023 steps, so
+//     index(g) = max{ i : T[i] <= g },   T[i] = the smallest non-negative float whose index is >= i
+// needs no pow on the device.  Several steps can share one float at the low end of a gamma > 1 (then T repeats a value; the
+// max{} form still holds), so this is a plain threshold array, not a bucket table: 2^13 consecutive bit patterns hold up to two
+// steps at gamma 0.25.  The domain ends four ulps above 1.0f (the samplers' weights sum to 1 +- 1 ulp); from T[1023] on every
+// value has index 1023.
+uint32_t gamma_index_direct(float gain, float gamma_inv) {
+  if (gamma_inv != 1.0f) gain = (float)std::pow((double)gain, (double)gamma_inv);
+  int idx = (int)((double)(gain * (float)(kGainN - 1)) + 0.5);
+  return (uint32_t)(idx < 0 ? 0 : (idx > kGainN - 1 ? kGainN - 1 : idx));
+}
+uint32_t gamma_index_lookup(float g, const float* T, float gamma_inv) {
+  // the estimate: what v_log_f32 / v_exp_f32 give the device, here from the float libm.  Only its cost depends on its accuracy.
+  const float e = exp2f(gamma_inv * log2f(g)) * 1023.0f + 0.5f;
+  const uint32_t est = e >= 0.0f ? (e < 1023.0f ? (uint32_t)e : 1023u) : 0u;  // NaN, negative -> 0 (v_cvt_u32_f32 saturates the same way)
+  // T is non-decreasing: with T[est - 1] <= g < T[est + 2] the two inner thresholds settle max{ i : T[i] <= g }
+  const float* q = T + (int)est;
+  uint32_t idx = est + (g >= q[1] ? 1u : 0u) - (g < q[0] ? 1u : 0u);
+  if (!(g >= q[-1] && g < q[2])) {
+    uint32_t lo = 0;
+    for (uint32_t step = 512; step; step >>= 1)
+      if (g >= T[lo + step]) lo += step;
+    idx = lo;
+  }
+  return idx;
+}
+static GammaIndexTable make_gamma_index_table(float gamma_inv) {
+  const auto t0 = std::chrono::steady_clock::now();
+  GammaIndexTable t;
+  t.gamma_inv = gamma_inv;
+  t.thr.assign((size_t)kGammaThrN, INFINITY);
+  float* const T = t.thr.data() + 1;  // T[-1] = 0 in front, T[1024] = T[1025] = +inf behind: the lookup reads T[est - 1 .. est + 2]
+  auto flt = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
+  auto bits_of = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
+  auto idx = [&](uint32_t u) { return gamma_index_direct(flt(u), gamma_inv); };
+  const uint32_t hi = bits_of(1.0f) + 4u;
+  // 0, negative, NaN and infinite gammas: 1 / gamma is then not a positive finite number
+  bool ok = std::isfinite(gamma_inv) && gamma_inv > 0.0f;
+  // both ends of the domain
+  ok = ok && idx(0u) == 0u && idx(bits_of(1.0f)) == (uint32_t)(kGainN - 1) && idx(hi) == (uint32_t)(kGainN - 1);
+  if (ok) {
+    T[-1] = 0.0f;
+    T[0] = 0.0f;
+    const double gamma = 1.0 / (double)gamma_inv;
+    uint32_t prev = 0;  // bits of T[i - 1]
+    for (uint32_t i = 1; i < (uint32_t)kGainN && ok; i++) {
+      // bracket the step from ((i - 0.5) / 1023)^gamma, widening by powers of two: lo has an index below i (or is T[i - 1],
+      // which T[i] cannot undercut), up has one >= i
+      const double guess = std::pow(((double)i - 0.5) / (double)(kGainN - 1), gamma);
+      uint32_t c = bits_of((float)(guess < 0.0 ? 0.0 : (guess > 1.0 ? 1.0 : guess)));
+      c = c < prev ? prev : (c > hi ? hi : c);
+      uint32_t lo = c, up = c;
+      if (idx(c) >= i) {
+        for (uint32_t w = 1; lo > prev; w <<= 1) {
+          lo = lo - prev > w ? lo - w : prev;
+          if (idx(lo) < i) break;
+          up = lo;
+        }
+        if (idx(lo) >= i) { T[i] = flt(lo); prev = lo; continue; }  // lo == prev: the step sits on T[i - 1]
+      } else {
+        for (uint32_t w = 1; up < hi; w <<= 1) {
+          up = hi - up > w ? up + w : hi;
+          if (idx(up) >= i) break;
+          lo = up;
+        }
+        if (idx(up) < i) { ok = false; break; }  // not reached inside the domain
+      }
+      while (up - lo > 1) {  // idx(lo) < i <= idx(up)
+        const uint32_t mid = lo + (up - lo) / 2;
+        if (idx(mid) >= i) up = mid;
+        else lo = mid;
+      }
+      T[i] = flt(up);
+      prev = up;
+    }
+  }
+  // the construction, checked as build_step_table checks its own: the index at every threshold and at its predecessor, the
+  // order of the thresholds, and the lookup procedure at all of these points
+  for (uint32_t i = 1; i < (uint32_t)kGainN && ok; i++) {
+    const uint32_t u = bits_of(T[i]);
+    if (!(T[i] >= T[i - 1]) || u > hi || idx(u) < i) ok = false;
+    if (ok && u > 0 && T[i] > T[i - 1] && idx(u - 1) >= i) ok = false;
+    if (ok && u == 0) ok = false;  // index 0 at g = 0 was checked above
+    if (ok && (gamma_index_lookup(T[i], T, gamma_inv) != idx(u) || gamma_index_lookup(flt(u - 1), T, gamma_inv) != idx(u - 1)))
+      ok = false;
+  }
+  if (ok && (gamma_index_lookup(0.0f, T, gamma_inv) != 0u || gamma_index_lookup(flt(hi), T, gamma_inv) != (uint32_t)(kGainN - 1))) ok = false;
+  t.exact = ok;
+  if (!ok) t.thr.assign((size_t)kGammaThrN, INFINITY);
+  t.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return t;
+}
+const GammaIndexTable& gamma_index_table(float gamma_inv) {
+  static std::mutex mu;
+  static std::vector<std::unique_ptr<GammaIndexTable>> cache;  // one per distinct 1 / gamma (bit pattern), for the life of the process
+  std::lock_guard<std::mutex> lk(mu);
+  for (const auto& e : cache)
+    if (!memcmp(&e->gamma_inv, &gamma_inv, 4)) return *e;
+  static const GammaIndexTable none;  // exact = false
+  if (cache.size() >= 256) return none;  // references stay valid: nothing is ever evicted; past 256 gammas a process keeps the pow route
+  cache.push_back(std::make_unique<GammaIndexTable>(make_gamma_index_table(gamma_inv)));
+  return *cache.back();
 }
 
 // ---- step tables of the ENCODE side ------------------------------------------------------------------------------------

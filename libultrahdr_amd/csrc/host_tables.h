@@ -33,6 +33,21 @@ struct OetfBuckets {
 };
 OetfBuckets build_step_table(const std::function<uint32_t(uint32_t)>& code_of_bits, uint32_t lo_bits, uint32_t hi_bits, uint32_t shift, uint32_t capacity);
 const OetfBuckets& oetf_code_buckets(int ct, bool prescaled = false);  // prescaled: argument is the value before (x * 203) / peak
+// applyGainMap with gamma != 1: GainLUT::getGainFactor's table index (gainmapmath.h:483-489) as thresholds over the gain value
+// (see host_tables.cpp).  One table per distinct 1 / gamma, built once per process.
+struct GammaIndexTable {
+  float gamma_inv = 0.0f;
+  bool exact = false;          // construction verified; false: no table for this gamma, the caller keeps the pow per sample
+  double build_ms = 0.0;       // host time of the construction, checks included
+  // kGammaThrN floats, T[i] at thr[1 + i]: T[-1] = 0 (read, never decisive), T[0] = 0, T[i] the smallest float whose index is >= i,
+  // T[1024] = T[1025] = +inf
+  std::vector<float> thr;
+};
+uint32_t gamma_index_direct(float gain, float gamma_inv);  // the reference's expression itself, with the host libm
+const GammaIndexTable& gamma_index_table(float gamma_inv);
+// the device's lookup (apply_gainmap.hip: gain_index) restated on the host: an estimate from float log2 / exp2, settled and
+// confirmed on two adjacent thresholds, else a binary search over T
+uint32_t gamma_index_lookup(float gain, const float* T, float gamma_inv);  // T = thr.data() + 1
 // encode side (see host_tables.cpp): toneMap's sRGB byte, encodeGain's byte, RGBA1010102 code -> linear value
 const OetfBuckets& srgb_code8_buckets();
 OetfBuckets gain_code8_buckets(float min_boost, float max_boost, float log2min, double log2_range, double log2_range_rcp);

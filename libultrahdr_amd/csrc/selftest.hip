@@ -8,8 +8,11 @@
 //      index) == srgb_oetf_table (round-1 form: nearest-of-65 table, degree 5) for every float in [0, 1]
 //   4  the device-built ratio -> byte step table of two-pass generation against the per-sample evaluation, for a given
 //      (min, max) range: every bit pattern of the table's domain and a margin on both sides (generate_gainmap.hip)
+//   5  the GainLUT index of a gamma != 1 (gain_index.h): the estimate-and-settle lookup against the binary search over the
+//      same host-built thresholds, for every float from 0 to a few ulps past the last threshold
 #include "cu_count.h"
 #include "encode_core.h"
+#include "gain_index.h"
 
 namespace uhdr {
 namespace {
@@ -110,6 +113,27 @@ __global__ __launch_bounds__(256) void sweep_affine(unsigned long long* out, con
   if (blockIdx.x == 0 && threadIdx.x == 0) { out[1] = last - first + 1; out[2] = td.n; }
 }
 
+// thr: one channel's kGammaThrN-float block (T[i] at [1 + i]); last: the bit pattern the sweep ends at
+__global__ __launch_bounds__(256) void sweep_gain_index(unsigned long long* out, const float* thr, uint32_t ginv_bits, uint32_t last) {
+  const float ginv = __uint_as_float(ginv_bits);
+  __shared__ float s_thr[kGammaThrN];
+  for (uint32_t i = threadIdx.x; i < (uint32_t)kGammaThrN; i += 256) s_thr[i] = thr[i];
+  __syncthreads();
+  const float* T = s_thr + 1;
+  unsigned long long bad = 0, searched = 0;
+  const uint64_t n = ((uint64_t)last + 256) & ~(uint64_t)255;  // whole waves: the lookup's ballot wants every lane of a wave in the loop
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const float g = __uint_as_float((uint32_t)(i <= last ? i : last));
+    bool ok;
+    (void)gain_index_try(g, T, ginv, ok);
+    if (!ok) searched++;
+    if (gain_index(g, T, ginv) != gain_index_search(g, T)) bad++;
+  }
+  atomicAdd(&out[0], bad);
+  atomicAdd(&out[2], searched);
+  if (blockIdx.x == 0 && threadIdx.x == 0) out[1] = (unsigned long long)last + 1;
+}
+
 }  // namespace
 
 // out: 8 zero-initialised device words.  which 4: dev = the AffineDev + tables to check (built by launch_minmax_table), arg0 = channel
@@ -122,6 +146,7 @@ hipError_t launch_selftest(int which, unsigned long long* out, uint32_t arg0, ui
     case 2: hipLaunchKernelGGL(sweep_div, grid, block, 0, s, out, seed, arg0, arg1); break;
     case 3: hipLaunchKernelGGL(sweep_srgb, grid, block, 0, s, out, math_tab); break;
     case 4: hipLaunchKernelGGL(sweep_affine, grid, block, 0, s, out, dev, (int)arg0, math_tab); break;
+    case 5: hipLaunchKernelGGL(sweep_gain_index, grid, block, 0, s, out, (const float*)dev, arg0, arg1); break;  // dev: the threshold block
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();

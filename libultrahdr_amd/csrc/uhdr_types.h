@@ -52,6 +52,10 @@ struct StepTab {
   uint32_t lo_bits, hi_bits;  // the device's clamp; lo_bits >= base8 << shm3, so bucket * 8 - base8 cannot underflow
 };
 constexpr int kMaxIdwScaleLds = 8;  // idw tables up to 4*8*8*4 floats = 4 KiB live in LDS
+// applyGainMap, gamma != 1 at a map scale other than 1: GainLUT::getGainFactor's index int(pow(g, 1 / gamma) * 1023 + 0.5)
+// (gainmapmath.h:483-489) as a step function of g -- thresholds T[0..1024] per channel, T[i] the smallest float whose index is
+// >= i, T[0] = 0, T[1024] = +inf (host_tables.cpp: gamma_index_table); padded to a multiple of four floats for 16-byte copies
+constexpr int kGammaThrN = 1028;
 
 struct ApplyTables {  // layout of the device table block, in floats
   static constexpr int kSrgbOff = 0;
@@ -127,6 +131,11 @@ struct ApplyParams {
   int resize_on;
   double resize_sx, resize_sy;
   FramePtrs frame_tab[kMaxBatchFrames];  // batch: plane pointers of the launch's frames, read with scalar loads from the kernel arguments
+  // gamma != 1 through the threshold table (UHDR_HIP_APPLY_GAMMA_TABLE; behind the frame table, so no older field moves): the three
+  // channels' tables, kGammaThrN floats each, or null -- the kernels then keep the pow per sample.  gamma_same: one table serves all
+  // three channels (what the quad kernel requires)
+  const float* gamma_thr;
+  int gamma_same;
 };
 
 // ---- generateGainMap -----------------------------------------------------------------------------
@@ -254,6 +263,7 @@ struct RgbToYcbcrParams {
 hipError_t launch_apply_gainmap(const ApplyParams& p, hipStream_t s);
 hipError_t launch_apply_gainmap_coef(const ApplyParams& p, hipStream_t s);
 int apply_quad_mode(const ApplyParams& p);  // >= 0: the quad kernel (and batch mode) applies
+int apply_gamma_route(const ApplyParams& p);  // gamma != 1 through the threshold table: 0 no, 1 the quad kernel, 2 the generic kernel
 hipError_t launch_generate_gainmap(const GenParams& p, bool two_pass, hipStream_t s);
 // generate_coef.hip: pass 1 / the one-pass generation with the SDR intent as the coefficient blocks of a 4:2:0, 4:2:2 or 4:4:4 JPEG
 // (sampling 420 / 422 / 444); p.sdr carries the decoded image's geometry only.  gen_coef_partials_count: the workgroups (= partials) of

@@ -541,6 +541,16 @@ class UltraHdr:
                    C.byref(map_hdr), C.c_void_p(map_data.data_ptr()), int(map_data.numel()), map_cg, libjpeg_variant, C.byref(gainmap_metadata), output_ct, output_format,
                    max_display_boost, C.byref(dest.raw))
 
+    def decodeApi1ScansEx(self, base_hdr: "A.JpegHeader", base_data, base_cg: int, map_hdr: "A.JpegHeader", map_data, map_cg: int,
+                          gainmap_metadata: A.GainmapMetadata, output_ct: int, output_format: int, max_display_boost: float, dest: Image,
+                          apply_flags: int, libjpeg_variant: int = 0):
+        """decodeApi1ScansAny whose applyGainMap stage runs with applyGainMapEx's flags (uhdr_hip_decode_api1_scans_ex_dev): with
+        A.UHDR_HIP_APPLY_GAMMA_TABLE a file whose gain-map gamma is not 1 (gainmapmath.h:483-489) keeps the fused route."""
+        assert base_data.is_cuda and map_data.is_cuda and _is_dev(dest)
+        self._call(True, self.lib.uhdr_hip_decode_api1_scans_ex_dev, self.ctx.handle, C.byref(base_hdr), C.c_void_p(base_data.data_ptr()), int(base_data.numel()), base_cg,
+                   C.byref(map_hdr), C.c_void_p(map_data.data_ptr()), int(map_data.numel()), map_cg, libjpeg_variant, C.byref(gainmap_metadata), output_ct, output_format,
+                   max_display_boost, C.byref(dest.raw), apply_flags)
+
     # ---- applyGainMap (ultrahdrcommon.h:531-534) -----------------------------------------------
     def applyGainMap(self, sdr_intent: Image, gainmap_img: Image, gainmap_metadata: A.GainmapMetadata,
                      output_ct: int, output_format: int, max_display_boost: float, dest: Image,
@@ -572,6 +582,24 @@ class UltraHdr:
             A.check(self.lib.uhdr_hip_apply_gainmap_any(
                 self.ctx.handle, C.byref(sdr_intent.raw), C.byref(gainmap_img.raw), C.byref(gainmap_metadata),
                 output_ct, output_format, max_display_boost, C.byref(dest.raw)))
+
+    def applyGainMapEx(self, sdr_intent: Image, gainmap_img: Image, gainmap_metadata: A.GainmapMetadata,
+                       output_ct: int, output_format: int, max_display_boost: float, dest: Image,
+                       flags: int, y0: int = 0, full_height: int = 0):
+        """applyGainMap with flags (uhdr_hip_apply_gainmap_ex / _ex_dev): 0 is applyGainMap, A.UHDR_HIP_APPLY_RESIZED_MAP is
+        applyGainMapAny, A.UHDR_HIP_APPLY_GAMMA_TABLE evaluates a gain-map gamma other than 1 at a map scale other than 1
+        through host-built thresholds of GainLUT::getGainFactor's table index (gainmapmath.h:483-489) instead of a pow per
+        sample: the reference's bits, and the 2x2-quad kernel where its geometry holds."""
+        if _is_dev(sdr_intent, gainmap_img, dest):
+            self._call(True, self.lib.uhdr_hip_apply_gainmap_ex_dev,
+                       self.ctx.handle, C.byref(sdr_intent.raw), C.byref(gainmap_img.raw), C.byref(gainmap_metadata),
+                       output_ct, output_format, max_display_boost, C.byref(dest.raw), y0, full_height, flags)
+        else:
+            if y0 or full_height:
+                raise ValueError("stripes are a device-buffer feature")
+            A.check(self.lib.uhdr_hip_apply_gainmap_ex(
+                self.ctx.handle, C.byref(sdr_intent.raw), C.byref(gainmap_img.raw), C.byref(gainmap_metadata),
+                output_ct, output_format, max_display_boost, C.byref(dest.raw), flags))
 
     def resizeImage(self, src: Image, dst_w: int, dst_h: int, dst: Image = None, y0: int = 0, full_height: int = 0) -> Image:
         """resize_image (editorhelper.cpp:88-146) of a Y400 / RGB888 / RGBA8888 image to dst_w x dst_h.  dst: a caller-made
@@ -620,6 +648,24 @@ class UltraHdr:
                 jc.qtable[i][k] = int(qtables[i][k])
         self._call(True, self.lib.uhdr_hip_apply_gainmap_coef444_dev, self.ctx.handle, C.byref(jc), w, h, base_cg, C.byref(gainmap_img.raw),
                    C.byref(gainmap_metadata), output_ct, output_format, max_display_boost, C.byref(dest.raw))
+
+    def applyGainMapFromCoefficientsEx(self, coefs, qtables, w: int, h: int, base_cg: int, gainmap_img: Image,
+                                       gainmap_metadata: A.GainmapMetadata, output_ct: int, output_format: int,
+                                       max_display_boost: float, dest: Image, sampling: str, flags: int):
+        """applyGainMapFromCoefficients / 444 behind one call with applyGainMapEx's flags (uhdr_hip_apply_gainmap_coef_ex_dev):
+        sampling "420", "422" or "444".  With A.UHDR_HIP_APPLY_GAMMA_TABLE a gamma other than 1 (gainmapmath.h:483-489) at an
+        even map scale <= 8 stays on the coefficient kernel; == idct_dequant x 3 + applyGainMapEx, bit for bit."""
+        assert all(c.is_cuda for c in coefs) and _is_dev(gainmap_img, dest)
+        if sampling not in ("420", "422", "444"):
+            raise ValueError(f"sampling is '420', '422' or '444', received {sampling!r}")
+        jc = A.JpegCoefficients()
+        for i in range(3):
+            jc.coef[i] = coefs[i].data_ptr()
+            jc.blocks_h[i], jc.blocks_w[i] = int(coefs[i].shape[0]), int(coefs[i].shape[1])
+            for k in range(64):
+                jc.qtable[i][k] = int(qtables[i][k])
+        self._call(True, self.lib.uhdr_hip_apply_gainmap_coef_ex_dev, self.ctx.handle, C.byref(jc), int(sampling), w, h, base_cg, C.byref(gainmap_img.raw),
+                   C.byref(gainmap_metadata), output_ct, output_format, max_display_boost, C.byref(dest.raw), flags)
 
     def applyGainMapBatch(self, sdr_intents, gainmap_imgs, gainmap_metadata: A.GainmapMetadata, output_ct: int,
                           output_format: int, max_display_boost: float, dests):
