@@ -256,7 +256,12 @@ bool generate_gainmap(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* hdr_intent
     // map straight to compressGainMap, jpegr.cpp:211-217, 253-257, 316-320, 377-381), and the previous state comes back afterwards
     const bool was = tl_lazy_now;
     if (tl_lazy_ok) uhdr_hip_resident_lazy(cur(), 1);
-    *st = uhdr_hip_generate_gainmap(cur(), sdr_intent, hdr_intent, &cfg, &md, img.get());
+    // UHDR_HIP_SEAM_GAMMA_ENCODE: a gain-map gamma other than 1 is evaluated through the library's byte thresholds
+    // (gainmapmath.cpp:769-770, 784-789; uhdr_hip_generate_gainmap_ex) -- the reference's bytes, where the call below uses the device's pow
+    if (getenv("UHDR_HIP_SEAM_GAMMA_ENCODE"))
+      *st = uhdr_hip_generate_gainmap_ex(cur(), sdr_intent, hdr_intent, &cfg, &md, img.get(), UHDR_HIP_GENERATE_GAMMA_TABLE);
+    else
+      *st = uhdr_hip_generate_gainmap(cur(), sdr_intent, hdr_intent, &cfg, &md, img.get());
     uhdr_hip_resident_lazy(cur(), was ? 1 : 0);
     if (!handled(*st, "generate_gainmap")) return false;
     if (st->error_code == UHDR_CODEC_OK) {
@@ -290,6 +295,11 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
   // launches (tools/api1_onepass_time.py, profiles/README.md)
   const bool realtime = preset == UHDR_USAGE_REALTIME && getenv("UHDR_HIP_SEAM_FUSED_REALTIME") != nullptr;
   if (realtime && *scale_factor != 1) return false;
+  // a gain-map gamma other than 1 takes the fused route only when asked to: UHDR_HIP_SEAM_GAMMA_ENCODE hands it to
+  // uhdr_hip_encode_api1_scans_ex with the threshold tables; without it the entry points below decline it and the per-stage seams run as
+  // before.  (That entry point takes the one-pass preset as well: the condition above stays what decides that.)
+  const bool gamma_ex = gamma != 1.0f && getenv("UHDR_HIP_SEAM_GAMMA_ENCODE") != nullptr;
+  if (gamma_ex && preset == UHDR_USAGE_REALTIME && !realtime) return false;
   const unsigned w = sdr_intent->w, h = sdr_intent->h;
   const int s = *scale_factor;
   const unsigned grid = rgba ? 8 : 16;  // whole MCUs: 1x1 / 1x1 / 1x1 sampling for RGBA8888, 2x2 / 1x1 / 1x1 otherwise
@@ -353,9 +363,14 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
     out->gainmap_data.reset(new (std::nothrow) unsigned char[lead_m + cap_m + 2]);
     if (!out->base_data || !out->gainmap_data) return false;
     nb = nm = 0;
-    *st = (realtime ? uhdr_hip_encode_api1_scans_onepass : rgba ? uhdr_hip_encode_api1_scans_any : uhdr_hip_encode_api1_scans)(
-        cur(), sdr_intent, hdr_intent, &cfg, UHDR_CG_DISPLAY_P3, qt_base, qt_map, &md, &gm_desc, out->base_data.get() + lead_b, cap_b, &nb,
-        out->gainmap_data.get() + lead_m, cap_m, &nm);
+    if (gamma_ex)
+      *st = uhdr_hip_encode_api1_scans_ex(cur(), sdr_intent, hdr_intent, &cfg, UHDR_CG_DISPLAY_P3, qt_base, qt_map, &md, &gm_desc,
+                                          out->base_data.get() + lead_b, cap_b, &nb, out->gainmap_data.get() + lead_m, cap_m, &nm,
+                                          UHDR_HIP_GENERATE_GAMMA_TABLE);
+    else
+      *st = (realtime ? uhdr_hip_encode_api1_scans_onepass : rgba ? uhdr_hip_encode_api1_scans_any : uhdr_hip_encode_api1_scans)(
+          cur(), sdr_intent, hdr_intent, &cfg, UHDR_CG_DISPLAY_P3, qt_base, qt_map, &md, &gm_desc, out->base_data.get() + lead_b, cap_b, &nb,
+          out->gainmap_data.get() + lead_m, cap_m, &nm);
     // a stream busier than the first guess: the encoder reports the size it needs -- once more with room for that (the device chain is ~1 ms at 4K;
     // the per-stage seams this used to fall to carry every intermediate over PCIe).  Any other MEM_ERROR (a device allocation) has no such sizes.
     if (st->error_code == UHDR_CODEC_MEM_ERROR && attempt == 0 && (nb > cap_b || nm > cap_m)) {

@@ -291,6 +291,32 @@ uhdr_error_info_t uhdr_hip_generate_gainmap_pass2_dev(uhdr_hip_ctx_t* ctx,
                                                       const float minmax[6],
                                                       const uhdr_hip_encode_cfg_t* cfg,
                                                       uhdr_raw_image_t* gainmap_img);
+/* generateGainMap with flags: uhdr_hip_generate_gainmap, uhdr_hip_generate_gainmap_dev and uhdr_hip_generate_gainmap_pass2_dev plus
+ * `flags`; 0 is the sibling, unknown bits are UHDR_CODEC_INVALID_PARAM.
+ * UHDR_HIP_GENERATE_GAMMA_TABLE: a gain-map gamma other than 1 without a pow per sample.  encodeGain's powf and truncation
+ * (gainmapmath.cpp:769-770) and affineMapGain's pow, rounding and clip (gainmapmath.cpp:784-789) are monotone step functions of one
+ * float; the host builds their 255 thresholds once per gamma with its own libm and checks both sides of every step
+ * (uhdr_hip_gamma_code_eval).  One pass: the gain -> byte step table that gamma 1 has is built for the gamma too.  Two pass: the
+ * per-channel ratio -> byte tables are built on the device from the thresholds, pass 2 is the table lookup it is at gamma 1; a channel
+ * whose range is too dense for a table (uhdr_hip_get_stats: generate_channels_per_sample) is evaluated per sample through an
+ * eight-step search over the thresholds.  The bytes are the reference's, where the sibling's device pow is within one map code of
+ * them.  A gamma of 1, and a gamma without a verified table, make the call its sibling.  A context keeps the thresholds of 16 distinct
+ * gammas (and 16 one-pass step tables); a call with a seventeenth gamma is its sibling as well -- the device's pow, within one map code --
+ * and uhdr_hip_encode_api1_scans_ex answers UHDR_CODEC_UNSUPPORTED_FEATURE for it before the intents are uploaded.  An even-integer gamma
+ * (2, 4, ...) never gets a two-pass bucket table (pow is even there, the byte function is not saturated below the range): its two-pass
+ * maps are always searched per sample, like every two-pass map at a gamma whose thresholds lie closer than a bucket (0.5). */
+#define UHDR_HIP_GENERATE_GAMMA_TABLE 0x1u
+uhdr_error_info_t uhdr_hip_generate_gainmap_ex(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr_intent,
+                                               const uhdr_raw_image_t* hdr_intent, const uhdr_hip_encode_cfg_t* cfg,
+                                               uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_raw_image_t* gainmap_img,
+                                               unsigned int flags);
+uhdr_error_info_t uhdr_hip_generate_gainmap_ex_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr_intent,
+                                                   const uhdr_raw_image_t* hdr_intent, const uhdr_hip_encode_cfg_t* cfg,
+                                                   uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_raw_image_t* gainmap_img,
+                                                   unsigned int flags);
+uhdr_error_info_t uhdr_hip_generate_gainmap_pass2_ex_dev(uhdr_hip_ctx_t* ctx, const float* gain_log2_dev, const float minmax[6],
+                                                         const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* gainmap_img,
+                                                         unsigned int flags);
 /* ---- multi-GPU: one process per GPU, images sharded by row stripe -----------------------------
  * Every stage of the path is stripe-local except two-pass generateGainMap's per-channel min / max merge
  * (jpegr.cpp:932-938).  uhdr_hip_generate_gainmap_striped_dev runs the whole two-pass sequence on this rank's stripe:
@@ -398,6 +424,13 @@ int uhdr_hip_exact_math_eval(int fn, const float* in, float* out, size_t n);
  *   which 5: the GainLUT index of gain-map gamma mm[0] (gainmapmath.h:483-489, UHDR_HIP_APPLY_GAMMA_TABLE): the kernels' estimate-and-settle
  *            lookup against the binary search over the same host-built thresholds, every float from 0 to eight ulps past the last threshold
  *                                                                                      out = {mismatches, floats swept, lanes whose estimate needed the search, 1 if the gamma got no table}
+ *   which 6: the map byte of gain-map gamma mm[0] through the thresholds of UHDR_HIP_GENERATE_GAMMA_TABLE (csrc/gamma_code.h), form arg0 (0 one
+ *            pass, 1 two pass): for every float from eight ulps below zero to eight ulps past the last threshold the code lies between its
+ *            thresholds, T[code] <= v < T[code + 1] (a negative float: code 0, or for an even-integer gamma the code of its magnitude)
+ *                                                                                      out = {violations, floats swept, lanes that ran the search (all: there is no estimate), 1 if the gamma got no table}
+ *   which 7: which 4 for the gamma whose bit pattern is `seed`: the table the device builds from the gamma's two-pass thresholds against the
+ *            per-sample evaluation that ends in the threshold search, over the table's whole domain and 2^20 bit patterns beyond either end
+ *                                                                                      out = {mismatches, ratios swept, table entries, 1 if the range or the gamma got no table}
  * The reference has no counterpart: these pin the arithmetic of jpegr.cpp:753-1013, 1945-1983 and gainmapmath.cpp:127-148 as evaluated here. */
 uhdr_error_info_t uhdr_hip_selftest(uhdr_hip_ctx_t* ctx, int which, unsigned int arg0, unsigned int arg1, unsigned int seed, const float mm[6],
                                     unsigned long long out[8]);
@@ -420,6 +453,16 @@ int uhdr_hip_step_table_eval(int which, float a, float b, const float* in, uint3
  * NULL with n = 0.  Returns 0; 1 when this gamma has no verified table (0, negative, NaN, infinite, non-monotone: the kernels then keep
  * the pow per sample) -- out and thresholds are then untouched. */
 int uhdr_hip_gamma_index_eval(float gamma, const float* in, uint32_t* out, size_t n, uint32_t info[4], float* thresholds);
+/* Host utility (no GPU needed): the map byte of generateGainMap for a gain-map gamma other than 1 through the threshold tables of
+ * UHDR_HIP_GENERATE_GAMMA_TABLE, by the device's lookup (csrc/gamma_code.h) restated on the host.
+ *   form 0 (one pass,  gainmapmath.cpp:769-770): (uint8_t)(powf(x, gamma) * 255.0f), for x up to four ulps past 1.0f
+ *   form 1 (two pass,  gainmapmath.cpp:784-789): x = (float)pow((double)x, (double)gamma); clip(x * 255 + 0.5, 0, 255), any finite x
+ * A negative x gives 0 in both forms, as the reference's conversion of pow's NaN does.  info (may be NULL) receives {verified exact,
+ * thresholds (256), microseconds the table's construction took, the smallest distance between two thresholds of this form in ulps};
+ * thresholds (may be NULL) receives T[0..255] (T[k]: the smallest float whose byte is >= k; T[0] = 0); in / out may be NULL with n = 0.
+ * Returns 0; 1 when this gamma has no verified table (0, negative, NaN, infinite, non-monotone: the kernels then keep the pow per
+ * sample) -- out and thresholds are then untouched; -1 for an unknown form. */
+int uhdr_hip_gamma_code_eval(float gamma, int form, const float* in, uint32_t* out, size_t n, uint32_t info[4], float* thresholds);
 /* islow 8x8 FDCT + quantize of one 8-bit plane.  Reads blocks_w*8 x blocks_h*8 samples (the
  * caller pads to the MCU grid exactly as jpegencoderhelper.cpp:246-309 does); writes blocks in
  * raster order, 64 int16 each in natural order = libjpeg's JBLOCK layout, ready for
@@ -980,6 +1023,25 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans_onepass_dev(uhdr_hip_ctx_t* ctx, co
                                                          uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
                                                          uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
                                                          uint8_t* map_scan, size_t map_capacity, size_t* map_bytes);
+/* uhdr_hip_encode_api1_scans_onepass / _onepass_dev with generateGainMap's flags (uhdr_hip_generate_gainmap_ex): 0 is the sibling, unknown
+ * bits are UHDR_CODEC_INVALID_PARAM.  With UHDR_HIP_GENERATE_GAMMA_TABLE a gain-map gamma other than 1 keeps the fused chain, both presets,
+ * both SDR intents: the one-pass kernel reads the gain -> byte step table built for the gamma, the range kernel builds the two-pass ratio ->
+ * byte tables from the gamma's thresholds, and the map kernel's per-sample tail (a range too dense for tables) searches the thresholds.
+ * Scans, map and metadata are bit-identical to uhdr_hip_generate_gainmap_ex_dev with the same flag + uhdr_hip_fdct_quant_dev / _rgb_dev +
+ * uhdr_hip_huffman_encode_dev.  A gamma without a verified threshold table (uhdr_hip_gamma_code_eval) is UHDR_CODEC_UNSUPPORTED_FEATURE
+ * before anything is uploaded; every other fused encode entry point keeps refusing gamma != 1. */
+uhdr_error_info_t uhdr_hip_encode_api1_scans_ex(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
+                                                uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned int flags);
+uhdr_error_info_t uhdr_hip_encode_api1_scans_ex_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                    const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                    const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                    uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                    uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
+                                                    uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned int flags);
 
 /* JpegR::encodeJPEGR API-0 (lib/src/jpegr.cpp:179-244) for the HDR intents whose tone-mapped rendition is RGBA8888 -- RGBA1010102 and RGBA
  * half float -- in ONE call (round 6): host intent in, the two entropy-coded scans out (host buffers).  uhdr_hip_encode_api0_fused_dev (tone

@@ -82,6 +82,15 @@ class UltraHdr {
   uhdr_error_info_t generateGainMap(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* hdr_intent,
                                     uhdr_gainmap_metadata_t* gainmap_metadata, std::unique_ptr<raw_image_ext>& gainmap_img,
                                     bool sdr_is_601 = false, bool use_luminance = true) {
+    return generateGainMapEx(sdr_intent, hdr_intent, gainmap_metadata, gainmap_img, 0u, sdr_is_601, use_luminance);
+  }
+
+  // generateGainMap with flags: 0 is uhdr_hip_generate_gainmap, anything else goes to uhdr_hip_generate_gainmap_ex --
+  // UHDR_HIP_GENERATE_GAMMA_TABLE runs a gain-map gamma other than 1 through the host-built byte thresholds instead of a pow per sample
+  // (gainmapmath.cpp:769-770, 784-789): the reference's bytes.
+  uhdr_error_info_t generateGainMapEx(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* hdr_intent, uhdr_gainmap_metadata_t* gainmap_metadata,
+                                      std::unique_ptr<raw_image_ext>& gainmap_img, unsigned int flags, bool sdr_is_601 = false,
+                                      bool use_luminance = true) {
     if (!mCtx) return mCreateStatus;
     if (!sdr_intent || !hdr_intent || !gainmap_metadata) return bad("received nullptr argument");
     uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
@@ -98,7 +107,8 @@ class UltraHdr {
     }
     gainmap_img = std::make_unique<raw_image_ext>(mUseMultiChannelGainMap ? UHDR_IMG_FMT_24bppRGB888 : UHDR_IMG_FMT_8bppYCbCr400,
                                                   hdr_intent->cg, hdr_intent->ct, hdr_intent->range, mw, mh, 64);
-    return uhdr_hip_generate_gainmap(mCtx, sdr_intent, hdr_intent, &cfg, gainmap_metadata, gainmap_img.get());
+    if (flags == 0u) return uhdr_hip_generate_gainmap(mCtx, sdr_intent, hdr_intent, &cfg, gainmap_metadata, gainmap_img.get());
+    return uhdr_hip_generate_gainmap_ex(mCtx, sdr_intent, hdr_intent, &cfg, gainmap_metadata, gainmap_img.get(), flags);
   }
 
   uhdr_error_info_t applyGainMap(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* gainmap_img,
@@ -298,6 +308,20 @@ class UltraHdr {
     return (dev ? uhdr_hip_encode_api1_scans_onepass_dev : uhdr_hip_encode_api1_scans_onepass)(mCtx, sdr_intent, hdr_intent, &cfg, base_encoding, qt_base,
                                                                                                qt_map, gainmap_metadata, gainmap_desc, base_scan,
                                                                                                base_capacity, base_bytes, map_scan, map_capacity, map_bytes);
+  }
+  // encodeApi1ScansOnePass with generateGainMap's flags (uhdr_hip_encode_api1_scans_ex / _ex_dev): with UHDR_HIP_GENERATE_GAMMA_TABLE a gain-map
+  // gamma other than 1 keeps the fused chain, both presets; flags 0 is encodeApi1ScansOnePass.
+  uhdr_error_info_t encodeApi1ScansEx(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* hdr_intent, uhdr_color_gamut_t base_encoding,
+                                      const uint16_t qt_base[2][64], const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* gainmap_metadata,
+                                      uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
+                                      uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned int flags, bool dev = false,
+                                      bool sdr_is_601 = false, bool use_luminance = true) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, sdr_is_601 ? 1 : 0, use_luminance ? 1 : 0};
+    return (dev ? uhdr_hip_encode_api1_scans_ex_dev : uhdr_hip_encode_api1_scans_ex)(mCtx, sdr_intent, hdr_intent, &cfg, base_encoding, qt_base, qt_map,
+                                                                                     gainmap_metadata, gainmap_desc, base_scan, base_capacity, base_bytes,
+                                                                                     map_scan, map_capacity, map_bytes, flags);
   }
 
   // generateGainMap on an SDR intent still in coefficient form -- the compressed intent of an API-3 encode after its Huffman decode (device

@@ -42,6 +42,8 @@ FLT_MIN = 1.1754943508222875e-38
 FLT_MAX = 3.4028234663852886e38
 # applyGainMap flags (uhdr_hip_apply_gainmap_ex and its siblings)
 UHDR_HIP_APPLY_RESIZED_MAP, UHDR_HIP_APPLY_GAMMA_TABLE = 0x1, 0x2
+# generateGainMap flags (uhdr_hip_generate_gainmap_ex and its siblings)
+UHDR_HIP_GENERATE_GAMMA_TABLE = 0x1
 
 
 class ErrorInfo(C.Structure):  # uhdr_error_info_t
@@ -209,6 +211,9 @@ _SIGS = {
     "uhdr_hip_generate_gainmap_pass1_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(EncodeCfg), C.c_void_p, C.c_void_p, _P(C.c_int)]),
     "uhdr_hip_generate_gainmap_finalize": (ErrorInfo, [_P(EncodeCfg), C.c_int, C.c_int, _P(C.c_float), _P(GainmapMetadata)]),
     "uhdr_hip_generate_gainmap_pass2_dev": (ErrorInfo, [C.c_void_p, C.c_void_p, _P(C.c_float), _P(EncodeCfg), _P(RawImage)]),
+    "uhdr_hip_generate_gainmap_ex": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(EncodeCfg), _P(GainmapMetadata), _P(RawImage), C.c_uint]),
+    "uhdr_hip_generate_gainmap_ex_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(EncodeCfg), _P(GainmapMetadata), _P(RawImage), C.c_uint]),
+    "uhdr_hip_generate_gainmap_pass2_ex_dev": (ErrorInfo, [C.c_void_p, C.c_void_p, _P(C.c_float), _P(EncodeCfg), _P(RawImage), C.c_uint]),
     "uhdr_hip_tone_map": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage)]),
     "uhdr_hip_tone_map_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage)]),
     "uhdr_hip_convert_yuv": (ErrorInfo, [C.c_void_p, _P(RawImage), C.c_int, C.c_int]),
@@ -232,6 +237,10 @@ _SIGS = {
                                                        _P(RawImage), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "uhdr_hip_encode_api1_scans_onepass_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(EncodeCfg), C.c_int, C.c_void_p, C.c_void_p, _P(GainmapMetadata),
                                                            _P(RawImage), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
+    "uhdr_hip_encode_api1_scans_ex": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(EncodeCfg), C.c_int, C.c_void_p, C.c_void_p, _P(GainmapMetadata),
+                                                  _P(RawImage), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_uint]),
+    "uhdr_hip_encode_api1_scans_ex_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(EncodeCfg), C.c_int, C.c_void_p, C.c_void_p, _P(GainmapMetadata),
+                                                      _P(RawImage), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_uint]),
     "uhdr_hip_huffman_encode2_dev": (ErrorInfo, [C.c_void_p, _P(JpegScan), C.c_void_p, C.c_size_t, _P(C.c_size_t), _P(JpegScan), C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "uhdr_hip_huffman_decode2_dev": (ErrorInfo, [C.c_void_p, _P(JpegScan), _P(HuffTables), C.c_void_p, C.c_size_t, _P(JpegScan), _P(HuffTables), C.c_void_p, C.c_size_t]),
     "uhdr_hip_encode_api1_scans": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(EncodeCfg), C.c_int, C.c_void_p, C.c_void_p, _P(GainmapMetadata),
@@ -305,6 +314,7 @@ _SIGS = {
     "uhdr_hip_apply_effect_dev": (ErrorInfo, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(RawImage), _P(RawImage)]),
     "uhdr_hip_step_table_eval": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uhdr_hip_gamma_index_eval": (C.c_int, [C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "uhdr_hip_gamma_code_eval": (C.c_int, [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "uhdr_hip_comm_unique_id": (C.c_int, [C.c_void_p]),
     "uhdr_hip_comm_init": (ErrorInfo, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "uhdr_hip_comm_destroy": (None, [C.c_void_p]),

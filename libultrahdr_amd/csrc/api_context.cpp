@@ -441,18 +441,35 @@ uhdr_error_info_t upload_step_table(const host::OetfBuckets& b, float** slot, St
   return ok_status();
 }
 // encodeGain's byte for the clamped gain (one pass, gamma 1), cached per boost range
-uhdr_error_info_t gain_step_table(uhdr_hip_ctx* c, const GenParams& p, StepTab* out) {
+// gamma_table (UHDR_HIP_GENERATE_GAMMA_TABLE): a gamma != 1 gets its table too, keyed by (min boost, max boost, gamma)
+uhdr_error_info_t gain_step_table(uhdr_hip_ctx* c, const GenParams& p, StepTab* out, bool gamma_table) {
   memset(out, 0, sizeof *out);
-  if (p.gamma != 1.0f) return ok_status();
+  if (p.gamma != 1.0f && !gamma_table) return ok_status();
   for (auto& g : c->gain_tabs)
-    if (g.mn == p.min_boost && g.mx == p.max_boost) { *out = g.meta; return ok_status(); }
+    if (g.mn == p.min_boost && g.mx == p.max_boost && !memcmp(&g.gamma, &p.gamma, 4)) { *out = g.meta; return ok_status(); }
   if (c->gain_tabs.size() >= 16) return ok_status();  // a caller cycling through boost ranges keeps the float64 evaluation
   uhdr_hip_ctx::GainTab g;
-  g.mn = p.min_boost; g.mx = p.max_boost; g.d = nullptr;
-  const host::OetfBuckets b = host::gain_code8_buckets(p.min_boost, p.max_boost, p.log2min, p.log2_range, p.log2_range_rcp);
+  g.mn = p.min_boost; g.mx = p.max_boost; g.d = nullptr; g.gamma = p.gamma;
+  const host::OetfBuckets b = host::gain_code8_buckets(p.min_boost, p.max_boost, p.log2min, p.log2_range, p.log2_range_rcp, p.gamma);
   UHDR_TRY(upload_step_table(b, &g.d, &g.meta, c->stream));
   c->gain_tabs.push_back(g);
   *out = g.meta;
+  return ok_status();
+}
+uhdr_error_info_t gamma_code_thresholds(uhdr_hip_ctx* c, float gamma, const float** d_thr, float* gap) {
+  *d_thr = nullptr;
+  *gap = 0.0f;
+  if (gamma == 1.0f) return ok_status();
+  for (auto& g : c->gamma_code_tabs)
+    if (!memcmp(&g.gamma, &gamma, 4)) { *d_thr = g.d; *gap = g.gap; return ok_status(); }
+  if (c->gamma_code_tabs.size() >= 16) return ok_status();  // a caller cycling through gammas keeps the pow per sample
+  const host::GammaCodeTable& t = host::gamma_code_table(gamma);
+  uhdr_hip_ctx::GammaCodeDev g;
+  g.gamma = gamma; g.d = nullptr; g.gap = t.exact ? t.min_gap[1] : 0.0f;
+  if (t.exact) UHDR_TRY(upload_lut(&g.d, t.thr, c->stream));
+  c->gamma_code_tabs.push_back(g);
+  *d_thr = g.d;
+  *gap = g.gap;
   return ok_status();
 }
 
@@ -680,6 +697,7 @@ void uhdr_hip_destroy(uhdr_hip_ctx_t* c) {
   if (c->d_srgb8) (void)hipFree(c->d_srgb8);
   for (float* q : c->d_lin10) if (q) (void)hipFree(q);
   for (auto& g : c->gain_tabs) if (g.d) (void)hipFree(g.d);
+  for (auto& g : c->gamma_code_tabs) if (g.d) (void)hipFree(g.d);
   uhdr_hip_comm_destroy(c);
   aux_worker_destroy(c);
   if (c->aux) uhdr_hip_destroy(c->aux);

@@ -733,8 +733,25 @@ uhdr_error_info_t uhdr_hip_generate_gainmap_pass1_dev(uhdr_hip_ctx_t* c, const u
   return ok_status();
 }
 
-uhdr_error_info_t uhdr_hip_generate_gainmap_pass2_dev(uhdr_hip_ctx_t* c, const float* gain_log2_dev, const float mm[6],
-                                                      const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* gm) {
+static uhdr_error_info_t check_generate_flags(unsigned int flags) {
+  if (flags & ~(unsigned int)UHDR_HIP_GENERATE_GAMMA_TABLE)
+    return err_status(UHDR_CODEC_INVALID_PARAM, "unknown generateGainMap flag bits 0x%x", flags & ~(unsigned int)UHDR_HIP_GENERATE_GAMMA_TABLE);
+  return ok_status();
+}
+// UHDR_HIP_GENERATE_GAMMA_TABLE: the two-pass byte thresholds of cfg->gamma for the launches between and after the passes (null where
+// the gamma is 1 or has no verified table: those launches are then what they are without the flag)
+static uhdr_error_info_t fill_twopass_gamma(uhdr_hip_ctx* c, const uhdr_hip_encode_cfg_t* cfg, bool gamma_table, MinmaxTableParams* t, AffineParams* a) {
+  if (!gamma_table) return ok_status();
+  const float* block = nullptr;
+  float gap = 0.0f;
+  UHDR_TRY(gamma_code_thresholds(c, cfg->gamma, &block, &gap));
+  if (!block) return ok_status();
+  t->gamma_thr = a->gamma_thr = block + kGammaCodeN;
+  t->gamma_gap = gap;
+  return ok_status();
+}
+static uhdr_error_info_t generate_gainmap_pass2_impl(uhdr_hip_ctx_t* c, const float* gain_log2_dev, const float mm[6],
+                                                     const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* gm, bool gamma_table) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!gain_log2_dev || !mm || !cfg || !gm || !gm->planes[0]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
   if (gm->stride[0] < gm->w) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap stride (%u) cannot be less than its width (%u)", gm->stride[0], gm->w);
@@ -757,10 +774,20 @@ uhdr_error_info_t uhdr_hip_generate_gainmap_pass2_dev(uhdr_hip_ctx_t* c, const f
   a.map_w = gm->w; a.map_h = gm->h; a.out_stride = gm->stride[0];
   a.nch = cfg->use_multi_channel_gainmap ? 3 : 1;
   a.gamma = cfg->gamma;
+  UHDR_TRY(fill_twopass_gamma(c, cfg, gamma_table, &t, &a));
   ProfScope ps(c, "generate_gainmap");
   HIP_TRY(launch_minmax_table(t, c->stream));
   HIP_TRY(launch_affine_map(a, c->stream));
   return ok_status();
+}
+uhdr_error_info_t uhdr_hip_generate_gainmap_pass2_dev(uhdr_hip_ctx_t* c, const float* gain_log2_dev, const float mm[6],
+                                                      const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* gm) {
+  return generate_gainmap_pass2_impl(c, gain_log2_dev, mm, cfg, gm, false);
+}
+uhdr_error_info_t uhdr_hip_generate_gainmap_pass2_ex_dev(uhdr_hip_ctx_t* c, const float* gain_log2_dev, const float mm[6],
+                                                         const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* gm, unsigned int flags) {
+  UHDR_TRY(check_generate_flags(flags));
+  return generate_gainmap_pass2_impl(c, gain_log2_dev, mm, cfg, gm, (flags & UHDR_HIP_GENERATE_GAMMA_TABLE) != 0);
 }
 
 void uhdr_api::note_table_stats(uhdr_hip_ctx* c, const uhdr_hip_encode_cfg_t* cfg) {  // after the synchronisation that landed c->h_mm
@@ -773,7 +800,8 @@ void uhdr_api::note_table_stats(uhdr_hip_ctx* c, const uhdr_hip_encode_cfg_t* cf
 
 // pass 1's partials -> extrema -> final range -> step tables -> pass 2, all stream ordered; the final range is copied to
 // the pinned c->h_mm for the caller's metadata fill (after ITS synchronisation)
-uhdr_error_info_t uhdr_api::two_pass_tail(uhdr_hip_ctx* c, const GenParams& p, int n_partials, const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* gm) {
+uhdr_error_info_t uhdr_api::two_pass_tail(uhdr_hip_ctx* c, const GenParams& p, int n_partials, const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* gm,
+                                          bool gamma_table) {
   UHDR_TRY(ensure(c->affine, kAffineDevBytes));
   UHDR_TRY(ensure(c->exchange, 256));
   if (!c->h_mm) HIP_TRY(hipHostMalloc((void**)&c->h_mm, 9 * sizeof(float), hipHostMallocDefault));
@@ -797,6 +825,7 @@ uhdr_error_info_t uhdr_api::two_pass_tail(uhdr_hip_ctx* c, const GenParams& p, i
   a.map_w = gm->w; a.map_h = gm->h; a.out_stride = gm->stride[0];
   a.nch = cfg->use_multi_channel_gainmap ? 3 : 1;
   a.gamma = cfg->gamma;
+  UHDR_TRY(fill_twopass_gamma(c, cfg, gamma_table, &t, &a));
   {
     ProfScope ps(c, "generate_gainmap");
     HIP_TRY(launch_minmax_table(t, c->stream));
@@ -808,8 +837,10 @@ uhdr_error_info_t uhdr_api::two_pass_tail(uhdr_hip_ctx* c, const GenParams& p, i
 
 // One pass (jpegr.cpp:724-737): the range is known before a pixel is read -- the metadata, the kernel's clamp and log2 constants, and the
 // gain -> byte step table for that range (p->gain8.tab stays null where host_tables.cpp has none: the kernels then evaluate per sample)
+// gamma_table (UHDR_HIP_GENERATE_GAMMA_TABLE): a gamma != 1 gets its step table as well, and the gamma's byte thresholds for the kernels' per-sample
+// evaluation where that table does not exist
 uhdr_error_info_t uhdr_api::fill_onepass_range(uhdr_hip_ctx* c, const uhdr_hip_encode_cfg_t* cfg, float hdr_white_nits, int use_base_cg, GenParams* p,
-                                               uhdr_gainmap_metadata_t* md) {
+                                               uhdr_gainmap_metadata_t* md, bool gamma_table) {
   for (int i = 0; i < 3; i++) {
     md->max_content_boost[i] = hdr_white_nits / 203.0f;
     md->min_content_boost[i] = 1.0f;
@@ -826,12 +857,17 @@ uhdr_error_info_t uhdr_api::fill_onepass_range(uhdr_hip_ctx* c, const uhdr_hip_e
   p->log2max = log2f(md->max_content_boost[0]);
   p->log2_range = (double)(p->log2max - p->log2min);
   p->log2_range_rcp = 1.0 / p->log2_range;
-  return gain_step_table(c, *p, &p->gain8);
+  if (gamma_table && p->gamma != 1.0f) {
+    float gap;
+    UHDR_TRY(gamma_code_thresholds(c, p->gamma, &p->gamma_thr, &gap));
+    if (!p->gamma_thr) return ok_status();  // no verified thresholds for this gamma: the call is what it is without the flag
+  }
+  return gain_step_table(c, *p, &p->gain8, gamma_table);
 }
 
-uhdr_error_info_t uhdr_hip_generate_gainmap_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
-                                                const uhdr_hip_encode_cfg_t* cfg, uhdr_gainmap_metadata_t* md,
-                                                uhdr_raw_image_t* gm) {
+static uhdr_error_info_t generate_gainmap_dev_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                   const uhdr_hip_encode_cfg_t* cfg, uhdr_gainmap_metadata_t* md,
+                                                   uhdr_raw_image_t* gm, bool gamma_table) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!md || !gm || !gm->planes[0]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for gainmap metadata or image");
   HIP_TRY(hipSetDevice(c->device));
@@ -842,7 +878,7 @@ uhdr_error_info_t uhdr_hip_generate_gainmap_dev(uhdr_hip_ctx_t* c, const uhdr_ra
   fill_gainmap_desc(hdr, p, gm);
   if (gm->stride[0] < gm->w) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap stride (%u) cannot be less than its width (%u)", gm->stride[0], gm->w);
   if (cfg->preset == UHDR_USAGE_REALTIME) {  // one pass: jpegr.cpp:724-737
-    UHDR_TRY(fill_onepass_range(c, cfg, hdr_white_nits, use_base_cg, &p, md));
+    UHDR_TRY(fill_onepass_range(c, cfg, hdr_white_nits, use_base_cg, &p, md, gamma_table));
     p.out = (uint8_t*)gm->planes[0];
     p.out_stride = gm->stride[0];
     ProfScope ps(c, "generate_gainmap");
@@ -859,12 +895,25 @@ uhdr_error_info_t uhdr_hip_generate_gainmap_dev(uhdr_hip_ctx_t* c, const uhdr_ra
     ProfScope ps(c, "generate_gainmap");
     HIP_TRY(launch_generate_gainmap(p, true, c->stream));
   }
-  UHDR_TRY(two_pass_tail(c, p, gen_partials_count(p), cfg, gm));
+  UHDR_TRY(two_pass_tail(c, p, gen_partials_count(p), cfg, gm, gamma_table));
   HIP_TRY(hipStreamSynchronize(c->stream));  // the only host synchronisation: the metadata needs the final range
   float mm[6];
   memcpy(mm, c->h_mm, sizeof mm);
   note_table_stats(c, cfg);
   return generate_gainmap_finalize_md(cfg, hdr->ct, use_base_cg, mm, md);
+}
+uhdr_error_info_t uhdr_hip_generate_gainmap_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                const uhdr_hip_encode_cfg_t* cfg, uhdr_gainmap_metadata_t* md,
+                                                uhdr_raw_image_t* gm) {
+  return generate_gainmap_dev_impl(c, sdr, hdr, cfg, md, gm, false);
+}
+// generateGainMap with flags.  UHDR_HIP_GENERATE_GAMMA_TABLE: a gamma != 1 runs through the host's byte thresholds (gamma_code.h) and the step
+// tables built on them instead of a pow per sample -- the reference's bytes, where the device's own pow is within one map code of them.
+uhdr_error_info_t uhdr_hip_generate_gainmap_ex_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                   const uhdr_hip_encode_cfg_t* cfg, uhdr_gainmap_metadata_t* md,
+                                                   uhdr_raw_image_t* gm, unsigned int flags) {
+  UHDR_TRY(check_generate_flags(flags));
+  return generate_gainmap_dev_impl(c, sdr, hdr, cfg, md, gm, (flags & UHDR_HIP_GENERATE_GAMMA_TABLE) != 0);
 }
 
 // generateGainMap with the SDR intent still in coefficient form -- JpegR::encodeJPEGR API-3 (jpegr.cpp:327-385): JpegDecoderHelper's
@@ -1249,6 +1298,23 @@ int uhdr_hip_gamma_index_eval(float gamma, const float* in, uint32_t* out, size_
   if (thresholds) memcpy(thresholds, T, sizeof(float) * (kGainN + 1));
   if (in && out)
     for (size_t i = 0; i < n; i++) out[i] = host::gamma_index_lookup(in[i], T, t.gamma_inv);
+  return 0;
+}
+
+int uhdr_hip_gamma_code_eval(float gamma, int form, const float* in, uint32_t* out, size_t n, uint32_t info[4], float* thresholds) {
+  if (form != 0 && form != 1) return -1;
+  const host::GammaCodeTable& t = host::gamma_code_table(gamma);
+  if (info) {
+    info[0] = t.exact ? 1u : 0u;
+    info[1] = (uint32_t)kGammaCodeN;
+    info[2] = (uint32_t)(t.build_ms * 1000.0);  // microseconds, of the call that built the table
+    info[3] = t.exact ? t.min_gap_ulps[form] : 0u;
+  }
+  if (!t.exact) return 1;  // nothing is written: the caller keeps the pow
+  const float* T = t.thr.data() + (size_t)form * kGammaCodeN;
+  if (thresholds) memcpy(thresholds, T, sizeof(float) * kGammaCodeN);
+  if (in && out)
+    for (size_t i = 0; i < n; i++) out[i] = host::gamma_code_lookup(in[i], T);
   return 0;
 }
 

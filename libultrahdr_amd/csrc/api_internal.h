@@ -203,8 +203,11 @@ struct uhdr_hip_ctx {
   float* d_srgb8 = nullptr;
   StepTab srgb8_meta = {};
   float* d_lin10[5] = {};
-  struct GainTab { float mn, mx; float* d; StepTab meta; };
+  struct GainTab { float mn, mx; float* d; StepTab meta; float gamma = 1.0f; };
   std::vector<GainTab> gain_tabs;
+  // UHDR_HIP_GENERATE_GAMMA_TABLE: the byte thresholds of a gamma != 1 (host_tables.cpp: gamma_code_table), 2 x kGammaCodeN floats per gamma
+  struct GammaCodeDev { float gamma; float* d; float gap; };
+  std::vector<GammaCodeDev> gamma_code_tabs;
   // multi-GPU (row stripes): RCCL communicator of this rank + the exchange buffers of two-pass generation
   void* comm = nullptr;          // ncclComm_t
   int comm_rank = 0, comm_size = 0;
@@ -275,7 +278,10 @@ uhdr_error_info_t stage_out(uhdr_hip_ctx* c, const uhdr_raw_image_t* dev, uhdr_r
 uhdr_error_info_t upload_lut(float** dst, const std::vector<float>& src, hipStream_t s);
 uhdr_error_info_t upload_math(uhdr_hip_ctx* c);
 uhdr_error_info_t upload_step_table(const host::OetfBuckets& b, float** slot, StepTab* meta, hipStream_t s);
-uhdr_error_info_t gain_step_table(uhdr_hip_ctx* c, const GenParams& p, StepTab* out);
+uhdr_error_info_t gain_step_table(uhdr_hip_ctx* c, const GenParams& p, StepTab* out, bool gamma_table = false);
+// UHDR_HIP_GENERATE_GAMMA_TABLE: the device copy of a gamma's byte thresholds (one-pass set, then the two-pass set) and the two-pass set's
+// smallest gap; *d_thr stays null for gamma 1 (no pow to replace) and for a gamma without a verified table
+uhdr_error_info_t gamma_code_thresholds(uhdr_hip_ctx* c, float gamma, const float** d_thr, float* gap);
 uhdr_error_info_t select_hdr_lut(uhdr_hip_ctx* c, uhdr_color_transfer_t ct, const float** lut, int* n);
 uhdr_error_info_t validate_metadata(const uhdr_gainmap_metadata_t* m);
 bool is_rgb_fmt_host(int fmt);
@@ -286,12 +292,14 @@ uhdr_error_info_t get_apply_tables(uhdr_hip_ctx* c, const uhdr_gainmap_metadata_
 // ---- api_gainmap.cpp: parameter blocks of the gain-map operators (shared with the striped and the fused entry points) ----
 uhdr_error_info_t fill_gen_params(uhdr_hip_ctx* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg, GenParams* p,
                                   int* use_base_cg, float* hdr_white_nits_out, bool sdr_in_registers = false);
-uhdr_error_info_t fill_onepass_range(uhdr_hip_ctx* c, const uhdr_hip_encode_cfg_t* cfg, float hdr_white_nits, int use_base_cg, GenParams* p, uhdr_gainmap_metadata_t* md);
+uhdr_error_info_t fill_onepass_range(uhdr_hip_ctx* c, const uhdr_hip_encode_cfg_t* cfg, float hdr_white_nits, int use_base_cg, GenParams* p, uhdr_gainmap_metadata_t* md,
+                                     bool gamma_table = false);
 void fill_finalize(MinmaxTableParams* t, const uhdr_hip_encode_cfg_t* cfg);
 void fill_gainmap_desc(const uhdr_raw_image_t* hdr, const GenParams& p, uhdr_raw_image_t* gm);
 uhdr_error_info_t generate_gainmap_finalize_md(const uhdr_hip_encode_cfg_t* cfg, uhdr_color_transfer_t hdr_ct, int use_base_cg, const float mm[6], uhdr_gainmap_metadata_t* md);
 void note_table_stats(uhdr_hip_ctx* c, const uhdr_hip_encode_cfg_t* cfg);
-uhdr_error_info_t two_pass_tail(uhdr_hip_ctx* c, const GenParams& p, int n_partials, const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* gm);
+uhdr_error_info_t two_pass_tail(uhdr_hip_ctx* c, const GenParams& p, int n_partials, const uhdr_hip_encode_cfg_t* cfg, uhdr_raw_image_t* gm,
+                                bool gamma_table = false);
 // generateGainMap from coefficients (uhdr_hip_generate_gainmap_coef_dev / _coef422_dev / _coef444_dev and the API-3 chain): every check of the operator, then the
 // parameter block and the coefficient descriptor.  Launches nothing; sampling: 420, 422 or 444.
 uhdr_error_info_t prepare_gen_coef(uhdr_hip_ctx* c, const uhdr_hip_jpeg_coefficients_t* sdr, unsigned int w, unsigned int h, int sampling, uhdr_color_gamut_t sdr_cg,

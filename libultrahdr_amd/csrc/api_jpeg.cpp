@@ -16,7 +16,8 @@ int uhdr_hip_oetf_code_thresholds(uhdr_color_transfer_t ct, float thresholds[102
 uhdr_error_info_t uhdr_hip_selftest(uhdr_hip_ctx_t* c, int which, unsigned int arg0, unsigned int arg1, unsigned int seed, const float mm[6],
                                     unsigned long long out[8]) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
-  if (!out || which < 0 || which > 5 || (which == 5 && !mm) || (which == 4 && (!mm || arg0 > 2 || arg1 < 1 || arg1 > 3 || arg0 >= arg1)) || (which == 2 && (arg0 < 1 || arg1 > 254 || arg0 > arg1)))
+  if (!out || which < 0 || which > 7 || (which == 5 && !mm) || (which == 6 && (!mm || arg0 > 1)) ||
+      ((which == 4 || which == 7) && (!mm || arg0 > 2 || arg1 < 1 || arg1 > 3 || arg0 >= arg1)) || (which == 2 && (arg0 < 1 || arg1 > 254 || arg0 > arg1)))
     return err_status(UHDR_CODEC_INVALID_PARAM, "bad self-test arguments");
   HIP_TRY(hipSetDevice(c->device));
   UHDR_TRY(upload_math(c));
@@ -53,7 +54,49 @@ uhdr_error_info_t uhdr_hip_selftest(uhdr_hip_ctx_t* c, int which, unsigned int a
     HIP_TRY(hipStreamSynchronize(c->stream));
     return ok_status();
   }
-  HIP_TRY(launch_selftest(which, d_out, arg0, arg1, seed, c->d_math, (const AffineDev*)c->affine.p, c->stream));
+  if (which == 6) {  // mm[0]: the gain-map gamma, arg0: the form (0 one pass, 1 two pass) whose byte thresholds are swept
+    const host::GammaCodeTable& t = host::gamma_code_table(mm[0]);
+    if (!t.exact) {
+      for (int i = 0; i < 8; i++) out[i] = 0;
+      out[3] = 1;  // no table for this gamma
+      return ok_status();
+    }
+    const float* T = t.thr.data() + (size_t)arg0 * kGammaCodeN;
+    UHDR_TRY(ensure(c->scratch[7], sizeof(float) * kGammaCodeN));
+    HIP_TRY(hipMemcpyAsync(c->scratch[7].p, T, sizeof(float) * kGammaCodeN, hipMemcpyHostToDevice, c->stream));
+    uint32_t last;
+    memcpy(&last, &T[kGammaCodeN - 1], 4);
+    last += 8;  // a few ulps past the last threshold
+    HIP_TRY(launch_selftest(which, d_out, arg0, last, seed, c->d_math, nullptr, c->stream, (const float*)c->scratch[7].p));
+    HIP_TRY(hipMemcpyAsync(out, d_out, 64, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return ok_status();
+  }
+  const float* thr2 = nullptr;
+  if (which == 7) {  // seed: the bit pattern of the gamma; the table of channel arg0 is built from its two-pass thresholds, as pass 2 with the flag builds it
+    float gamma, gap = 0.0f;
+    memcpy(&gamma, &seed, 4);
+    const float* block = nullptr;
+    UHDR_TRY(gamma_code_thresholds(c, gamma, &block, &gap));
+    if (!block) {
+      for (int i = 0; i < 8; i++) out[i] = 0;
+      out[3] = 1;  // no thresholds for this gamma (or gamma 1: sweep 4)
+      return ok_status();
+    }
+    thr2 = block + kGammaCodeN;
+    MinmaxTableParams t;
+    memset(&t, 0, sizeof t);
+    t.do_table = 1;
+    t.nch = (int)arg1;
+    t.gamma = gamma;
+    t.gamma_thr = thr2;
+    t.gamma_gap = gap;
+    for (int i = 0; i < 6; i++) t.final_mm[i] = mm[i];
+    t.dev = (AffineDev*)c->affine.p;
+    t.math_tab = c->d_math;
+    HIP_TRY(launch_minmax_table(t, c->stream));
+  }
+  HIP_TRY(launch_selftest(which, d_out, arg0, arg1, seed, c->d_math, (const AffineDev*)c->affine.p, c->stream, thr2));
   HIP_TRY(hipMemcpyAsync(out, d_out, 64, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return ok_status();
@@ -351,6 +394,7 @@ enum Api1Route : unsigned {
   kApi1Dev = 1,      // (scans) the intents and the two scans are device buffers
   kApi1AnySdr = 2,   // an RGBA8888 SDR intent is taken as well as a 4:2:0 one
   kApi1Onepass = 4,  // the real-time preset is taken too
+  kApi1GammaTable = 8,  // UHDR_HIP_GENERATE_GAMMA_TABLE: a gamma != 1 is taken, through the host's byte thresholds (gamma_code.h)
 };
 
 // What the chain declines whatever else the request holds -- the SDR intent's format and MCU rule, the preset, gamma -- stated once: the
@@ -370,7 +414,10 @@ static uhdr_error_info_t check_api1_request(const uhdr_raw_image_t* sdr, const u
   }
   if (cfg->preset == UHDR_USAGE_REALTIME && !(route & kApi1Onepass))
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain is the two-pass (best quality) encode; one pass: generate_gainmap + fdct_quant");
-  if (cfg->gamma != 1.0f) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs gain-map gamma 1 (received %f); use the operators", cfg->gamma);
+  if (cfg->gamma != 1.0f && !(route & kApi1GammaTable))
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs gain-map gamma 1 (received %f); use the operators", cfg->gamma);
+  if (cfg->gamma != 1.0f && !host::gamma_code_table(cfg->gamma).exact)  // (host arithmetic, once per gamma: nothing has gone up yet)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain has no verified threshold table for gain-map gamma %f; use the operators", cfg->gamma);
   return ok_status();
 }
 
@@ -395,6 +442,9 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   // onepass (uhdr_hip_encode_api1_fused_onepass_dev): the real-time preset is taken too, as TWO launches -- launch_map_blocks_onepass (the
   // range is known beforehand, jpegr.cpp:724-737: no ratio plane, no reduction, no range read-back) and the base image's blocks
   const bool one = onepass && cfg && cfg->preset == UHDR_USAGE_REALTIME;
+  const bool gamma_table = (route & kApi1GammaTable) != 0;
+  const float* gamma_thr2 = nullptr;  // two pass, gamma != 1: the thresholds behind the range kernel's tables and the map kernel's per-sample tail
+  float gamma_gap = 0.0f;
   if (one && striped) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes, which stay two-pass (uhdr_hip_encode_api1_fused_dev)");
   if (rgba && striped) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes of 4:2:0 base images; an RGBA8888 SDR intent is encoded whole");
   Rgb2Yuv base_k;
@@ -445,6 +495,13 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
       convert = r == 0;
     }
     if (!one) UHDR_TRY(ensure(c->scratch[7], (size_t)p.map_w * p.map_h * nch * sizeof(float)));
+    if (!one && gamma_table && cfg->gamma != 1.0f) {
+      const float* block = nullptr;
+      UHDR_TRY(gamma_code_thresholds(c, cfg->gamma, &block, &gamma_gap));
+      // (the map kernel's per-sample tail has no pow of its own: without thresholds the chain cannot take this gamma)
+      if (!block) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain has no threshold table left for gain-map gamma %f; use the operators", cfg->gamma);
+      gamma_thr2 = block + kGammaCodeN;
+    }
     return ok_status();
   };
   if (!one) {  // the exchange buffers first: without them a rank cannot even contribute the identity
@@ -456,7 +513,7 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   }
   uhdr_error_info_t local = prepare();
   if (local.error_code != UHDR_CODEC_OK && !striped) return local;
-  if (one) UHDR_TRY(fill_onepass_range(c, cfg, hdr_white_nits, use_base_cg, &p, md));  // the metadata is host arithmetic: complete here
+  if (one) UHDR_TRY(fill_onepass_range(c, cfg, hdr_white_nits, use_base_cg, &p, md, gamma_table));  // the metadata is host arithmetic: complete here
   auto base_launch = [&](hipStream_t s) -> hipError_t {
     if (rgba) return launch_base_blocks_rgba(view_of(sdr), base_k, convert ? &conv : nullptr, qt_base[0], qt_base[1], blocks->base_coef, s);
     return launch_base_blocks(view_of(sdr), convert ? &conv : nullptr, qt_base[0], qt_base[1], blocks->base_coef, s);
@@ -533,6 +590,8 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
     t.out_mm = final_mm;
     t.dev = (AffineDev*)c->affine.p;
     t.math_tab = c->d_math;
+    t.gamma_thr = gamma_thr2;
+    t.gamma_gap = gamma_gap;
     if (!striped) {  // one launch for everything between the passes
       t.do_reduce = t.do_finalize = t.do_table = 1;
       note_hip(launch_minmax_table(t, c->stream), "minmax / tables");
@@ -563,7 +622,7 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   if (run && xchg.error_code == UHDR_CODEC_OK) {
     ProfScope ps(c, "fdct_quant");
     note_hip(launch_map_blocks(p.gain_log2, (const AffineDev*)c->affine.p, c->d_math, nch, (int)(p.map_w / 8), (int)(p.map_h / 8), qt_map[0], qt_map[1],
-                               blocks->map_coef, map_out, map_stride, c->stream), "map blocks");
+                               blocks->map_coef, map_out, map_stride, c->stream, gamma_thr2), "map blocks");
     if (!side && !rgba) note_hip(base_launch(c->stream), "base blocks");
   }
   if (run && xchg.error_code == UHDR_CODEC_OK && !side && rgba) {
@@ -636,6 +695,12 @@ static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   UHDR_TRY(validate_image(sdr, "sdr intent"));
   UHDR_TRY(validate_image(hdr, "hdr intent"));
   HIP_TRY(hipSetDevice(c->device));
+  if ((route & kApi1GammaTable) && cfg->gamma != 1.0f && cfg->preset != UHDR_USAGE_REALTIME) {  // before the intents go up: a context keeps 16 gammas
+    const float* block = nullptr;
+    float gap;
+    UHDR_TRY(gamma_code_thresholds(c, cfg->gamma, &block, &gap));
+    if (!block) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain has no threshold table left for gain-map gamma %f; use the operators", cfg->gamma);
+  }
   const unsigned w = sdr->w, h = sdr->h, mw = w / (unsigned)scale, mh = h / (unsigned)scale;
   const int nch = cfg->use_multi_channel_gainmap ? 3 : 1;
   uhdr_raw_image_t ds, dh;
@@ -784,6 +849,33 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans_onepass(uhdr_hip_ctx_t* c, const uh
                                                      size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
   return encode_api1_scans_timed(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
                                  map_bytes, kApi1AnySdr | kApi1Onepass);
+}
+
+// ... and with generateGainMap's flags: UHDR_HIP_GENERATE_GAMMA_TABLE lets a gain-map gamma other than 1 through (both presets), evaluated through the
+// host's byte thresholds as uhdr_hip_generate_gainmap_ex_dev evaluates it; flags 0 is the _onepass sibling
+static uhdr_error_info_t check_api1_flags(unsigned int flags, unsigned* route) {
+  if (flags & ~(unsigned int)UHDR_HIP_GENERATE_GAMMA_TABLE)
+    return err_status(UHDR_CODEC_INVALID_PARAM, "unknown generateGainMap flag bits 0x%x", flags & ~(unsigned int)UHDR_HIP_GENERATE_GAMMA_TABLE);
+  if (flags & UHDR_HIP_GENERATE_GAMMA_TABLE) *route |= kApi1GammaTable;
+  return ok_status();
+}
+uhdr_error_info_t uhdr_hip_encode_api1_scans_ex_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                    uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                    uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                                    size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned int flags) {
+  unsigned route = kApi1Dev | kApi1AnySdr | kApi1Onepass;
+  UHDR_TRY(check_api1_flags(flags, &route));
+  return encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
+                                map_bytes, route);
+}
+uhdr_error_info_t uhdr_hip_encode_api1_scans_ex(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                                size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned int flags) {
+  unsigned route = kApi1AnySdr | kApi1Onepass;
+  UHDR_TRY(check_api1_flags(flags, &route));
+  return encode_api1_scans_timed(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
+                                 map_bytes, route);
 }
 
 // JpegR::encodeJPEGR API-0 (jpegr.cpp:179-244) for the HDR intents its tone map renders to RGBA8888 -- RGBA1010102 (BASELINE config 3) and

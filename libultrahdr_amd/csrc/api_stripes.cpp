@@ -315,9 +315,10 @@ uhdr_error_info_t uhdr_hip_generate_gainmap_striped_dev(uhdr_hip_ctx_t* c, const
   return generate_gainmap_finalize_md(cfg, hdr->ct, use_base_cg, mm, md);
 }
 
-uhdr_error_info_t uhdr_hip_generate_gainmap(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
-                                            const uhdr_hip_encode_cfg_t* cfg, uhdr_gainmap_metadata_t* md,
-                                            uhdr_raw_image_t* gm) {
+// ex: the device stage is uhdr_hip_generate_gainmap_ex_dev with `flags` (which checks them before anything runs on the device)
+static uhdr_error_info_t generate_gainmap_host(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                               const uhdr_hip_encode_cfg_t* cfg, uhdr_gainmap_metadata_t* md,
+                                               uhdr_raw_image_t* gm, bool ex, unsigned int flags) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!sdr || !hdr || !cfg || !md || !gm || !gm->planes[0]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
   HIP_TRY(hipSetDevice(c->device));
@@ -338,11 +339,24 @@ uhdr_error_info_t uhdr_hip_generate_gainmap(uhdr_hip_ctx_t* c, const uhdr_raw_im
   if (tmp.stride[0] < mw) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap stride (%u) cannot be less than its width (%u)", tmp.stride[0], mw);
   uhdr_raw_image_t dgm;
   UHDR_TRY(stage_in(c, 2, &tmp, &dgm, false));
-  UHDR_TRY(uhdr_hip_generate_gainmap_dev(c, &dsdr, &dhdr, cfg, md, &dgm));
+  if (ex) UHDR_TRY(uhdr_hip_generate_gainmap_ex_dev(c, &dsdr, &dhdr, cfg, md, &dgm, flags));
+  else UHDR_TRY(uhdr_hip_generate_gainmap_dev(c, &dsdr, &dhdr, cfg, md, &dgm));
   void* host_plane = gm->planes[0];
   const unsigned host_stride = gm->stride[0];
   *gm = dgm;
   gm->planes[0] = host_plane; gm->planes[1] = gm->planes[2] = nullptr;
   gm->stride[0] = host_stride; gm->stride[1] = gm->stride[2] = 0;
   return stage_out(c, &dgm, gm);
+}
+uhdr_error_info_t uhdr_hip_generate_gainmap(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                            const uhdr_hip_encode_cfg_t* cfg, uhdr_gainmap_metadata_t* md,
+                                            uhdr_raw_image_t* gm) {
+  return generate_gainmap_host(c, sdr, hdr, cfg, md, gm, false, 0u);
+}
+uhdr_error_info_t uhdr_hip_generate_gainmap_ex(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                               const uhdr_hip_encode_cfg_t* cfg, uhdr_gainmap_metadata_t* md,
+                                               uhdr_raw_image_t* gm, unsigned int flags) {
+  if (flags & ~(unsigned int)UHDR_HIP_GENERATE_GAMMA_TABLE)  // before anything is uploaded
+    return err_status(UHDR_CODEC_INVALID_PARAM, "unknown generateGainMap flag bits 0x%x", flags & ~(unsigned int)UHDR_HIP_GENERATE_GAMMA_TABLE);
+  return generate_gainmap_host(c, sdr, hdr, cfg, md, gm, true, flags);
 }

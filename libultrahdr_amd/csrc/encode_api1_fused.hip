@@ -54,6 +54,7 @@ struct MapBlocksParams {
   int bw, bh;              // blocks (map_w / 8, map_h / 8)
   int16_t* coef[3];
   QuantTables q;
+  const float* gamma_thr;  // the two-pass byte thresholds of a gamma != 1 (gamma_code.h), global memory; null: gamma is 1
 };
 
 constexpr int kMapBlock = 512;  // eight waves share one copy of the step tables (24 KB): three workgroups = 24 waves per CU
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(kMapBlock) void map_blocks_kernel(const MapBlocksPa
           for (int i = 0; i < 4; i++) acc |= step_code(f[i], s_tab[(4 * k + i) % NCH], st[(4 * k + i) % NCH]) << (8 * i);
           w[k] = acc;
         }
-      } else {  // a channel without a table (gamma is 1 here, the launcher checks): the per-sample evaluation of generate_gainmap.hip,
+      } else {  // a channel without a table (gamma is 1 here, or comes with its thresholds): the per-sample evaluation of generate_gainmap.hip,
                 // as a rolled loop that parks its words in the wave's (idle) LDS workspace -- its float64 arithmetic must not
                 // set the register count of the table path
         const float* gp = (const float*)src;
@@ -119,6 +120,10 @@ __global__ __launch_bounds__(kMapBlock) void map_blocks_kernel(const MapBlocksPa
             const int c = (4 * k + i) % NCH;
             const float lg = gain_log2_of_ratio(gp[4 * k + i], p.math_tab);
             float m = div_by_rcp64(lg - p.dev->mn[c], p.dev->range_rcp[c]);
+            if (p.gamma_thr) {  // (wave-uniform) the pow, the scaling and the clip as a search over the host's thresholds
+              acc |= gamma_code(m, p.gamma_thr) << (8 * i);
+              continue;
+            }
             m *= 255.0f;
             float t2 = m + 0.5f;
             t2 = (t2 < 0.0f) ? 0.0f : ((t2 > 255.0f) ? 255.0f : t2);
@@ -489,9 +494,11 @@ int resident_grid(int total_wave_items, int per_cu) {
 // ratio plane (pass 1) + AffineDev (launch_minmax_table) -> quantized coefficients of the map's JPEG (+ the 8-bit map when map_out != null).
 // nch 3: packed RGB semantics (rgb_ycc_convert, 4:4:4, luma table for Y, chroma table for Cb / Cr); nch 1: a Y400 map.
 hipError_t launch_map_blocks(const float* ratio, const AffineDev* dev, const double* math_tab, int nch, int bw, int bh, const uint16_t* qt_luma,
-                             const uint16_t* qt_chroma, int16_t* const coef[3], uint8_t* map_out, uint32_t out_stride, hipStream_t s) {
+                             const uint16_t* qt_chroma, int16_t* const coef[3], uint8_t* map_out, uint32_t out_stride, hipStream_t s,
+                             const float* gamma_thr) {
   MapBlocksParams p;
   memset(&p, 0, sizeof p);
+  p.gamma_thr = gamma_thr;
   p.ratio = ratio; p.dev = dev; p.math_tab = math_tab; p.map_out = map_out; p.out_stride = out_stride; p.bw = bw; p.bh = bh;
   for (int i = 0; i < nch; i++) p.coef[i] = coef[i];
   fill_quant_table(qt_luma, &p.q.luma);

@@ -16,6 +16,7 @@
 //     max commute with the monotone log2, and pass 2's byte is a step function of the ratio (generate_gainmap.hip).
 #pragma once
 #include "exact_math.h"
+#include "gamma_code.h"
 #include "lds_copy.h"
 #include "pixel_io.h"
 #include "uhdr_types.h"
@@ -198,6 +199,8 @@ __device__ __forceinline__ uint8_t encode_gain(float y_sdr, float y_hdr, const G
   if (gain > p.max_boost) gain = p.max_boost;
   const double lg = log2_table_f64(gain, T);
   const float n = (float)div_by_const_f64(lg - (double)p.log2min, p.log2_range, p.log2_range_rcp);
+  // UHDR_HIP_GENERATE_GAMMA_TABLE, gamma != 1 (wave-uniform): the powf and the truncation as a search over the host's thresholds
+  if (p.gamma_thr) return (uint8_t)gamma_code(n, gamma_thr_onepass(p.gamma_thr));
   const float ng = (p.gamma == 1.0f) ? n : powf(n, p.gamma);  // powf(x, 1) == x exactly
   return (uint8_t)(ng * 255.0f);
 }

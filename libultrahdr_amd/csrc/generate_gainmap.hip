@@ -146,12 +146,23 @@ __device__ __forceinline__ uint32_t affine_code(float q, float mn, double rr, fl
   return (uint32_t)t2;
 }
 
+// ... and the same composite for a gamma != 1 behind UHDR_HIP_GENERATE_GAMMA_TABLE: the pow, the scaling, the clip and the truncation are
+// one search over the host's two-pass thresholds (gamma_code.h), which are the reference's bytes for every finite m
+__device__ __forceinline__ uint32_t affine_code_thr(float q, float mn, double rr, const float* thr, const double* T) {
+  const float g = gain_log2_of_ratio(q, T);
+  return gamma_code(div_by_rcp64(g - mn, rr), thr);
+}
+
 constexpr int kTabBlock = 1024;
+// GT: the byte comes from affine_code_thr (p.gamma_thr, staged into LDS: every bisection step reads it eight times in a row); the GT = false
+// instantiation is the kernel as it was
+template <bool GT>
 __global__ __launch_bounds__(kTabBlock) void minmax_table_kernel(const MinmaxTableParams p) {
   __shared__ float s_red[kTabBlock / 64][2];
   __shared__ float s_mm[2];
   __shared__ uint32_t s_geo[8];
   __shared__ double s_T[kMathTabDoubles];  // the log2 tables: every bisection step is a dependent table read
+  __shared__ float s_thr[GT ? kGammaCodeN : 1];
   const int c = blockIdx.x;  // channel
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   // this thread's partials first, THEN the table staging: both round trips to memory are in flight together (the kernel is a
@@ -165,6 +176,8 @@ __global__ __launch_bounds__(kTabBlock) void minmax_table_kernel(const MinmaxTab
   float merged_min = 0.0f, merged_max = 0.0f;
   if (p.do_finalize && p.merged_in) { merged_min = p.merged_in[c]; merged_max = -p.merged_in[3 + c]; }
   for (int i = tid; i < kMathTabDoubles; i += kTabBlock) s_T[i] = p.math_tab[i];
+  if constexpr (GT)
+    if (tid < kGammaCodeN) s_thr[tid] = p.gamma_thr[tid];
   __syncthreads();
   const double* T = s_T;
   float gmin, gmax;
@@ -202,7 +215,7 @@ __global__ __launch_bounds__(kTabBlock) void minmax_table_kernel(const MinmaxTab
   const double rr = 1.0 / (double)(gmax - gmin);
   AffineTabDev& td = p.dev->tab[c];
   if (tid == 0) { p.dev->mn[c] = gmin; p.dev->mx[c] = gmax; p.dev->range_rcp[c] = rr; }
-  if (!p.do_table || c >= p.nch || p.gamma != 1.0f) {  // (a user gamma: pass 2 evaluates per sample, launch_affine_map)
+  if (!p.do_table || c >= p.nch || (!GT && p.gamma != 1.0f)) {  // (a user gamma without thresholds: pass 2 evaluates per sample, launch_affine_map)
     if (tid == 0) {
       td.ok = 0;
       if (p.out_mm) p.out_mm[6 + c] = 0.0f;
@@ -210,6 +223,10 @@ __global__ __launch_bounds__(kTabBlock) void minmax_table_kernel(const MinmaxTab
     return;
   }
   // ---- the ratio -> byte step table of this channel --------------------------------------------------------------------------
+  auto code = [&](uint32_t bits) -> uint32_t {
+    if constexpr (GT) return affine_code_thr(__uint_as_float(bits), gmin, rr, s_thr, T);
+    else return affine_code<false>(__uint_as_float(bits), gmin, rr, p.gamma, T);
+  };
   // geometry: buckets per binade B = 2^(23 - shift) such that a bucket is narrower (in log2) than the spacing of the byte
   // thresholds, (max - min) / 255 for gamma 1: 1.4427 / B < range / 255 with 5 % to spare
   if (tid == 0) {
@@ -217,9 +234,10 @@ __global__ __launch_bounds__(kTabBlock) void minmax_table_kernel(const MinmaxTab
     uint32_t ok = (range > 0.0f) && (range < 64.0f);
     uint32_t shift = 0, lo_bits = 0, hi_bits = 0, n = 0;
     if (ok) {
-      const float need = 386.3f / range;  // 1.4427 * 255 * 1.05
+      // GT: the byte thresholds are not evenly spaced in m; the host's smallest gap between two of them takes 1 / 255's place
+      const float need = GT ? 1.5149f / (range * p.gamma_gap) : 386.3f / range;  // 1.4427 * 255 * 1.05
       int e = 0;
-      while ((float)(1u << e) < need && e < 21) e++;
+      while ((float)(1u << e) < need && e < 21) e++;  // (GT: a zero gap makes need infinite, e ends at 21 and the table is declined)
       shift = 23u - (uint32_t)e;
       if (e > 20) ok = 0;  // step_code addresses buckets with shift >= 3
       // domain: two buckets beyond [2^min, 2^max] on either side (exp2f is accurate to a few ulp, a bucket is at least 8;
@@ -231,8 +249,8 @@ __global__ __launch_bounds__(kTabBlock) void minmax_table_kernel(const MinmaxTab
       n = (hi_bits >> shift) - (lo_bits >> shift) + 1u;
       if (n > (uint32_t)kAffTabMax) ok = 0;
       if (ok) {  // the step function must be saturated at both ends of the domain and beyond
-        const uint32_t c_lo = affine_code<false>(__uint_as_float(lo_bits), gmin, rr, p.gamma, T), c_hi = affine_code<false>(__uint_as_float(hi_bits), gmin, rr, p.gamma, T);
-        if (c_lo != affine_code<false>(0x1p-120f, gmin, rr, p.gamma, T) || c_hi != affine_code<false>(0x1p120f, gmin, rr, p.gamma, T) || c_hi < c_lo) ok = 0;
+        const uint32_t c_lo = code(lo_bits), c_hi = code(hi_bits);
+        if (c_lo != code(__float_as_uint(0x1p-120f)) || c_hi != code(__float_as_uint(0x1p120f)) || c_hi < c_lo) ok = 0;
       }
     }
     s_geo[0] = ok; s_geo[1] = shift; s_geo[2] = lo_bits; s_geo[3] = hi_bits; s_geo[4] = n;
@@ -244,7 +262,7 @@ __global__ __launch_bounds__(kTabBlock) void minmax_table_kernel(const MinmaxTab
   if (s_geo[0]) {
     for (uint32_t k = tid; k < n; k += kTabBlock) {
       const uint32_t start = lo_bits + (k << shift), end = start + (1u << shift) - 1u;
-      const uint32_t f_lo = affine_code<false>(__uint_as_float(start), gmin, rr, p.gamma, T), f_hi = affine_code<false>(__uint_as_float(end), gmin, rr, p.gamma, T);
+      const uint32_t f_lo = code(start), f_hi = code(end);
       uint32_t thr = 0xFFFFFFFFu;
       if (f_hi != f_lo) {
         uint32_t a = start, b = end;  // invariant: code(a) == f_lo < code(b)
@@ -254,21 +272,21 @@ __global__ __launch_bounds__(kTabBlock) void minmax_table_kernel(const MinmaxTab
         // a dependent float64 chain, and the kernel was little else).  If not (a step of two codes, a range so narrow
         // that the log2's float rounding decides), the whole bucket is searched as before.
         {
-          const float g_thr = gmin + ((float)f_hi - 0.5f) * ((gmax - gmin) * (1.0f / 255.0f));
+          // (GT: the byte changes to f_hi where m crosses the host's threshold T[f_hi], i.e. at g = min + T[f_hi] * range)
+          const float g_thr = GT ? gmin + s_thr[f_hi & 255u] * (gmax - gmin) : gmin + ((float)f_hi - 0.5f) * ((gmax - gmin) * (1.0f / 255.0f));
           const uint32_t est = __float_as_uint(exp2f(g_thr));
           const uint32_t a2 = max(start, est - 64u), b2 = min(end, est + 64u);
-          if (est > 64u && a2 < b2 && a2 >= start && b2 <= end && affine_code<false>(__uint_as_float(a2), gmin, rr, p.gamma, T) == f_lo &&
-              affine_code<false>(__uint_as_float(b2), gmin, rr, p.gamma, T) > f_lo) {
+          if (est > 64u && a2 < b2 && a2 >= start && b2 <= end && code(a2) == f_lo && code(b2) > f_lo) {
             a = a2;
             b = b2;
           }
         }
         while (b - a > 1u) {
           const uint32_t mid = a + (b - a) / 2u;
-          if (affine_code<false>(__uint_as_float(mid), gmin, rr, p.gamma, T) > f_lo) b = mid; else a = mid;
+          if (code(mid) > f_lo) b = mid; else a = mid;
         }
         thr = b;
-        if (affine_code<false>(__uint_as_float(b), gmin, rr, p.gamma, T) != f_hi || f_hi < f_lo) atomicAnd(&s_geo[5], 0u);  // a second threshold / not monotone
+        if (code(b) != f_hi || f_hi < f_lo) atomicAnd(&s_geo[5], 0u);  // a second threshold / not monotone
       }
       tab[k] = uint2{thr, f_lo | (f_hi << 16)};
     }
@@ -315,7 +333,7 @@ __global__ __launch_bounds__(kBlock) void affine_kernel(const AffineParams p) {
   __shared__ AffineLds L;
   StepTab st[3];
   const bool tabs = p.nch == 3 ? stage_affine_tabs<3>(p, L, st, threadIdx.x, kBlock) : stage_affine_tabs<1>(p, L, st, threadIdx.x, kBlock);
-  // (no table: a range too dense for one threshold per bucket; gamma is 1 here, see launch_affine_map)
+  // (no table: a range too dense for one threshold per bucket; gamma is 1 here or comes with its thresholds, see launch_affine_map)
   const uint32_t row_elems = p.map_w * p.nch;
   const uint32_t per_row = VEC4 ? row_elems / 4 : row_elems;
   const uint32_t tiles_x = (per_row + kBlock - 1) / kBlock, tiles = tiles_x * p.map_h;
@@ -326,7 +344,9 @@ __global__ __launch_bounds__(kBlock) void affine_kernel(const AffineParams p) {
     uint8_t* dst = p.out + (size_t)y * p.out_stride * p.nch;
     auto map1 = [&](float q, uint32_t e) -> uint32_t {
       const uint32_t c = p.nch == 3 ? e % 3 : 0;
-      if (!tabs) return affine_code<false>(q, p.dev->mn[c], p.dev->range_rcp[c], 1.0f, p.math_tab);
+      if (!tabs)
+        return p.gamma_thr ? affine_code_thr(q, p.dev->mn[c], p.dev->range_rcp[c], p.gamma_thr, p.math_tab)
+                           : affine_code<false>(q, p.dev->mn[c], p.dev->range_rcp[c], 1.0f, p.math_tab);
       return c == 0 ? step_code(q, L.tab[0], st[0]) : (c == 1 ? step_code(q, L.tab[1], st[1]) : step_code(q, L.tab[2], st[2]));
     };
     if constexpr (VEC4) {
@@ -357,14 +377,15 @@ __global__ __launch_bounds__(kBlock) void affine_wide_kernel(const AffineParams 
     const uint32_t y = idx / per_row, j = idx - y * per_row;
     const float4* src = (const float4*)(p.gain_log2 + (size_t)y * row_elems + (size_t)j * NS);
     uint8_t* dst = p.out + (size_t)y * p.out_stride * NCH + (size_t)j * NS;
-    if (!tabs) {  // a range too dense for one threshold per bucket (gamma is 1 here: launch_affine_map): per sample through the
+    if (!tabs) {  // a range too dense for one threshold per bucket (gamma is 1 here or comes with its thresholds: launch_affine_map): per sample through the
                   // exact evaluation, one load and one store at a time -- register-light, this path must not cost the table
                   // path its occupancy
       const float* sp = (const float*)src;
 #pragma unroll 1
       for (int e = 0; e < NS; e++) {
         const int c = e % NCH;
-        dst[e] = (uint8_t)affine_code<false>(sp[e], p.dev->mn[c], p.dev->range_rcp[c], 1.0f, p.math_tab);
+        dst[e] = (uint8_t)(p.gamma_thr ? affine_code_thr(sp[e], p.dev->mn[c], p.dev->range_rcp[c], p.gamma_thr, p.math_tab)
+                                       : affine_code<false>(sp[e], p.dev->mn[c], p.dev->range_rcp[c], 1.0f, p.math_tab));
       }
       continue;
     }
@@ -389,8 +410,8 @@ __global__ __launch_bounds__(kBlock) void affine_wide_kernel(const AffineParams 
   }
 }
 
-// The per-sample evaluation for maps with a user gamma != 1 (the host knows: no tables are built, launch_affine_map comes
-// here directly).  Kept out of the table kernels because its float64 pow would cost them half their occupancy.
+// The per-sample evaluation for maps with a user gamma != 1 and no thresholds (the host knows: no tables are built,
+// launch_affine_map comes here directly).  Kept out of the table kernels because its float64 pow would cost them half their occupancy.
 __global__ __launch_bounds__(kBlock) void affine_exact_kernel(const AffineParams p) {
   const uint32_t row_elems = p.map_w * p.nch;
   const size_t total = (size_t)row_elems * p.map_h;
@@ -474,13 +495,14 @@ hipError_t launch_generate_gainmap(const GenParams& p, bool two_pass, hipStream_
 }
 
 hipError_t launch_minmax_table(const MinmaxTableParams& p, hipStream_t s) {
-  hipLaunchKernelGGL(minmax_table_kernel, dim3(3), dim3(kTabBlock), 0, s, p);
+  if (p.gamma_thr) hipLaunchKernelGGL(minmax_table_kernel<true>, dim3(3), dim3(kTabBlock), 0, s, p);
+  else hipLaunchKernelGGL(minmax_table_kernel<false>, dim3(3), dim3(kTabBlock), 0, s, p);
   return hipGetLastError();
 }
 
 hipError_t launch_affine_map(const AffineParams& p, hipStream_t s) {
   const uint32_t row_elems = p.map_w * p.nch;
-  if (p.gamma != 1.0f) {
+  if (p.gamma != 1.0f && !p.gamma_thr) {
     hipLaunchKernelGGL(affine_exact_kernel, dim3(2048), dim3(kBlock), 0, s, p);
     return hipGetLastError();
   }

@@ -432,6 +432,148 @@ const GammaIndexTable& gamma_index_table(float gamma_inv) {
   return *cache.back();
 }
 
+// ---- generateGainMap, gamma != 1: the map byte as thresholds over the normalised gain ---------------------------------------
+// Both byte functions of the encode side are monotone staircases of one float with 255 steps:
+//   form 0  encodeGain (gainmapmath.cpp:769-770)      (uint8_t)(powf(n, gamma) * 255.0f)
+//   form 1  affineMapGain (gainmapmath.cpp:784-789)   m = (float)pow((double)m, (double)gamma); m *= 255; clip(m + 0.5, 0, 255), truncated
+// so byte(v) = max{ k : T[k] <= v } with T[k] the smallest float whose byte is >= k needs no pow on the device.  A negative argument
+// (two pass: a min-boost hint above the content's minimum; one pass: the float / double log2 mismatch at gain == min_boost) makes pow
+// return NaN, which the reference's float -> integer conversion turns into byte 0 on x86 (cvttss2si yields 0x80000000, whose low byte
+// is 0; form 1's clip passes a NaN through both comparisons) -- and "below T[1]" is byte 0 as well, so the table needs no special case.
+// The exception is a gamma that is an EVEN INTEGER (2, 4, ...): pow(-x, gamma) is then pow(x, gamma), not a NaN, and the byte of a negative
+// argument is the byte of its magnitude.  Such a table says so in the sign bit of T[0] (-0.0f, still "T[0] = 0"), and the lookup clears the
+// argument's sign with it.  (An odd integer gamma gives a negative power, which is byte 0 like the NaN.)
+static uint32_t byte_of_float(float p) {  // the x86 narrowing (uint8_t)p, with the NaN case written out (undefined in C++)
+  if (!(p > -1.0f)) return 0u;            // NaN; and anything <= -1 is outside both forms' ranges
+  return (uint32_t)(uint8_t)(int)p;
+}
+uint32_t gamma_code_direct(float v, float gamma, int form) {
+  if (form == 0) {
+    const float ng = powf(v, gamma);
+    return byte_of_float(ng * 255.0f);
+  }
+  float m = v;
+  if (gamma != 1.0f) m = (float)std::pow((double)m, (double)gamma);
+  m *= 255;
+  float t = m + 0.5f;
+  t = (t < 0) ? 0 : ((t > 255) ? 255 : t);
+  return byte_of_float(t);
+}
+uint32_t gamma_code_lookup(float v, const float* T) {
+  uint32_t vb, t0;
+  memcpy(&vb, &v, 4);
+  memcpy(&t0, &T[0], 4);
+  vb &= ~t0;  // T[0] is -0.0f for an even-integer gamma: the argument's magnitude decides
+  memcpy(&v, &vb, 4);
+  uint32_t lo = 0;
+  for (uint32_t step = (uint32_t)kGammaCodeN / 2; step; step >>= 1)
+    if (v >= T[lo + step]) lo += step;  // lo + step <= 255; a NaN or a negative v passes no comparison
+  return lo;
+}
+static bool make_gamma_code_set(float gamma, int form, float* T, float* min_gap, uint32_t* min_gap_ulps) {
+  auto flt = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
+  auto bits_of = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
+  auto code = [&](uint32_t u) { return gamma_code_direct(flt(u), gamma, form); };
+  const uint32_t hi = kGammaCodeHi0, top = (uint32_t)kGammaCodeN - 1;
+  // both ends of the domain, and what lies beyond them
+  if (code(0u) != 0u || code(bits_of(1.0f)) != top || code(hi) != top) return false;
+  // negative arguments: byte 0, or for an even-integer gamma the byte of the magnitude.  Form 0 sees none below about -1e-7 (the float /
+  // double log2 mismatch at gain == min_boost), and a product <= -1 would not narrow to 0 there.
+  const bool sym = fmodf(gamma, 2.0f) == 0.0f;
+  for (float neg : {-0.0f, -1e-30f, -1e-9f, -1e-6f, -0.5f, -3.0f, -FLT_MAX}) {
+    if (form == 0 && neg < -1e-6f) continue;
+    if (gamma_code_direct(neg, gamma, form) != (sym ? gamma_code_direct(-neg, gamma, form) : 0u)) return false;
+  }
+  if (form == 1)
+    for (float big : {1.5f, 7.0f, 1e10f, FLT_MAX})
+      if (gamma_code_direct(big, gamma, form) != top) return false;
+  T[0] = 0.0f;  // (the symmetry flag goes into its sign bit once the thresholds are checked)
+  uint32_t prev = 0;  // bits of T[k - 1]
+  for (uint32_t k = 1; k <= top; k++) {
+    // bracket the step from ((k - 0.5) / 255)^(1 / gamma) -- (k / 255)^(1 / gamma) for the truncating form --, widening by powers of
+    // two: lo has a byte below k (or is T[k - 1], which T[k] cannot undercut), up has one >= k
+    const double guess = std::pow(((double)k - (form ? 0.5 : 0.0)) / 255.0, 1.0 / (double)gamma);
+    uint32_t c = bits_of((float)(guess < 0.0 ? 0.0 : (guess > 1.0 ? 1.0 : guess)));
+    c = c < prev ? prev : (c > hi ? hi : c);
+    uint32_t lo = c, up = c;
+    if (code(c) >= k) {
+      for (uint32_t w = 1; lo > prev; w <<= 1) {
+        lo = lo - prev > w ? lo - w : prev;
+        if (code(lo) < k) break;
+        up = lo;
+      }
+      if (code(lo) >= k) { T[k] = flt(lo); prev = lo; continue; }  // lo == prev: the step sits on T[k - 1]
+    } else {
+      for (uint32_t w = 1; up < hi; w <<= 1) {
+        up = hi - up > w ? up + w : hi;
+        if (code(up) >= k) break;
+        lo = up;
+      }
+      if (code(up) < k) return false;  // not reached inside the domain
+    }
+    while (up - lo > 1) {  // code(lo) < k <= code(up)
+      const uint32_t mid = lo + (up - lo) / 2;
+      if (code(mid) >= k) up = mid;
+      else lo = mid;
+    }
+    T[k] = flt(up);
+    prev = up;
+  }
+  // the construction, checked on both sides of every step: the byte at every threshold, at its predecessor and half way to the
+  // next one, the order of the thresholds, and the lookup procedure at all of these points.  255 strictly increasing thresholds
+  // are required: a staircase of a byte function that skips or repeats a value is not what the reference's expression gives for
+  // a usable gamma.
+  *min_gap = INFINITY;
+  *min_gap_ulps = 0xFFFFFFFFu;
+  for (uint32_t k = 1; k <= top; k++) {
+    const uint32_t u = bits_of(T[k]);
+    if (!(T[k] > T[k - 1]) || u > hi || u == 0u) return false;
+    if (code(u) != k || code(u - 1) != k - 1) return false;
+    const uint32_t next = k < top ? bits_of(T[k + 1]) : hi;
+    const uint32_t mid = u + (next - u) / 2;
+    if (code(mid) != k) return false;
+    for (uint32_t probe : {u, u - 1, mid})
+      if (gamma_code_lookup(flt(probe), T) != code(probe)) return false;
+    if (k < top) {
+      if (T[k + 1] - T[k] < *min_gap) *min_gap = T[k + 1] - T[k];
+      if (next - u < *min_gap_ulps) *min_gap_ulps = next - u;
+    }
+  }
+  if (sym) T[0] = -0.0f;
+  for (float v : {0.0f, -0.0f, -1e-9f, -1e-6f, -0.5f, -3.0f, 1.0f, flt(hi), 7.0f})
+    if ((form == 1 || (v <= flt(hi) && v >= -1e-6f)) && gamma_code_lookup(v, T) != gamma_code_direct(v, gamma, form)) return false;
+  return *min_gap > 0.0f;
+}
+static GammaCodeTable make_gamma_code_table(float gamma) {
+  const auto t0 = std::chrono::steady_clock::now();
+  GammaCodeTable t;
+  t.gamma = gamma;
+  t.thr.assign(2 * (size_t)kGammaCodeN, INFINITY);
+  // 0, negative, NaN and infinite gammas have no table
+  bool ok = std::isfinite(gamma) && gamma > 0.0f;
+  for (int form = 0; form < 2 && ok; form++)
+    ok = make_gamma_code_set(gamma, form, t.thr.data() + (size_t)form * kGammaCodeN, &t.min_gap[form], &t.min_gap_ulps[form]);
+  t.exact = ok;
+  if (!ok) {
+    t.thr.assign(2 * (size_t)kGammaCodeN, INFINITY);
+    t.min_gap[0] = t.min_gap[1] = 0.0f;
+    t.min_gap_ulps[0] = t.min_gap_ulps[1] = 0u;
+  }
+  t.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return t;
+}
+const GammaCodeTable& gamma_code_table(float gamma) {
+  static std::mutex mu;
+  static std::vector<std::unique_ptr<GammaCodeTable>> cache;  // one per distinct gamma (bit pattern), for the life of the process
+  std::lock_guard<std::mutex> lk(mu);
+  for (const auto& e : cache)
+    if (!memcmp(&e->gamma, &gamma, 4)) return *e;
+  static const GammaCodeTable none;  // exact = false
+  if (cache.size() >= 256) return none;  // references stay valid: nothing is ever evicted; past 256 gammas a process keeps the pow route
+  cache.push_back(std::make_unique<GammaCodeTable>(make_gamma_code_table(gamma)));
+  return *cache.back();
+}
+
 // ---- step tables of the ENCODE side ------------------------------------------------------------------------------------
 // toneMap's last stage for RGBA8888 output: clampPixelFloat -> srgbOetf -> putRgba8888Pixel's byte
 // (jpegr.cpp:1976-1977, gainmapmath.cpp:139-148, 538-552) is a monotone step function of the linear value with 255
@@ -499,13 +641,16 @@ const std::vector<float>& srgb_inv_oetf_of_byte() {
 }
 // encodeGain (gainmapmath.cpp:758-771) after its clamp to [min_boost, max_boost], gamma == 1: the byte is a monotone
 // step function of the clamped gain, evaluated here through the kernels' own log2_table_f64 / div_by_const_f64.
-OetfBuckets gain_code8_buckets(float min_boost, float max_boost, float log2min, double log2_range, double log2_range_rcp) {
+// gamma != 1 (asked for by UHDR_HIP_GENERATE_GAMMA_TABLE only): the callback gains the reference's powf step -- the host libm's,
+// through gamma_code_direct -- and build_step_table's own verification decides whether the table is exact.
+OetfBuckets gain_code8_buckets(float min_boost, float max_boost, float log2min, double log2_range, double log2_range_rcp, float gamma) {
   const std::vector<double>& T = math_tables();
   auto code = [&](uint32_t u) -> uint32_t {
     float g;
     memcpy(&g, &u, 4);
     const double lg = log2_table_f64(g, T.data());
     const float n = (float)div_by_const_f64(lg - (double)log2min, log2_range, log2_range_rcp);
+    if (gamma != 1.0f) return gamma_code_direct(n, gamma, 0);
     return (uint32_t)(uint8_t)(n * 255.0f);
   };
   uint32_t lo, hi;
@@ -514,6 +659,7 @@ OetfBuckets gain_code8_buckets(float min_boost, float max_boost, float log2min, 
   OetfBuckets none;
   none.exact = false;
   if (!(min_boost > 0.0f) || !(max_boost > min_boost) || !std::isfinite(max_boost) || lo < 0x00800000u) return none;
+  if (!(gamma > 0.0f) || !std::isfinite(gamma)) return none;
   if (code(hi) < code(lo)) return none;
   for (uint32_t sh : {16u, 15u, 14u}) {
     OetfBuckets b = build_step_table(code, lo, hi, sh, kStepTabMax);

@@ -48,9 +48,28 @@ const GammaIndexTable& gamma_index_table(float gamma_inv);
 // the device's lookup (apply_gainmap.hip: gain_index) restated on the host: an estimate from float log2 / exp2, settled and
 // confirmed on two adjacent thresholds, else a binary search over T
 uint32_t gamma_index_lookup(float gain, const float* T, float gamma_inv);  // T = thr.data() + 1
+// generateGainMap with gamma != 1: the two byte functions of the encode side as thresholds over their float argument
+//   form 0 (one pass, encodeGain gainmapmath.cpp:769-770):    (uint8_t)(powf(n, gamma) * 255.0f)
+//   form 1 (two pass, affineMapGain gainmapmath.cpp:784-789): m = (float)pow((double)m, (double)gamma); clip(m * 255 + 0.5, 0, 255)
+// Domains: form 1 answers for EVERY finite float m (negative -> 0, anything from T[255] on -> 255); form 0
+// answers for every n of [-1e-6, kGammaCodeHi0 = four ulps past 1.0f] (negative -> 0), beyond which the reference's narrowing of a
+// product >= 256 or <= -1 is not a step function any more (encodeGain's n stays within an ulp of [0, 1]).  An even-integer gamma
+// maps a negative argument to the byte of its magnitude, as pow does: the sign bit of T[0] says so (host_tables.cpp).
+struct GammaCodeTable {
+  float gamma = 0.0f;
+  bool exact = false;            // both sets verified; false: no table for this gamma, the caller keeps the pow per sample
+  double build_ms = 0.0;         // host time of the construction, checks included
+  std::vector<float> thr;        // 2 x kGammaCodeN: form 0's T[0..255], then form 1's; T[0] = +-0, T[k] the smallest float whose byte is >= k
+  float min_gap[2] = {0, 0};     // the smallest T[k + 1] - T[k], k = 1..254, per form (the device table builder's bucket width)
+  uint32_t min_gap_ulps[2] = {0, 0};  // the same distance in bit patterns
+};
+constexpr uint32_t kGammaCodeHi0 = 0x3f800004u;  // bit pattern of the last float of form 0's domain
+uint32_t gamma_code_direct(float v, float gamma, int form);  // the reference's expression itself, with the host libm
+uint32_t gamma_code_lookup(float v, const float* T);         // the device's lookup (gamma_code.h) restated: eight steps over T[0..255]
+const GammaCodeTable& gamma_code_table(float gamma);
 // encode side (see host_tables.cpp): toneMap's sRGB byte, encodeGain's byte, RGBA1010102 code -> linear value
 const OetfBuckets& srgb_code8_buckets();
-OetfBuckets gain_code8_buckets(float min_boost, float max_boost, float log2min, double log2_range, double log2_range_rcp);
+OetfBuckets gain_code8_buckets(float min_boost, float max_boost, float log2min, double log2_range, double log2_range_rcp, float gamma = 1.0f);
 std::vector<float> lin10_table(const float* lut, int n);
 float gain_cap_ratio();                            // computeGain's 2.3f cap in the ratio domain (0: not representable)
 const std::vector<float>& srgb_inv_oetf_of_byte(); // 256: byte -> byte / 255.0f -> sRGB inverse-OETF table value

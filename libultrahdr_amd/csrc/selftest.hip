@@ -10,6 +10,10 @@
 //      (min, max) range: every bit pattern of the table's domain and a margin on both sides (generate_gainmap.hip)
 //   5  the GainLUT index of a gamma != 1 (gain_index.h): the estimate-and-settle lookup against the binary search over the
 //      same host-built thresholds, for every float from 0 to a few ulps past the last threshold
+//   6  the map byte of a gamma != 1 (gamma_code.h): the code of every float from eight ulps below zero to eight ulps past the last
+//      threshold lies between its two thresholds, T[code] <= v < T[code + 1]
+//   7  sweep 4 for the table minmax_table_kernel builds from a gamma's two-pass thresholds, against the per-sample evaluation
+//      that ends in gamma_code
 #include "cu_count.h"
 #include "encode_core.h"
 #include "gain_index.h"
@@ -82,8 +86,10 @@ __global__ __launch_bounds__(256) void sweep_srgb(unsigned long long* out, const
   if (blockIdx.x == 0 && threadIdx.x == 0) out[2] = n + 1;
 }
 
-// the per-sample composite of pass 2 (generate_gainmap.hip: affine_code, gamma 1) restated here against the device-built table
-__global__ __launch_bounds__(256) void sweep_affine(unsigned long long* out, const AffineDev* dev, int ch, const double* math_tab) {
+// the per-sample composite of pass 2 (generate_gainmap.hip: affine_code, gamma 1; thr non-null: affine_code_thr, the two-pass
+// thresholds of a gamma != 1) restated here against the device-built table
+template <bool GT>
+__global__ __launch_bounds__(256) void sweep_affine(unsigned long long* out, const AffineDev* dev, int ch, const double* math_tab, const float* thr) {
   __shared__ uint2 s_tab[kAffTabMax];
   const AffineTabDev td = dev->tab[ch];
   if (!td.ok) {
@@ -104,13 +110,43 @@ __global__ __launch_bounds__(256) void sweep_affine(unsigned long long* out, con
     const float q = __uint_as_float((uint32_t)i);
     const float g = (float)log2_table_f64(q, math_tab);
     float m = div_by_rcp64(g - mn, rr);
-    m *= 255.0f;
-    float t2 = m + 0.5f;
-    t2 = (t2 < 0.0f) ? 0.0f : ((t2 > 255.0f) ? 255.0f : t2);
-    if (step_code(q, s_tab, st) != (uint32_t)t2) bad++;
+    uint32_t want;
+    if constexpr (GT) {
+      want = gamma_code(m, thr);
+    } else {
+      m *= 255.0f;
+      float t2 = m + 0.5f;
+      t2 = (t2 < 0.0f) ? 0.0f : ((t2 > 255.0f) ? 255.0f : t2);
+      want = (uint32_t)t2;
+    }
+    if (step_code(q, s_tab, st) != want) bad++;
   }
   atomicAdd(&out[0], bad);
   if (blockIdx.x == 0 && threadIdx.x == 0) { out[1] = last - first + 1; out[2] = td.n; }
+}
+
+// thr: one set of kGammaCodeN thresholds (T[0] = +-0: -0 for an even-integer gamma, whose negative arguments take the byte of their
+// magnitude); last: the bit pattern the sweep ends at.  Every lane runs the search: there is no estimate that could spare it.
+__global__ __launch_bounds__(256) void sweep_gamma_code(unsigned long long* out, const float* thr, uint32_t last) {
+  __shared__ float s_thr[kGammaCodeN];
+  for (uint32_t i = threadIdx.x; i < (uint32_t)kGammaCodeN; i += 256) s_thr[i] = thr[i];
+  __syncthreads();
+  const float* T = s_thr;
+  const bool sym = (__float_as_uint(T[0]) >> 31) != 0;
+  unsigned long long bad = 0;
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i <= last; i += (uint64_t)gridDim.x * blockDim.x) {
+    const float v = __uint_as_float((uint32_t)i);
+    const uint32_t k = gamma_code(v, T);
+    const bool lower = k == 0 || T[k] <= v, upper = k == (uint32_t)kGammaCodeN - 1 || v < T[k + 1];
+    if (k >= (uint32_t)kGammaCodeN || !lower || !upper) bad++;
+  }
+  if (blockIdx.x == 0 && threadIdx.x <= 8) {  // -0 and the eight floats below it: byte 0, or the byte of the magnitude
+    const uint32_t u = 0x80000000u + threadIdx.x;
+    const uint32_t k = gamma_code(__uint_as_float(u), T);
+    if (k != (sym ? gamma_code(__uint_as_float(u & 0x7fffffffu), T) : 0u)) bad++;
+  }
+  atomicAdd(&out[0], bad);
+  if (blockIdx.x == 0 && threadIdx.x == 0) { out[1] = (unsigned long long)last + 1 + 9; out[2] = (unsigned long long)last + 1 + 9; }
 }
 
 // thr: one channel's kGammaThrN-float block (T[i] at [1 + i]); last: the bit pattern the sweep ends at
@@ -137,16 +173,25 @@ __global__ __launch_bounds__(256) void sweep_gain_index(unsigned long long* out,
 }  // namespace
 
 // out: 8 zero-initialised device words.  which 4: dev = the AffineDev + tables to check (built by launch_minmax_table), arg0 = channel
+// which 6: thr = the set to sweep, arg1 = the last bit pattern.  which 7: as 4, thr = the two-pass thresholds the table was built from
 hipError_t launch_selftest(int which, unsigned long long* out, uint32_t arg0, uint32_t arg1, uint32_t seed, const double* math_tab, const AffineDev* dev,
-                           hipStream_t s) {
+                           hipStream_t s, const float* thr) {
   const dim3 grid(device_cu_count() * 8), block(256);
   switch (which) {
     case 0: hipLaunchKernelGGL(sweep_rpi, grid, block, 0, s, out); break;
     case 1: hipLaunchKernelGGL(sweep_rcp, grid, block, 0, s, out); break;
     case 2: hipLaunchKernelGGL(sweep_div, grid, block, 0, s, out, seed, arg0, arg1); break;
     case 3: hipLaunchKernelGGL(sweep_srgb, grid, block, 0, s, out, math_tab); break;
-    case 4: hipLaunchKernelGGL(sweep_affine, grid, block, 0, s, out, dev, (int)arg0, math_tab); break;
+    case 4: hipLaunchKernelGGL(sweep_affine<false>, grid, block, 0, s, out, dev, (int)arg0, math_tab, (const float*)nullptr); break;
     case 5: hipLaunchKernelGGL(sweep_gain_index, grid, block, 0, s, out, (const float*)dev, arg0, arg1); break;  // dev: the threshold block
+    case 6:
+      if (!thr) return hipErrorInvalidValue;
+      hipLaunchKernelGGL(sweep_gamma_code, grid, block, 0, s, out, thr, arg1);
+      break;
+    case 7:
+      if (!thr) return hipErrorInvalidValue;
+      hipLaunchKernelGGL(sweep_affine<true>, grid, block, 0, s, out, dev, (int)arg0, math_tab, thr);
+      break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();

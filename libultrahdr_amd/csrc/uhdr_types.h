@@ -56,6 +56,10 @@ constexpr int kMaxIdwScaleLds = 8;  // idw tables up to 4*8*8*4 floats = 4 KiB l
 // (gainmapmath.h:483-489) as a step function of g -- thresholds T[0..1024] per channel, T[i] the smallest float whose index is
 // >= i, T[0] = 0, T[1024] = +inf (host_tables.cpp: gamma_index_table); padded to a multiple of four floats for 16-byte copies
 constexpr int kGammaThrN = 1028;
+// generateGainMap, gamma != 1 (UHDR_HIP_GENERATE_GAMMA_TABLE): the two byte functions of the encode side as thresholds over their
+// float argument (host_tables.cpp: gamma_code_table).  One block is 2 x kGammaCodeN floats: the one-pass set (encodeGain's powf and
+// truncation) first, then the two-pass set (affineMapGain's pow, + 0.5, clip); T[k] is the smallest float whose byte is >= k, T[0] = 0.
+constexpr int kGammaCodeN = 256;
 
 struct ApplyTables {  // layout of the device table block, in floats
   static constexpr int kSrgbOff = 0;
@@ -165,6 +169,9 @@ struct GenParams {
   // two pass
   float* gain_log2;          // map_w*map_h*(3|1): the float gain RATIOS (round 4; log2 of the six extrema only, see encode_core.h)
   float* minmax;             // 6 floats: the reference's log2 extrema
+  // gamma != 1 behind UHDR_HIP_GENERATE_GAMMA_TABLE (last, so no older field moves): the gamma's 2 x kGammaCodeN byte thresholds
+  // in global memory, or null -- the per-sample evaluation then keeps its powf
+  const float* gamma_thr;
 };
 
 // Two-pass generation: the final per-channel range and everything derived from it live in device memory, so the
@@ -196,6 +203,7 @@ struct AffineParams {
   float gamma;
   const AffineDev* dev;        // range + step tables (written by minmax_table_kernel); the tables follow at kAffineTablesOff
   const double* math_tab;      // exact_math.h tables in global memory (per-sample evaluation when a table is not ok)
+  const float* gamma_thr;      // UHDR_HIP_GENERATE_GAMMA_TABLE with gamma != 1: the two-pass byte thresholds (kGammaCodeN floats); else null
 };
 // One launch for everything between the passes (generate_gainmap.hip: minmax_table_kernel), one workgroup per channel:
 //   reduce    partials of pass 1 (ratio extrema) -> log2 extrema mm6 {min0..2, max0..2} (+ the {min, -max} form for the
@@ -221,6 +229,10 @@ struct MinmaxTableParams {
   AffineDev* dev;
   float gamma;
   const double* math_tab;
+  // UHDR_HIP_GENERATE_GAMMA_TABLE with gamma != 1: the two-pass byte thresholds (kGammaCodeN floats) and the smallest distance between
+  // two of them (in units of the normalised gain m), which sizes the buckets; null / 0: gamma != 1 gets no table, as before
+  const float* gamma_thr;
+  float gamma_gap;
 };
 
 // ---- toneMap -------------------------------------------------------------------------------------
@@ -273,8 +285,10 @@ int gen_coef_partials_count(const GenParams& p, int sampling);
 hipError_t launch_affine_map(const AffineParams& p, hipStream_t s);
 hipError_t launch_minmax_table(const MinmaxTableParams& p, hipStream_t s);
 // encode_api1_fused.hip
+// gamma_thr: the two-pass byte thresholds of a gamma != 1 (UHDR_HIP_GENERATE_GAMMA_TABLE) for channels without a step table; null: gamma is 1
 hipError_t launch_map_blocks(const float* ratio, const AffineDev* dev, const double* math_tab, int nch, int bw, int bh, const uint16_t* qt_luma,
-                             const uint16_t* qt_chroma, int16_t* const coef[3], uint8_t* map_out, uint32_t out_stride, hipStream_t s);
+                             const uint16_t* qt_chroma, int16_t* const coef[3], uint8_t* map_out, uint32_t out_stride, hipStream_t s,
+                             const float* gamma_thr = nullptr);
 hipError_t launch_map_blocks_onepass(const GenParams& g, int nch, const uint16_t* qt_luma, const uint16_t* qt_chroma, int16_t* const coef[3],
                                      uint8_t* map_out, uint32_t out_stride, hipStream_t s);
 hipError_t launch_base_blocks(const ImageView& yuv420, const Mat3* c, const uint16_t* qt_luma, const uint16_t* qt_chroma, int16_t* const coef[3],
@@ -282,7 +296,7 @@ hipError_t launch_base_blocks(const ImageView& yuv420, const Mat3* c, const uint
 hipError_t launch_base_blocks_rgba(const ImageView& rgba, const Rgb2Yuv& k, const Mat3* c, const uint16_t* qt_luma, const uint16_t* qt_chroma,
                                    int16_t* const coef[3], hipStream_t s);
 hipError_t launch_selftest(int which, unsigned long long* out, uint32_t arg0, uint32_t arg1, uint32_t seed, const double* math_tab, const AffineDev* dev,
-                           hipStream_t s);  // selftest.hip
+                           hipStream_t s, const float* thr = nullptr);  // selftest.hip
 int gen_partials_count(const GenParams& p);  // workgroups (= partials) launch_generate_gainmap(p, two_pass = true) writes
 hipError_t launch_encode_api0_fused(const FusedParams& p, bool two_pass, int* grid_out, hipStream_t s);
 bool encode_api0_p010_layout_ok(const ImageView& hdr, const ImageView& base420);  // quad_layout_ok (pixel_io.h) of both images

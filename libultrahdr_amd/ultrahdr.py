@@ -181,6 +181,21 @@ class UltraHdr:
         gm.sync_meta_from_raw()
         return md, gm
 
+    def generateGainMapEx(self, sdr_intent: Image, hdr_intent: Image, flags: int, sdr_is_601=False, use_luminance=True):
+        """generateGainMap with flags (uhdr_hip_generate_gainmap_ex / _ex_dev): 0 is generateGainMap, A.UHDR_HIP_GENERATE_GAMMA_TABLE
+        runs a gain-map gamma other than 1 through the host-built byte thresholds instead of a pow per sample (gainmapmath.cpp:769-770,
+        784-789): the reference's bytes.  Returns (metadata, gainmap Image)."""
+        dev = _is_dev(sdr_intent, hdr_intent)
+        mw, mh = self.gainmap_dims(sdr_intent.w, sdr_intent.h)
+        fmt = A.UHDR_IMG_FMT_24bppRGB888 if self.mUseMultiChannelGainMap else A.UHDR_IMG_FMT_8bppYCbCr400
+        gm = Image(fmt, mw, mh, align=64, device=sdr_intent.device)
+        md = A.GainmapMetadata()
+        cfg = self.encode_cfg(sdr_is_601, use_luminance)
+        fn = self.lib.uhdr_hip_generate_gainmap_ex_dev if dev else self.lib.uhdr_hip_generate_gainmap_ex
+        self._call(dev, fn, self.ctx.handle, C.byref(sdr_intent.raw), C.byref(hdr_intent.raw), C.byref(cfg), C.byref(md), C.byref(gm.raw), C.c_uint(flags))
+        gm.sync_meta_from_raw()
+        return md, gm
+
     def generateGainMapFromCoefficients(self, coefs, qtables, w: int, h: int, sdr_cg: int, hdr_intent: Image, sampling: str = "420",
                                         sdr_is_601=False, use_luminance=True, gm: Image = None):
         """generateGainMap on a 4:2:0 (sampling "420"), 4:2:2 ("422": uhdr_hip_generate_gainmap_coef422_dev) or 4:4:4 ("444":
@@ -415,6 +430,15 @@ class UltraHdr:
         uhdr_hip_encode_api1_scans_onepass for host images): same arguments, same returns."""
         return self.encodeApi1ScansAny(sdr_intent, hdr_intent, base_encoding, qt_base, qt_map, out_base, out_map, sdr_is_601, use_luminance,
                                        _fns=(self.lib.uhdr_hip_encode_api1_scans_onepass_dev, self.lib.uhdr_hip_encode_api1_scans_onepass))
+
+    def encodeApi1ScansEx(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, out_base, out_map, flags: int,
+                          sdr_is_601=False, use_luminance=True):
+        """encodeApi1ScansOnePass with generateGainMap's flags (uhdr_hip_encode_api1_scans_ex_dev for device images, uhdr_hip_encode_api1_scans_ex
+        for host images): with A.UHDR_HIP_GENERATE_GAMMA_TABLE a gain-map gamma other than 1 keeps the fused chain, both presets, evaluated
+        through the host's byte thresholds as generateGainMapEx evaluates it; flags 0 is encodeApi1ScansOnePass.  Same arguments, same returns."""
+        lib, fl = self.lib, C.c_uint(flags)
+        return self.encodeApi1ScansAny(sdr_intent, hdr_intent, base_encoding, qt_base, qt_map, out_base, out_map, sdr_is_601, use_luminance,
+                                       _fns=(lambda *a: lib.uhdr_hip_encode_api1_scans_ex_dev(*a, fl), lambda *a: lib.uhdr_hip_encode_api1_scans_ex(*a, fl)))
 
     def encodeApi1ScansAny(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, out_base, out_map,
                            sdr_is_601=False, use_luminance=True, _fns=None):
