@@ -389,6 +389,7 @@ uhdr_error_info_t uhdr_hip_huffman_decode_dev(uhdr_hip_ctx_t* c, const uhdr_hip_
   UHDR_TRY(check_scan(sc, true, &mpr, &mrows, &bpm));
   if (sc->restart_interval < 0 || sc->restart_interval > 65535) return err_status(UHDR_CODEC_INVALID_PARAM, "restart_interval %d out of range", sc->restart_interval);
   HIP_TRY(hipSetDevice(c->device));
+  c->huff_dc_dense = nullptr;
   if (!c->d_huff) {  // the zig-zag map lives behind the encoder's code tables
     std::vector<uint32_t> blob(host::jpeg_huff_code_tables());
     blob.resize((size_t)host::kHuffTabWords + 16);
@@ -606,6 +607,7 @@ uhdr_error_info_t uhdr_hip_huffman_decode_dev(uhdr_hip_ctx_t* c, const uhdr_hip_
     const bool scratch2 = form2 && !form3;
     const size_t scan_bytes = scratch2 ? (size_t)total_blocks * 64 * sizeof(int16_t) : 0;
     const size_t o_cs = scratch2 ? take(scan_bytes + 256) : 0;
+    const size_t o_dd = form3 ? take((size_t)total_blocks * sizeof(int16_t)) : 0;  // form 3: the DC terms on the side (HuffSyncArgs::dc_dense)
     UHDR_TRY(ensure(c->scratch[6], off));
     uint8_t* sb = (uint8_t*)c->scratch[6].p;
     HuffSyncArgs y;
@@ -649,6 +651,10 @@ uhdr_error_info_t uhdr_hip_huffman_decode_dev(uhdr_hip_ctx_t* c, const uhdr_hip_
       y.strag_cap = nsub * (uint32_t)bpm;
     }
     if (scratch2) y.coef_scan = (int16_t*)(sb + o_cs);
+    if (form3) {
+      y.dc_dense = (int16_t*)(sb + o_dd);
+      y.dc_no_scatter = c->huff_dc_side ? 1 : 0;
+    }
     y.total_mcus = (uint32_t)a.total_mcus;
     // lockstep levels of pass 1 before the stragglers get a wave each (0: all levels in lockstep, the round-4 form); restart files keep the lockstep form
     // (a lane walks a 1024-bit subsequence in ~33 us, a straggler's wave in ~10: 4K three-channel gain map 634 us with all 15
@@ -794,6 +800,8 @@ uhdr_error_info_t uhdr_hip_huffman_decode_dev(uhdr_hip_ctx_t* c, const uhdr_hip_
         if (fl[1] & 8u) return err_status(UHDR_CODEC_INVALID_PARAM, "corrupt entropy-coded data (the scan ends before its last block)");
         if (fl[1] & 2u) return err_status(UHDR_CODEC_INVALID_PARAM, "corrupt entropy-coded data (undefined Huffman code or a run past the end of a block)");
         sync_done = true;
+        // a form-3 attempt delivered (the loop ends with it) and did not scatter: term 0 of every block is on the side array
+        if (hyp_done && y.write_form == 3 && y.dc_no_scatter) c->huff_dc_dense = y.dc_dense;
       } else {  // not settled: start over on the serial path
         if (a.nseg == 1 && !c->huff_serial_ok && data_bytes > (256u << 10)) {
           c->stats.entropy_decode_declined++;

@@ -116,6 +116,12 @@ struct uhdr_hip_ctx {
   DeviceBuf scratch[8];
   uhdr_hip_stats_t stats = {};    // uhdr_hip_get_stats: which route the entropy stage took, call by call
   bool huff_serial_ok = true;  // uhdr_hip_jpeg_decode_scan clears it: a large marker-less scan that the parallel decoder cannot settle goes back to the caller
+  // entropy decode, write form 3 (HuffSyncArgs::dc_dense).  huff_dc_side, set around one call by a caller that owns the coefficient arrays and reads
+  // term 0 from the side array (decode_api1_scans_impl, the gain map's scan): a form-3 attempt does not scatter the predicted DC terms.
+  // huff_dc_dense, set by every uhdr_hip_huffman_decode_dev call: that side array (in scratch[6], good until this context's next decode) when such
+  // an attempt delivered the scan; nullptr on every other route (form 2, the rounds, intervals, one lane), where the arrays are whole
+  bool huff_dc_side = false;
+  const int16_t* huff_dc_dense = nullptr;
   // marker-less Huffman encoder: the per-segment bit slots of the one-walk route (huffman_encode.hip), and the switch that keeps the
   // two-pass route instead (UHDR_HIP_HUFF_TWO_PASS, read once when the context is created; the auxiliary context reads it the same way)
   DeviceBuf huff_slots;

@@ -1107,9 +1107,10 @@ uhdr_error_info_t uhdr_hip_jpeg_ycc_to_rgb(uhdr_hip_ctx_t* c, const uhdr_raw_ima
 }
 
 // 3-channel gain map: dequant + IDCT of the three components + ycc_rgb_convert in one pass
-uhdr_error_info_t uhdr_hip_idct_dequant_rgb_dev(uhdr_hip_ctx_t* c, const int16_t* coef_y, const int16_t* coef_cb, const int16_t* coef_cr,
-                                                int bw, int bh, const uint16_t qt_luma[64], const uint16_t qt_chroma[64], int variant,
-                                                uhdr_raw_image_t* rgb) {
+// dc_dense (internal callers): the blocks' term 0 on the entropy decoder's side array (uhdr_hip_ctx::huff_dc_dense); nullptr: in the arrays
+static uhdr_error_info_t idct_dequant_rgb_impl(uhdr_hip_ctx_t* c, const int16_t* coef_y, const int16_t* coef_cb, const int16_t* coef_cr, int bw, int bh,
+                                               const uint16_t qt_luma[64], const uint16_t qt_chroma[64], int variant, uhdr_raw_image_t* rgb,
+                                               const int16_t* dc_dense) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!coef_y || !coef_cb || !coef_cr || !qt_luma || !qt_chroma || !rgb || !rgb->planes[0] || bw <= 0 || bh <= 0)
     return err_status(UHDR_CODEC_INVALID_PARAM, "received bad argument for idct_dequant_rgb");
@@ -1127,8 +1128,13 @@ uhdr_error_info_t uhdr_hip_idct_dequant_rgb_dev(uhdr_hip_ctx_t* c, const int16_t
   HIP_TRY(hipSetDevice(c->device));
   rgb->range = UHDR_CR_FULL_RANGE;
   ProfScope ps(c, "idct_dequant");
-  HIP_TRY(launch_idct_dequant_rgb(coef_y, coef_cb, coef_cr, bw, bh, qt_luma, qt_chroma, variant, view_mut_of(rgb), c->stream));
+  HIP_TRY(launch_idct_dequant_rgb(coef_y, coef_cb, coef_cr, bw, bh, qt_luma, qt_chroma, variant, view_mut_of(rgb), c->stream, dc_dense));
   return ok_status();
+}
+uhdr_error_info_t uhdr_hip_idct_dequant_rgb_dev(uhdr_hip_ctx_t* c, const int16_t* coef_y, const int16_t* coef_cb, const int16_t* coef_cr,
+                                                int bw, int bh, const uint16_t qt_luma[64], const uint16_t qt_chroma[64], int variant,
+                                                uhdr_raw_image_t* rgb) {
+  return idct_dequant_rgb_impl(c, coef_y, coef_cb, coef_cr, bw, bh, qt_luma, qt_chroma, variant, rgb, nullptr);
 }
 
 // JpegEncoderHelper::compressImage's sample -> entropy-coded-data part (jpegencoderhelper.cpp:131-309) on the device: FDCT +
@@ -1652,10 +1658,17 @@ static uhdr_error_info_t decode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_hi
   for (int i = 0; i < nm; i++) { o_map[i] = off; off += ((size_t)sm.blocks_w[i] * sm.blocks_h[i] * 128 + 255) & ~(size_t)255; }
   UHDR_TRY(ensure(c->enc[0], off));
   for (int i = 0; i < nm; i++) sm.coef[i] = (const int16_t*)((const uint8_t*)c->enc[0].p + o_map[i]);
+  // a three-channel map's arrays are read by one kernel of this function alone: it takes term 0 of every block from the entropy decoder's side
+  // array where a form-3 attempt delivers the scan, and that attempt leaves the scatter out (the map's scan runs on the auxiliary context)
+  uhdr_hip_ctx* x = nullptr;
+  UHDR_TRY(aux_context(c, &x));
+  x->huff_dc_side = nm == 3;
   c->huff_serial_ok = false;  // a scan the parallel decoder declines goes back to the caller (UNSUPPORTED_FEATURE), not to one lane
   const uhdr_error_info_t hs = uhdr_hip_huffman_decode2_dev(c, &sb, tables_of(base), base_data, base_bytes, &sm, tables_of(map), map_data, map_bytes);
   c->huff_serial_ok = true;
+  x->huff_dc_side = false;
   if (hs.error_code != UHDR_CODEC_OK) return hs;
+  const int16_t* map_dc = nm == 3 ? x->huff_dc_dense : nullptr;  // nullptr: another route delivered, the arrays are whole
   // the decoded gain-map image, device resident
   uhdr_raw_image_t gm;
   memset(&gm, 0, sizeof gm);
@@ -1670,7 +1683,7 @@ static uhdr_error_info_t decode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_hi
     UHDR_TRY(ensure(c->jpg[4], pitch_px * 4 * sm.h));
     gm.planes[0] = c->jpg[4].p;
     gm.stride[0] = (unsigned int)pitch_px;
-    UHDR_TRY(uhdr_hip_idct_dequant_rgb_dev(c, sm.coef[0], sm.coef[1], sm.coef[2], sm.blocks_w[0], sm.blocks_h[0], map->qtable[0], map->qtable[1], libjpeg_variant, &gm));
+    UHDR_TRY(idct_dequant_rgb_impl(c, sm.coef[0], sm.coef[1], sm.coef[2], sm.blocks_w[0], sm.blocks_h[0], map->qtable[0], map->qtable[1], libjpeg_variant, &gm, map_dc));
   } else {
     gm.fmt = UHDR_IMG_FMT_8bppYCbCr400;
     const size_t pitch = ((size_t)sm.blocks_w[0] * 8 + 63) & ~(size_t)63;

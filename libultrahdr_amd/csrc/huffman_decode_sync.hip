@@ -792,6 +792,10 @@ struct __attribute__((aligned(16))) Write2Lds {  // == the layout of HuffSyncArg
 // makes them behind its own table read; LDS returns in order, so the wait for the table entry covers the indices.  The last step's pair is
 // stored behind the loop.  Every store lies inside [coef[b] + 64 m, + 64) with b < ncomp and m < total_mcus, whatever the start state: a lost
 // attempt's garbage stays inside the arrays.
+// The DC difference does not go to term 0 of its JBLOCK but to dc_dense[t] (HuffSyncArgs::dc_dense), t the block's place in the scan: the step that
+// starts a block (k == 0) decodes the DC symbol first, so its first carried store takes the side array's element as its base -- the index read gives
+// nat[0] = 0 -- and is made whatever the difference (zero too: the side array gets no fill).  A select on the store's base and one pointer bump per
+// block; t < total_blocks wherever blk < total_mcus and b < ncomp, so a lost attempt's garbage stays inside dc_dense as well.
 template <bool JB>
 __device__ __forceinline__ void write_span2(const HuffSyncArgs& a, const Staged& st, uint32_t region_bit, const Write2Lds& L, uint32_t p, uint32_t b, uint32_t k,
                                             uint32_t end_bit, uint32_t& nblk, uint32_t blk, const uint32_t* __restrict__ nat = nullptr) {
@@ -822,8 +826,10 @@ __device__ __forceinline__ void write_span2(const HuffSyncArgs& a, const Staged&
   }
   uint32_t cls = JB ? (b ? 2u : 0u) : (((cpack >> (2u * b)) & 3u) ? 2u : 0u);
   int16_t* dst = JB ? a.coef[b] + (size_t)min(blk, limit) * 64 : a.coef_scan + (size_t)blk * 64;
+  int16_t* dcp = JB ? a.dc_dense + ((size_t)min(blk, limit) * bpm + b) : nullptr;  // JB: this block's DC difference
   // JB: the stores of the step before
   int16_t* pdst = dst;
+  int16_t* pdst1 = dst;  // ... the first one's base: pdst, or the DC difference's place
   uint32_t pn1 = 0, pn2 = 0;
   int pv1 = 0, pv2 = 0;
   bool ps1 = false, ps2 = false;
@@ -834,8 +840,9 @@ __device__ __forceinline__ void write_span2(const HuffSyncArgs& a, const Staged&
     const uint32_t ti = cls + (k ? 1u : 0u);
     const uint2 e = P[ti * (uint32_t)kHuffPairWords + (w16 >> (16 - kHuffPairBits))];
     uint32_t e1 = e.x, e2 = e.y;
+    const bool dc1 = JB && k == 0u;  // the first symbol of this step is the block's DC difference
     if (JB) {
-      if (ps1) pdst[pn1] = (int16_t)pv1;
+      if (ps1) pdst1[pn1] = (int16_t)pv1;
       if (ps2) pdst[pn2] = (int16_t)pv2;
     }
     if (__builtin_amdgcn_ballot_w64((e1 >> 31) != 0) != 0) {  // a code longer than the index: its sub-table, one symbol
@@ -860,8 +867,9 @@ __device__ __forceinline__ void write_span2(const HuffSyncArgs& a, const Staged&
       pn1 = nat[zz1 & 63u];
       pn2 = nat[zz2 & 63u];
       pdst = dst;
+      pdst1 = dc1 ? dcp : dst;
       pv1 = v1; pv2 = v2;
-      ps1 = sz1 != 0 && !over1;
+      ps1 = dc1 || (sz1 != 0 && !over1);  // (a DC symbol without magnitude bits has v1 == 0)
       ps2 = sz2 != 0 && !over2;
     } else {
       if (sz1 != 0 && !over1) dst[zz1] = (int16_t)v1;
@@ -875,6 +883,7 @@ __device__ __forceinline__ void write_span2(const HuffSyncArgs& a, const Staged&
       if constexpr (JB) {
         const bool last = b + 1u == bpm;
         dst += dA;
+        dcp++;
         const ptrdiff_t t = dA;
         dA = dB; dB = dC; dC = t;
         b = last ? 0u : b + 1u;
@@ -892,7 +901,7 @@ __device__ __forceinline__ void write_span2(const HuffSyncArgs& a, const Staged&
     }
   }
   if (JB) {
-    if (ps1) pdst[pn1] = (int16_t)pv1;
+    if (ps1) pdst1[pn1] = (int16_t)pv1;
     if (ps2) pdst[pn2] = (int16_t)pv2;
   }
   if (bad) atomicOr(a.flags + 1, 2u);
@@ -1735,8 +1744,9 @@ __global__ __launch_bounds__(kPlaceChunk) void coef_place_kernel(const HuffSyncA
     dst[lane & 31u] = lo | (hi << 16);
   }
 }
-// form 3 of the write pass: the DC differences sit at [0] of every JBLOCK of the component arrays, and scan position t is JBLOCK t / ncomp of
-// component t % ncomp.  The prediction happens in place, on term 0 alone: per-chunk sums per component, then carry-in + in-chunk scan + store
+// form 3 of the write pass: the DC differences sit in dc_dense[] (scan order; term 0 of every JBLOCK is zero), and scan position t is JBLOCK
+// t / ncomp of component t % ncomp.  The prediction happens on the side array: per-chunk sums per component, then carry-in + in-chunk scan + store
+// back to dc_dense[t] and -- unless the consumer reads the side array (dc_no_scatter) -- to term 0 of the JBLOCK
 // (same chunks, same int sums and the same final cast as coef_place_kernel; partial / self_prefix as there).
 __device__ __forceinline__ int16_t* dc_term3(const HuffSyncArgs& a, uint32_t t, int& c) {
   const uint32_t n = (uint32_t)a.ncomp, m = t / n;
@@ -1749,11 +1759,7 @@ __global__ __launch_bounds__(kPlaceChunk) void dc_partial3_kernel(const HuffSync
   const int tid = (int)threadIdx.x;
   const uint32_t t = blockIdx.x * (uint32_t)kPlaceChunk + (uint32_t)tid;
   int v[3] = {0, 0, 0};
-  if (t < a.total_blocks) {
-    int c;
-    const int16_t* d = dc_term3(a, t, c);
-    v[c] = *d;
-  }
+  if (t < a.total_blocks) v[t % (uint32_t)a.ncomp] = a.dc_dense[t];
   dc_chunk_scan(v, s_sum, tid);
   if (tid == kPlaceChunk - 1) { partial[blockIdx.x * 3] = v[0]; partial[blockIdx.x * 3 + 1] = v[1]; partial[blockIdx.x * 3 + 2] = v[2]; }
 }
@@ -1763,10 +1769,9 @@ __global__ __launch_bounds__(kPlaceChunk) void dc_apply3_kernel(const HuffSyncAr
   const uint32_t t = blockIdx.x * (uint32_t)kPlaceChunk + (uint32_t)tid;
   int v[3] = {0, 0, 0};
   int c = 0;
-  int16_t* d = nullptr;
   if (t < a.total_blocks) {
-    d = dc_term3(a, t, c);
-    v[c] = *d;
+    c = (int)(t % (uint32_t)a.ncomp);
+    v[c] = a.dc_dense[t];
   }
   int carry[3];
   if (self_prefix) {
@@ -1783,7 +1788,13 @@ __global__ __launch_bounds__(kPlaceChunk) void dc_apply3_kernel(const HuffSyncAr
     carry[2] = partial[blockIdx.x * 3 + 2];
   }
   dc_chunk_scan(v, s_sum, tid);
-  if (d) *d = (int16_t)((c == 0 ? carry[0] : (c == 1 ? carry[1] : carry[2])) + v[c]);
+  if (t >= a.total_blocks) return;
+  const int16_t dc = (int16_t)((c == 0 ? carry[0] : (c == 1 ? carry[1] : carry[2])) + v[c]);
+  a.dc_dense[t] = dc;
+  if (!a.dc_no_scatter) {
+    int cc;
+    *dc_term3(a, t, cc) = dc;
+  }
 }
 __global__ __launch_bounds__(1024) void dc_scan_partials_kernel(int* __restrict__ partial, int nchunks) {  // exclusive, in place
   __shared__ int s_sum[3 * 16];
@@ -1946,7 +1957,7 @@ static void launch_write2(const HuffSyncArgs& a, uint32_t nsub, int final_buf, h
   }
   hipLaunchKernelGGL(sync_write2_kernel<false>, dim3(grid), dim3(threads), lds, s, a, final_buf);
 }
-// form 3: the DC prediction in place (dc_partial3_kernel, dc_apply3_kernel)
+// form 3: the DC prediction on the side array (dc_partial3_kernel, dc_apply3_kernel)
 static void launch_dc3(const HuffSyncArgs& a, int* dc_partial, hipStream_t s) {
   const int nch = (int)((a.total_blocks + kPlaceChunk - 1) / kPlaceChunk);
   hipLaunchKernelGGL(dc_partial3_kernel, dim3(nch), dim3(kPlaceChunk), 0, s, a, dc_partial);

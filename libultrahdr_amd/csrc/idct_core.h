@@ -67,10 +67,11 @@ __device__ __forceinline__ void idct_1d(const int in[8], int out[8]) {
 // Lane (row rr, block rb) fetches and dequantizes its coefficient row of block (by, bx); `big` collects the
 // magnitude bits that rule out the 24-bit multiply path.
 __device__ __forceinline__ void load_dequant_row(const int16_t* __restrict__ coef, int bw, int by, int bx, int rr,
-                                                 const int q[8], int v[8], int& big, bool row_ok = true) {
+                                                 const int q[8], int v[8], int& big, bool row_ok = true, bool dc_put = false, uint32_t dc = 0) {
   if (bx < bw && row_ok) {
     const uint4 raw = *(const uint4*)(coef + ((size_t)by * bw + bx) * 64 + rr * 8);
-    const uint32_t w4[4] = {raw.x, raw.y, raw.z, raw.w};
+    // dc_put (the lane of row 0): the block's term 0 is the low half of dc, not what the array holds
+    const uint32_t w4[4] = {dc_put ? (raw.x & 0xffff0000u) | (dc & 0xffffu) : raw.x, raw.y, raw.z, raw.w};
 #pragma unroll
     for (int c = 0; c < 4; c++) {
       v[2 * c] = __mul24((int)(int16_t)(w4[c] & 0xffff), q[2 * c]);  // |coef| < 2^15, q < 2^16: exact

@@ -179,9 +179,15 @@ struct IdctRgbArgs {
   int bw, bh;
   int k_cr_g, k_cb_g;
   uint16_t q[2][64];  // luma, chroma (natural order)
+  // != nullptr: term 0 of block (by, bx) of component c is dc_dense[(by * bw + bx) * 3 + c] (the entropy decoder's side array,
+  // HuffSyncArgs::dc_dense, scan order) and zero in the arrays
+  const int16_t* dc_dense;
 };
 
-template <int BPP>
+// DENSE: term 0 from IdctRgbArgs::dc_dense.  A kernel of its own: the plain one sits at 72 VGPRs, the last count that keeps seven waves on a SIMD,
+// and so must this one -- the term goes into the raw coefficient word in front of the dequantization (load_dequant_row's dc_put), nothing of it
+// lives beyond the row loads.
+template <int BPP, bool DENSE>
 __global__ __launch_bounds__(kBlock) void idct_dequant_rgb_kernel(const IdctRgbArgs a) {
   __shared__ int s_ws[kBlock / 64][8 * 8 * 9];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -201,9 +207,22 @@ __global__ __launch_bounds__(kBlock) void idct_dequant_rgb_kernel(const IdctRgbA
     // all three coefficient rows are requested before the first transform starts
     int vy[8], vb[8], vr[8];
     int big_y = 0, big_b = 0, big_r = 0;
-    load_dequant_row(a.coef[0], bw, by, bx, rr, ql, vy, big_y);
-    load_dequant_row(a.coef[1], bw, by, bx, rr, qc, vb, big_b);
-    load_dequant_row(a.coef[2], bw, by, bx, rr, qc, vr, big_r);
+    // DENSE: the lane of row 0 takes term 0 of its three blocks from the side array (Y and Cb share a register on their way)
+    uint32_t dc_yb = 0, dc_r = 0;
+    const bool dc_put = DENSE && rr == 0;
+    if constexpr (DENSE) {
+      if (rr == 0 && bx < bw) {
+        uint32_t m = (uint32_t)(by * bw + bx);  // the block's number, as the row loads compute it
+        // (hidden from the loop optimizer: it would keep 3 m as a second induction variable, the 73rd register)
+        asm volatile("" : "+v"(m));
+        const uint32_t m3 = m * 3u;
+        dc_yb = (uint32_t)(uint16_t)a.dc_dense[m3] | ((uint32_t)(uint16_t)a.dc_dense[m3 + 1u] << 16);
+        dc_r = (uint16_t)a.dc_dense[m3 + 2u];
+      }
+    }
+    load_dequant_row(a.coef[0], bw, by, bx, rr, ql, vy, big_y, true, dc_put, dc_yb);
+    load_dequant_row(a.coef[1], bw, by, bx, rr, qc, vb, big_b, true, dc_put, dc_yb >> 16);
+    load_dequant_row(a.coef[2], bw, by, bx, rr, qc, vr, big_r, true, dc_put, dc_r);
     uint32_t sy[8], sb[8], sr[8];
     idct_wave(ws, vy, big_y, rr, rb, sy);
     idct_wave(ws, vb, big_b, rr, rb, sb);
@@ -234,9 +253,10 @@ hipError_t launch_idct_dequant(const int16_t* coef, int bw, int bh, const uint16
 
 hipError_t launch_idct_dequant_rgb(const int16_t* coef_y, const int16_t* coef_cb, const int16_t* coef_cr, int bw, int bh,
                                    const uint16_t* qt_luma_host, const uint16_t* qt_chroma_host, int variant,
-                                   const ImageViewMut& rgb, hipStream_t s) {
+                                   const ImageViewMut& rgb, hipStream_t s, const int16_t* dc_dense) {
   IdctRgbArgs a = {};
   a.coef[0] = coef_y; a.coef[1] = coef_cb; a.coef[2] = coef_cr;
+  a.dc_dense = dc_dense;
   a.rgb = (uint8_t*)rgb.p[0];
   const int bpp = rgb.fmt == UHDR_IMG_FMT_32bppRGBA8888 ? 4 : 3;
   a.pitch = (size_t)rgb.stride[0] * bpp;
@@ -245,8 +265,11 @@ hipError_t launch_idct_dequant_rgb(const int16_t* coef_y, const int16_t* coef_cb
   for (int i = 0; i < 64; i++) { a.q[0][i] = qt_luma_host[i]; a.q[1][i] = qt_chroma_host[i]; }
   const int total = ((bw + 7) / 8) * bh;
   const int grid = resident_grid((uint32_t)(total + 3) / 4, 8);
-  if (bpp == 4) hipLaunchKernelGGL((idct_dequant_rgb_kernel<4>), dim3(grid), dim3(kBlock), 0, s, a);
-  else hipLaunchKernelGGL((idct_dequant_rgb_kernel<3>), dim3(grid), dim3(kBlock), 0, s, a);
+  if (dc_dense) {  // the fused API-1 decode's map: RGBA8888 (there is no RGB888 form of the dense kernel: a missing kernel is an error)
+    if (bpp != 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((idct_dequant_rgb_kernel<4, true>), dim3(grid), dim3(kBlock), 0, s, a);
+  } else if (bpp == 4) hipLaunchKernelGGL((idct_dequant_rgb_kernel<4, false>), dim3(grid), dim3(kBlock), 0, s, a);
+  else hipLaunchKernelGGL((idct_dequant_rgb_kernel<3, false>), dim3(grid), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 

@@ -461,9 +461,15 @@ struct HuffSyncArgs {
   int16_t* coef_scan;
   // write pass, form 3 (marker-less scans whose components are all sampled 1x1, hypothesis attempts): block t of the scan IS JBLOCK
   // t / ncomp of component t % ncomp, so the write pass stores straight into the (zero-initialised) component arrays -- natural order, the
-  // DC DIFFERENCE at [0] -- and two small kernels turn the differences into predictions in place.  No scan-order scratch, no placing pass.
+  // DC DIFFERENCE on the side (dc_dense below) -- and two small kernels turn the differences into predictions.  No scan-order scratch, no placing pass.
   int write_form;        // 3: that form; else coef_scan decides between 2 and 1
   uint32_t total_mcus;   // form 3: JBLOCKs per component
+  // form 3, the DC terms on the side: the write pass stores block t's DC DIFFERENCE into dc_dense[t] (t = JBLOCK index x ncomp + component, i.e.
+  // scan order; every block's, a zero difference too: no fill needed) and leaves term 0 of the JBLOCK to pass 0's zero fill; dc_partial3_kernel /
+  // dc_apply3_kernel read 2 dense bytes per block (not one term per 128-byte block), the latter writes the PREDICTED value back to dc_dense[t] and
+  // scatters it to term 0 of the JBLOCK -- unless dc_no_scatter: a consumer that takes term 0 from dc_dense itself (launch_idct_dequant_rgb)
+  int16_t* dc_dense;     // [total_blocks]
+  int dc_no_scatter;
   // round 6: pass 0 zero-fills what the write pass stores into on the side (its lanes wait on table lookups, the memory system is idle):
   // zero_vec[r] 16-byte pieces from zero_ptr[r], grid-stride -- form 2's scratch is one region, form 3's component arrays up to three
   // (a caller's arrays need not be contiguous); all 0: the host has enqueued fills instead (the rounds scheme)
@@ -517,7 +523,9 @@ hipError_t launch_idct_dequant(const int16_t* coef, int bw, int bh, const uint16
                                size_t stride, hipStream_t s);
 hipError_t launch_idct_dequant_rgb(const int16_t* coef_y, const int16_t* coef_cb, const int16_t* coef_cr, int bw, int bh,
                                    const uint16_t* qt_luma_host, const uint16_t* qt_chroma_host, int variant,
-                                   const ImageViewMut& rgb, hipStream_t s);
+                                   const ImageViewMut& rgb, hipStream_t s, const int16_t* dc_dense = nullptr);
+// (dc_dense != nullptr: term 0 of block (by, bx) of component c comes from dc_dense[(by * bw + bx) * 3 + c] -- HuffSyncArgs::dc_dense of a
+// three-component scan -- and the arrays hold zero there)
 // jpeg_upsample.hip: 4:2:0 (vsamp 2) or 4:2:2 (vsamp 1: 2x1 / 1x1 / 1x1, the chroma grids cover ceil(w/2) x h samples) coefficient
 // blocks -> packed RGB888 / RGBA8888, libjpeg-turbo (0) or IJG 9 (1) chroma reconstruction
 size_t upsample_scratch_bytes(const int bw[3], const int bh[3]);
