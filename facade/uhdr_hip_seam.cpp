@@ -303,9 +303,18 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
   const unsigned w = sdr_intent->w, h = sdr_intent->h;
   const int s = *scale_factor;
   const unsigned grid = rgba ? 8 : 16;  // whole MCUs: 1x1 / 1x1 / 1x1 sampling for RGBA8888, 2x2 / 1x1 / 1x1 otherwise
-  if (w == 0 || h == 0 || w % grid || h % grid || w > 65535 || h > 65535) return false;
+  if (w == 0 || h == 0 || w > 65535 || h > 65535) return false;
   const unsigned mw = w / (unsigned)s, mh = h / (unsigned)s;
-  if (mw == 0 || mh == 0 || mw % 8 || mh % 8) return false;  // (the tiny-image fallback of jpegr.cpp:690-706 stays with generate_gainmap)
+  if (mw == 0 || mh == 0) return false;  // (the tiny-image fallback of jpegr.cpp:690-706 stays with generate_gainmap)
+  // a 4:2:0 frame that is not whole MCUs (1920 x 1080) or whose map is not whole blocks takes the fused route only when asked to:
+  // UHDR_HIP_SEAM_FUSED_EDGES hands it to uhdr_hip_encode_api1_scans_edges, which makes up the samples beyond the frame the way
+  // JpegEncoderHelper::compressYCbCr does; without it the per-stage seams run as before.  The preset and gamma conditions above stay what they are.
+  bool edges = false;
+  if (w % grid || h % grid || mw % 8 || mh % 8) {
+    if (rgba || sdr_intent->fmt != UHDR_IMG_FMT_12bppYCbCr420 || w % 2 || h % 2 || !getenv("UHDR_HIP_SEAM_FUSED_EDGES")) return false;
+    if ((preset == UHDR_USAGE_REALTIME && !realtime) || (gamma != 1.0f && !gamma_ex)) return false;  // (what the whole-MCU entry points decline)
+    edges = true;
+  }
   if (base_icc_size > 65533 || map_icc_size > 65533 || (map_comment && strlen(map_comment) > 65533)) return false;
   if (base_quality < 0 || base_quality > 100 || map_quality < 0 || map_quality > 100) return false;
   enter();
@@ -332,13 +341,13 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
   sb.num_components = 3;
   sb.w = w; sb.h = h;
   for (int i = 0; i < 3; i++) {
-    sb.blocks_w[i] = (int)(i ? w / grid : w / 8);
-    sb.blocks_h[i] = (int)(i ? h / grid : h / 8);
+    sb.blocks_w[i] = (int)(i ? (w + grid - 1) / grid : (w + 7) / 8);  // (libjpeg's width_in_blocks: real blocks)
+    sb.blocks_h[i] = (int)(i ? (h + grid - 1) / grid : (h + 7) / 8);
     sb.h_samp[i] = sb.v_samp[i] = (i || rgba) ? 1 : 2;
   }
   sm.num_components = nch;
   sm.w = mw; sm.h = mh;
-  for (int i = 0; i < nch; i++) { sm.blocks_w[i] = (int)(mw / 8); sm.blocks_h[i] = (int)(mh / 8); sm.h_samp[i] = sm.v_samp[i] = 1; }
+  for (int i = 0; i < nch; i++) { sm.blocks_w[i] = (int)((mw + 7) / 8); sm.blocks_h[i] = (int)((mh + 7) / 8); sm.h_samp[i] = sm.v_samp[i] = 1; }
   unsigned char hb[2048], hm[2048];
   const unsigned char none = 0;
   const size_t nhb = uhdr_hip_jpeg_assemble(&sb, qt_base[0], qt_base[1], &none, 0, hb, sizeof hb);
@@ -348,6 +357,10 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
   auto lead = [](size_t nh, size_t icc, const char* com) { return 20 + (icc ? 4 + icc : 0) + (com ? 4 + strlen(com) : 0) + (nh - 22); };
   const size_t lead_b = lead(nhb, base_icc ? base_icc_size : 0, nullptr), lead_m = lead(nhm, map_icc ? map_icc_size : 0, map_comment);
   size_t cap_b = (rgba ? (size_t)w * h * 3 : (size_t)w * h * 3 / 2) + (1u << 16), cap_m = (size_t)mw * mh * nch + (1u << 16);  // one byte per coefficient: never seen exceeded
+  if (edges) {  // ... of the blocks there are, not of w * h
+    cap_b = ((size_t)sb.blocks_w[0] * sb.blocks_h[0] + 2 * (size_t)sb.blocks_w[1] * sb.blocks_h[1]) * 64 + (1u << 16);
+    cap_m = (size_t)sm.blocks_w[0] * sm.blocks_h[0] * 64 * nch + (1u << 16);
+  }
   if (const char* e = getenv("UHDR_HIP_SEAM_TEST_SMALL_CAP")) {  // (tests: the second attempt below)
     const size_t div = (size_t)(atoi(e) > 1 ? atoi(e) : 16);
     cap_b /= div;
@@ -363,7 +376,11 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
     out->gainmap_data.reset(new (std::nothrow) unsigned char[lead_m + cap_m + 2]);
     if (!out->base_data || !out->gainmap_data) return false;
     nb = nm = 0;
-    if (gamma_ex)
+    if (edges)
+      *st = uhdr_hip_encode_api1_scans_edges(cur(), sdr_intent, hdr_intent, &cfg, UHDR_CG_DISPLAY_P3, qt_base, qt_map, &md, &gm_desc,
+                                             out->base_data.get() + lead_b, cap_b, &nb, out->gainmap_data.get() + lead_m, cap_m, &nm,
+                                             gamma_ex ? UHDR_HIP_GENERATE_GAMMA_TABLE : 0u);
+    else if (gamma_ex)
       *st = uhdr_hip_encode_api1_scans_ex(cur(), sdr_intent, hdr_intent, &cfg, UHDR_CG_DISPLAY_P3, qt_base, qt_map, &md, &gm_desc,
                                           out->base_data.get() + lead_b, cap_b, &nb, out->gainmap_data.get() + lead_m, cap_m, &nm,
                                           UHDR_HIP_GENERATE_GAMMA_TABLE);

@@ -1043,6 +1043,47 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans_ex_dev(uhdr_hip_ctx_t* ctx, const u
                                                     uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
                                                     uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned int flags);
 
+/* ---- The fused API-1 encode for frames that are not whole MCUs and maps that are not whole blocks (lib/src/jpegr.cpp:247-291 through
+ * JpegEncoderHelper::compressYCbCr's edge handling, lib/src/jpegencoderhelper.cpp:246-309) ---------------------------------------------
+ * 1920 x 1080, 4000 x 3000, any frame uhdr_enc_set_raw_image admits.  Three entry points: the front end with the parameter list of
+ * uhdr_hip_encode_api1_fused_onepass_dev plus flags, the two scans forms with the parameter lists of uhdr_hip_encode_api1_scans_ex /
+ * _ex_dev.  flags: 0 or UHDR_HIP_GENERATE_GAMMA_TABLE; unknown bits are UHDR_CODEC_INVALID_PARAM.  A request the _ex siblings take runs
+ * exactly what they run.  In addition:
+ *   - a UHDR_IMG_FMT_12bppYCbCr420 SDR intent of any even w, h >= 2.  Coefficient arrays sit on libjpeg's width_in_blocks grids, as for
+ *     uhdr_hip_jpeg_encode_image: luma ceil(w / 8) x ceil(h / 8), chroma ceil((w / 2) / 8) x ceil((h / 2) / 8); a luma block that only
+ *     completes an MCU is not written (the entropy coder makes it up).  Samples beyond the frame follow compressYCbCr after convertYuv ran
+ *     in place on w x h: per plane, a stride that covers the 8-aligned width (column mode 0) means columns past the width are the CALLER'S
+ *     bytes there, unconverted, and rows past the height are 0 (Y) / 128 (Cb, Cr); a shorter stride (column mode 1) means columns past the
+ *     width are 0 / 128 and rows past the height repeat the converted row one MCU row up (zeros in the first MCU row).  In column mode 0
+ *     the planes must be readable up to the 8-aligned width in every row, the last included (the host form uploads them so);
+ *   - any map size (w / S) x (h / S) >= 1 x 1 for scale factors 1, 2, 4: coefficient arrays of ceil(mw / 8) x ceil(mh / 8) blocks.  A
+ *     one-channel map is byte 0 outside mw x mh (the reference's zero-initialised 64-aligned allocation), a three-channel map repeats its
+ *     last column and row (jpeg_write_scanlines).  With gm given, any stride >= mw and any address: exactly mw x mh samples are written.
+ * Both presets, one and three channels, gamma 1 and the table gamma, every HDR format.  The scans carry the real blocks with the true w, h
+ * and equal uhdr_hip_convert_yuv + uhdr_hip_jpeg_encode_image on the caller's strides, uhdr_hip_generate_gainmap(_ex) into a zero-filled
+ * map of stride ALIGN(mw, 64) + uhdr_hip_jpeg_encode_image, byte for byte; scan capacities are a matter of block counts, not of w * h.
+ * UHDR_CODEC_UNSUPPORTED_FEATURE before anything is uploaded or launched: an odd or empty 4:2:0 frame, an RGBA8888 SDR intent whose dimensions
+ * are not multiples of 8 or whose map (w / S) x (h / S) is not whole 8 x 8 blocks (the edge handling, the map's included, is for 4:2:0
+ * intents), a context with a communicator, a frame so small that generateGainMap changes the scale factor (w / S or h / S == 0).  A scale
+ * factor below 1 is UHDR_CODEC_INVALID_PARAM, as for uhdr_hip_generate_gainmap. */
+uhdr_error_info_t uhdr_hip_encode_api1_fused_edges_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                       const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                       const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                       const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm,
+                                                       unsigned int flags);
+uhdr_error_info_t uhdr_hip_encode_api1_scans_edges(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                   const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                   const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                   uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                   uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
+                                                   uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned int flags);
+uhdr_error_info_t uhdr_hip_encode_api1_scans_edges_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                       const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                       const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                       uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                       uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
+                                                       uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned int flags);
+
 /* JpegR::encodeJPEGR API-0 (lib/src/jpegr.cpp:179-244) for the HDR intents whose tone-mapped rendition is RGBA8888 -- RGBA1010102 and RGBA
  * half float -- in ONE call (round 6): host intent in, the two entropy-coded scans out (host buffers).  uhdr_hip_encode_api0_fused_dev (tone
  * map + one-pass gain map + RGB -> YCbCr 4:4:4) + FDCT / quantize + both scans Huffman-coded; what the facade binds at encodeJPEGR API-0.

@@ -323,6 +323,31 @@ class UltraHdr {
                                                                                      gainmap_metadata, gainmap_desc, base_scan, base_capacity, base_bytes,
                                                                                      map_scan, map_capacity, map_bytes, flags);
   }
+  // encodeApi1FusedOnePass / encodeApi1ScansEx for frames that are not whole MCUs and maps that are not whole blocks -- 1920 x 1080, 4000 x 3000
+  // (uhdr_hip_encode_api1_fused_edges_dev, uhdr_hip_encode_api1_scans_edges / _edges_dev; jpegencoderhelper.cpp:246-309): a 4:2:0 SDR intent of
+  // any even size, a map of any size, coefficient arrays on libjpeg's width_in_blocks grids.  What the siblings take runs what they run.
+  uhdr_error_info_t encodeApi1FusedEdges(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* hdr_intent, uhdr_color_gamut_t base_encoding,
+                                         const uint16_t qt_base[2][64], const uint16_t qt_map[2][64], const uhdr_hip_api1_blocks_t* blocks,
+                                         uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_raw_image_t* gainmap_img, unsigned int flags = 0,
+                                         bool sdr_is_601 = false, bool use_luminance = true) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, sdr_is_601 ? 1 : 0, use_luminance ? 1 : 0};
+    return uhdr_hip_encode_api1_fused_edges_dev(mCtx, sdr_intent, hdr_intent, &cfg, base_encoding, qt_base, qt_map, blocks, gainmap_metadata, gainmap_img,
+                                                flags);
+  }
+  uhdr_error_info_t encodeApi1ScansEdges(uhdr_raw_image_t* sdr_intent, uhdr_raw_image_t* hdr_intent, uhdr_color_gamut_t base_encoding,
+                                         const uint16_t qt_base[2][64], const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* gainmap_metadata,
+                                         uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes,
+                                         uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned int flags = 0, bool dev = false,
+                                         bool sdr_is_601 = false, bool use_luminance = true) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, sdr_is_601 ? 1 : 0, use_luminance ? 1 : 0};
+    return (dev ? uhdr_hip_encode_api1_scans_edges_dev : uhdr_hip_encode_api1_scans_edges)(mCtx, sdr_intent, hdr_intent, &cfg, base_encoding, qt_base,
+                                                                                           qt_map, gainmap_metadata, gainmap_desc, base_scan, base_capacity,
+                                                                                           base_bytes, map_scan, map_capacity, map_bytes, flags);
+  }
 
   // generateGainMap on an SDR intent still in coefficient form -- the compressed intent of an API-3 encode after its Huffman decode (device
   // pointers; hdr_intent and gainmap_img are device images): the dequantize + IDCT stage runs inside the kernel

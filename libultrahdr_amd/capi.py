@@ -241,6 +241,12 @@ _SIGS = {
                                                   _P(RawImage), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_uint]),
     "uhdr_hip_encode_api1_scans_ex_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(EncodeCfg), C.c_int, C.c_void_p, C.c_void_p, _P(GainmapMetadata),
                                                       _P(RawImage), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_uint]),
+    "uhdr_hip_encode_api1_fused_edges_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(EncodeCfg), C.c_int, C.c_void_p, C.c_void_p, _P(Api1Blocks),
+                                                         _P(GainmapMetadata), _P(RawImage), C.c_uint]),
+    "uhdr_hip_encode_api1_scans_edges": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(EncodeCfg), C.c_int, C.c_void_p, C.c_void_p, _P(GainmapMetadata),
+                                                     _P(RawImage), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_uint]),
+    "uhdr_hip_encode_api1_scans_edges_dev": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(EncodeCfg), C.c_int, C.c_void_p, C.c_void_p, _P(GainmapMetadata),
+                                                         _P(RawImage), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_uint]),
     "uhdr_hip_huffman_encode2_dev": (ErrorInfo, [C.c_void_p, _P(JpegScan), C.c_void_p, C.c_size_t, _P(C.c_size_t), _P(JpegScan), C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "uhdr_hip_huffman_decode2_dev": (ErrorInfo, [C.c_void_p, _P(JpegScan), _P(HuffTables), C.c_void_p, C.c_size_t, _P(JpegScan), _P(HuffTables), C.c_void_p, C.c_size_t]),
     "uhdr_hip_encode_api1_scans": (ErrorInfo, [C.c_void_p, _P(RawImage), _P(RawImage), _P(EncodeCfg), C.c_int, C.c_void_p, C.c_void_p, _P(GainmapMetadata),

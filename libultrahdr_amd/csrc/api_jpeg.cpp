@@ -353,16 +353,16 @@ static uhdr_error_info_t carve_coef_arrays(DeviceBuf& buf, const size_t* nblocks
   return ok_status();
 }
 
-// The scan of a w x h image of whole blocks.  chroma_div: a chroma block's width in luma samples -- 8: every component 1x1 (4:4:4, a map);
-// 16: 4:2:0, the luma component 2x2
+// The scan of a w x h image on libjpeg's width_in_blocks grids (real blocks).  chroma_div: a chroma block's width in luma samples -- 8: every
+// component 1x1 (4:4:4, a map); 16: 4:2:0, the luma component 2x2
 static void fill_scan(uhdr_hip_jpeg_scan_t* s, unsigned w, unsigned h, int components, unsigned chroma_div, int16_t* const* coef) {
   memset(s, 0, sizeof *s);
   s->num_components = components;
   s->w = w; s->h = h;
   for (int i = 0; i < components; i++) {
     s->coef[i] = coef[i];
-    s->blocks_w[i] = (int)(i ? w / chroma_div : w / 8);
-    s->blocks_h[i] = (int)(i ? h / chroma_div : h / 8);
+    s->blocks_w[i] = (int)(i ? (w + chroma_div - 1) / chroma_div : (w + 7) / 8);
+    s->blocks_h[i] = (int)(i ? (h + chroma_div - 1) / chroma_div : (h + 7) / 8);
     s->h_samp[i] = s->v_samp[i] = (i || chroma_div == 8) ? 1 : 2;
   }
 }
@@ -395,13 +395,24 @@ enum Api1Route : unsigned {
   kApi1AnySdr = 2,   // an RGBA8888 SDR intent is taken as well as a 4:2:0 one
   kApi1Onepass = 4,  // the real-time preset is taken too
   kApi1GammaTable = 8,  // UHDR_HIP_GENERATE_GAMMA_TABLE: a gamma != 1 is taken, through the host's byte thresholds (gamma_code.h)
+  kApi1Edges = 16,   // the _edges entry points: 4:2:0 frames that are not whole MCUs and maps that are not whole blocks are taken
 };
 
 // What the chain declines whatever else the request holds -- the SDR intent's format and MCU rule, the preset, gamma -- stated once: the
 // scans entry points ask before 37 MB go up for nothing.  whole_image: h == 0 is declined with the dimensions (the chain lets an empty stripe through)
 static uhdr_error_info_t check_api1_request(const uhdr_raw_image_t* sdr, const uhdr_hip_encode_cfg_t* cfg, unsigned route, bool whole_image) {
   const bool empty = sdr->w == 0 || (whole_image && sdr->h == 0);
-  if ((route & kApi1AnySdr) && sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888) {
+  if (route & kApi1Edges) {  // (whole images only)
+    if (sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888 && (sdr->w % 8 || sdr->h % 8 || sdr->w == 0 || sdr->h == 0))
+      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain has edge handling for 4:2:0 base images only: a UHDR_IMG_FMT_32bppRGBA8888 SDR intent "
+                        "needs dimensions that are multiples of 8 (received %ux%u); use the operators", sdr->w, sdr->h);
+    if (sdr->fmt != UHDR_IMG_FMT_32bppRGBA8888 && sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420)
+      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_12bppYCbCr420 or UHDR_IMG_FMT_32bppRGBA8888 SDR intent "
+                        "(received format %d); use the operators", sdr->fmt);
+    if (sdr->fmt == UHDR_IMG_FMT_12bppYCbCr420 && (sdr->w % 2 || sdr->h % 2 || sdr->w < 2 || sdr->h < 2))
+      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_12bppYCbCr420 base image of even dimensions, 2x2 at least "
+                        "(received %ux%u); use the operators", sdr->w, sdr->h);
+  } else if ((route & kApi1AnySdr) && sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888) {
     if (sdr->w % 8 || sdr->h % 8 || empty)
       return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_32bppRGBA8888 SDR intent whose dimensions are multiples of 8 "
                         "(received %ux%u); use the operators", sdr->w, sdr->h);
@@ -443,8 +454,13 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   // range is known beforehand, jpegr.cpp:724-737: no ratio plane, no reduction, no range read-back) and the base image's blocks
   const bool one = onepass && cfg && cfg->preset == UHDR_USAGE_REALTIME;
   const bool gamma_table = (route & kApi1GammaTable) != 0;
+  // edges (uhdr_hip_encode_api1_fused_edges_dev): a 4:2:0 frame of any even size and a map of any size -- launch_base_blocks and the map
+  // launches with their EDGE kernels where the request is not whole MCUs / blocks, the kernels of the siblings where it is
+  const bool edges = (route & kApi1Edges) != 0;
+  bool map_edges = false;
   const float* gamma_thr2 = nullptr;  // two pass, gamma != 1: the thresholds behind the range kernel's tables and the map kernel's per-sample tail
   float gamma_gap = 0.0f;
+  if (edges && striped) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes of whole MCU rows (uhdr_hip_encode_api1_fused_dev); frames that are not whole MCUs are encoded whole");
   if (one && striped) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes, which stay two-pass (uhdr_hip_encode_api1_fused_dev)");
   if (rgba && striped) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes of 4:2:0 base images; an RGBA8888 SDR intent is encoded whole");
   Rgb2Yuv base_k;
@@ -466,7 +482,14 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
     }
     if (sdr->h == 0) return err_status(UHDR_CODEC_INVALID_PARAM, "empty base image");
     UHDR_TRY(fill_gen_params(c, sdr, hdr, cfg, &p, &use_base_cg, &hdr_white_nits));
-    if (p.scale != (uint32_t)cfg->map_dimension_scale_factor || p.map_w % 8 || p.map_h % 8)
+    if (edges && p.scale != (uint32_t)cfg->map_dimension_scale_factor)
+      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain keeps the scale factor it is given: a %ux%u frame is too small for scale factor %d "
+                        "(generateGainMap would take %u); use the operators", sdr->w, sdr->h, cfg->map_dimension_scale_factor, p.scale);
+    map_edges = edges && !rgba && (p.map_w % 8 || p.map_h % 8);
+    if (edges && rgba && (p.map_w % 8 || p.map_h % 8))  // (the EDGE map kernels read 4:2:0 intents: what the scans forms answer)
+      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs map dimensions that are multiples of 8 (scale factor %d on %ux%u)",
+                        cfg->map_dimension_scale_factor, sdr->w, sdr->h);
+    if (!edges && (p.scale != (uint32_t)cfg->map_dimension_scale_factor || p.map_w % 8 || p.map_h % 8))
       return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs map dimensions that are multiples of 8 (%ux%u at scale factor %u); use the operators",
                         p.map_w, p.map_h, p.scale);
     nch = p.multichannel ? 3 : 1;
@@ -484,7 +507,10 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
       fill_gainmap_desc(hdr, p, gm);
       if (!gm->planes[0]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for the gainmap image's plane");
       if (gm->stride[0] < gm->w) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap stride (%u) cannot be less than its width (%u)", gm->stride[0], gm->w);
-      if (((uintptr_t)gm->planes[0] | ((size_t)gm->stride[0] * nch)) & 7) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain stores the map in 8-byte pieces: aligned rows");
+      if (((uintptr_t)gm->planes[0] | ((size_t)gm->stride[0] * nch)) & 7) {
+        if (!edges || rgba) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain stores the map in 8-byte pieces: aligned rows");
+        map_edges = true;  // (the EDGE kernels store the map byte by byte)
+      }
       map_out = (uint8_t*)gm->planes[0];
       map_stride = gm->stride[0];
     }
@@ -516,7 +542,7 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   if (one) UHDR_TRY(fill_onepass_range(c, cfg, hdr_white_nits, use_base_cg, &p, md, gamma_table));  // the metadata is host arithmetic: complete here
   auto base_launch = [&](hipStream_t s) -> hipError_t {
     if (rgba) return launch_base_blocks_rgba(view_of(sdr), base_k, convert ? &conv : nullptr, qt_base[0], qt_base[1], blocks->base_coef, s);
-    return launch_base_blocks(view_of(sdr), convert ? &conv : nullptr, qt_base[0], qt_base[1], blocks->base_coef, s);
+    return launch_base_blocks(view_of(sdr), convert ? &conv : nullptr, qt_base[0], qt_base[1], blocks->base_coef, s, edges);
   };
   bool run = local.error_code == UHDR_CODEC_OK && !empty;
   float* merged = (float*)c->exchange.p;
@@ -556,7 +582,7 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   if (one) {  // map blocks here, base blocks there (or behind them); nothing to read back
     {
       ProfScope ps(c, "map_blocks_onepass");
-      note_hip(launch_map_blocks_onepass(p, nch, qt_map[0], qt_map[1], blocks->map_coef, map_out, map_stride, c->stream), "one-pass map blocks");
+      note_hip(launch_map_blocks_onepass(p, nch, qt_map[0], qt_map[1], blocks->map_coef, map_out, map_stride, c->stream, map_edges), "one-pass map blocks");
     }
     if (!side) {
       ProfScope ps(c, rgba ? "base_blocks_rgba" : "fdct_quant");
@@ -621,8 +647,8 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   }
   if (run && xchg.error_code == UHDR_CODEC_OK) {
     ProfScope ps(c, "fdct_quant");
-    note_hip(launch_map_blocks(p.gain_log2, (const AffineDev*)c->affine.p, c->d_math, nch, (int)(p.map_w / 8), (int)(p.map_h / 8), qt_map[0], qt_map[1],
-                               blocks->map_coef, map_out, map_stride, c->stream, gamma_thr2), "map blocks");
+    note_hip(launch_map_blocks(p.gain_log2, (const AffineDev*)c->affine.p, c->d_math, nch, (int)((p.map_w + 7) / 8), (int)((p.map_h + 7) / 8), qt_map[0], qt_map[1],
+                               blocks->map_coef, map_out, map_stride, c->stream, gamma_thr2, map_edges ? p.map_w : 0, map_edges ? p.map_h : 0), "map blocks");
     if (!side && !rgba) note_hip(base_launch(c->stream), "base blocks");
   }
   if (run && xchg.error_code == UHDR_CODEC_OK && !side && rgba) {
@@ -670,6 +696,44 @@ uhdr_error_info_t uhdr_hip_encode_api1_fused_onepass_dev(uhdr_hip_ctx_t* c, cons
                                                          const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm) {
   return encode_api1_fused_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, blocks, md, gm, kApi1Dev | kApi1AnySdr | kApi1Onepass);
 }
+// stage_in for a (validated) host 4:2:0 intent that is not whole MCUs: the host pitch is kept, and where a plane's stride covers its 8-aligned
+// width (compressYCbCr's column mode 0, jpegencoderhelper.cpp:256) the LAST row goes up to that width too -- the bytes behind the width are
+// input there, as they are for the helper
+static uhdr_error_info_t stage_in_420_edges(uhdr_hip_ctx* c, const uhdr_raw_image_t* host, uhdr_raw_image_t* dev) {
+  if (c->sticky.error_code != UHDR_CODEC_OK) {  // see uhdr_hip_ctx::sticky
+    const uhdr_error_info_t e = c->sticky;
+    c->sticky = ok_status();
+    return e;
+  }
+  size_t off[3], bytes[3], total = 0;
+  for (int pl = 0; pl < 3; pl++) {
+    const size_t pw = pl ? host->w / 2 : host->w, rows = pl ? host->h / 2 : host->h, aligned = (pw + 7) & ~(size_t)7;
+    bytes[pl] = (rows - 1) * (size_t)host->stride[pl] + (host->stride[pl] >= aligned ? aligned : pw);
+    off[pl] = total;
+    total += (bytes[pl] + 255) & ~(size_t)255;
+  }
+  UHDR_TRY(ensure(c->scratch[0], total));
+  *dev = *host;
+  for (int pl = 0; pl < 3; pl++) {
+    dev->planes[pl] = (char*)c->scratch[0].p + off[pl];
+    UHDR_TRY(fast_h2d(c, dev->planes[pl], host->planes[pl], bytes[pl]));
+  }
+  return ok_status();
+}
+
+static uhdr_error_info_t check_api1_flags(unsigned int flags, unsigned* route);
+// ... and for frames that are not whole MCUs / maps that are not whole blocks (jpegr.cpp:247-291 through compressYCbCr's edge handling,
+// jpegencoderhelper.cpp:246-309), with generateGainMap's flags
+uhdr_error_info_t uhdr_hip_encode_api1_fused_edges_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
+                                                       const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
+                                                       const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                       const uhdr_hip_api1_blocks_t* blocks, uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gm,
+                                                       unsigned int flags) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  unsigned route = kApi1Dev | kApi1AnySdr | kApi1Onepass | kApi1Edges;
+  UHDR_TRY(check_api1_flags(flags, &route));
+  return encode_api1_fused_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, blocks, md, gm, route);
+}
 
 // JpegR::encodeJPEGR API-1 (jpegr.cpp:253-316) from its two raw intents to its two entropy-coded scans in ONE entry point: the
 // intents go up once (fast_h2d), the fused chain leaves coefficient blocks in HBM, the marker-less Huffman coder turns them into
@@ -685,10 +749,18 @@ static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   const bool dev = (route & kApi1Dev) != 0;
   const bool rgba = (route & kApi1AnySdr) && sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888;  // base image 4:4:4: a 1x1 / 1x1 / 1x1 scan
   const int scale = cfg->map_dimension_scale_factor;
-  if (scale < 1 || sdr->w / (unsigned)scale == 0 || sdr->h / (unsigned)scale == 0 || (sdr->w / (unsigned)scale) % 8 || (sdr->h / (unsigned)scale) % 8)
+  // edges (uhdr_hip_encode_api1_scans_edges / _edges_dev): a 4:2:0 frame that is not whole MCUs, a map that is not whole blocks
+  const bool edges = (route & kApi1Edges) != 0, edges420 = edges && !rgba;
+  if (edges && scale < 1) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap scale factor %d is not positive", scale);  // (fill_gen_params' answer)
+  if (edges && (sdr->w / (unsigned)scale == 0 || sdr->h / (unsigned)scale == 0))
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain keeps the scale factor it is given: a %ux%u frame is too small for scale factor %d; use the operators",
+                      sdr->w, sdr->h, scale);
+  if (!edges420 && (scale < 1 || sdr->w / (unsigned)scale == 0 || sdr->h / (unsigned)scale == 0 || (sdr->w / (unsigned)scale) % 8 || (sdr->h / (unsigned)scale) % 8))
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs map dimensions that are multiples of 8 (scale factor %d on %ux%u)", scale, sdr->w, sdr->h);
   if (hdr->w != sdr->w || hdr->h != sdr->h)
     return err_status(UHDR_CODEC_INVALID_PARAM, "sdr intent resolution %ux%u and hdr intent resolution %ux%u do not match", sdr->w, sdr->h, hdr->w, hdr->h);
+  if (edges && (c->comm != nullptr || c->comm_custom))
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes of whole MCU rows (uhdr_hip_encode_api1_fused_dev); frames that are not whole MCUs are encoded whole");
   if (c->comm != nullptr || c->comm_custom)
     return rgba ? err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes of 4:2:0 base images; an RGBA8888 SDR intent is encoded whole")
                 : err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes (uhdr_hip_encode_api1_fused_dev)");
@@ -709,13 +781,14 @@ static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
     dh = *hdr;
   } else {
     if (c->resident_on) UHDR_TRY(resident_write_back_all(c));
-    UHDR_TRY(stage_in(c, 0, sdr, &ds, true));
+    if (edges420 && (w % 16 || h % 16)) UHDR_TRY(stage_in_420_edges(c, sdr, &ds));
+    else UHDR_TRY(stage_in(c, 0, sdr, &ds, true));
     UHDR_TRY(stage_in(c, 1, hdr, &dh, true));
   }
-  // coefficient arrays: base Y, Cb, Cr, then the map's 1 or 3 components; 256-byte aligned
+  // coefficient arrays: base Y, Cb, Cr, then the map's 1 or 3 components, each on its real-block grid; 256-byte aligned
   const unsigned cdiv = rgba ? 8 : 16;  // a chroma block's width in luma samples
-  const size_t nbc = (size_t)(w / cdiv) * (h / cdiv), nm = (size_t)(mw / 8) * (mh / 8);
-  const size_t nblocks[6] = {(size_t)(w / 8) * (h / 8), nbc, nbc, nm, nm, nm};
+  const size_t nbc = (size_t)((w + cdiv - 1) / cdiv) * ((h + cdiv - 1) / cdiv), nm = (size_t)((mw + 7) / 8) * ((mh + 7) / 8);
+  const size_t nblocks[6] = {(size_t)((w + 7) / 8) * ((h + 7) / 8), nbc, nbc, nm, nm, nm};
   uhdr_hip_api1_blocks_t blocks;
   memset(&blocks, 0, sizeof blocks);
   int16_t* coef[6];
@@ -873,6 +946,28 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans_ex(uhdr_hip_ctx_t* c, const uhdr_ra
                                                 uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
                                                 size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned int flags) {
   unsigned route = kApi1AnySdr | kApi1Onepass;
+  UHDR_TRY(check_api1_flags(flags, &route));
+  return encode_api1_scans_timed(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
+                                 map_bytes, route);
+}
+// ... and for 4:2:0 frames that are not whole MCUs and maps that are not whole blocks: uhdr_hip_encode_api1_fused_edges_dev in front of the
+// same entropy stage, whose scans carry the real blocks of libjpeg's width_in_blocks grids with the true w, h
+uhdr_error_info_t uhdr_hip_encode_api1_scans_edges_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                       uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                       uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                                       size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned int flags) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  unsigned route = kApi1Dev | kApi1AnySdr | kApi1Onepass | kApi1Edges;
+  UHDR_TRY(check_api1_flags(flags, &route));
+  return encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
+                                map_bytes, route);
+}
+uhdr_error_info_t uhdr_hip_encode_api1_scans_edges(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                   uhdr_color_gamut_t base_encoding, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                                   uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc, uint8_t* base_scan, size_t base_capacity,
+                                                   size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned int flags) {
+  if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
+  unsigned route = kApi1AnySdr | kApi1Onepass | kApi1Edges;
   UHDR_TRY(check_api1_flags(flags, &route));
   return encode_api1_scans_timed(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
                                  map_bytes, route);

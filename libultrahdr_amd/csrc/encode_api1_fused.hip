@@ -55,10 +55,33 @@ struct MapBlocksParams {
   int16_t* coef[3];
   QuantTables q;
   const float* gamma_thr;  // the two-pass byte thresholds of a gamma != 1 (gamma_code.h), global memory; null: gamma is 1
+  uint32_t map_w, map_h;   // EDGE: the map's samples; bw, bh are ceil(map_w / 8), ceil(map_h / 8)
 };
 
-constexpr int kMapBlock = 512;  // eight waves share one copy of the step tables (24 KB): three workgroups = 24 waves per CU
+// EDGE kernels: how many of the eight samples of row y, columns x0 .. x0 + 7 lie inside the map
+__device__ __forceinline__ uint32_t map_row_valid(uint32_t x0, uint32_t y, uint32_t map_w, uint32_t map_h) {
+  return y < map_h ? min(8u, map_w - x0) : 0u;
+}
+// EDGE, one channel: the map goes to compressYCbCr in a zero-initialised allocation whose stride covers the block-aligned width
+// (uhdr_memory_block_t, ultrahdr_api.cpp:46), so every sample outside map_w x map_h is byte 0
+__device__ __forceinline__ void map_row_zero_outside(uint32_t (&w)[2], uint32_t nv) {
+  const unsigned long long m = nv >= 8 ? ~0ull : ((1ull << (8 * nv)) - 1);
+  w[0] &= (uint32_t)m;
+  w[1] &= (uint32_t)(m >> 32);
+}
+// EDGE: the nv * NCH map bytes of a lane's row, one by one (any pitch, nothing beside them touched)
 template <int NCH>
+__device__ __forceinline__ void map_row_store_bytes(uint8_t* o, const uint32_t (&w)[2 * NCH], uint32_t nv) {
+#pragma unroll
+  for (int e = 0; e < 8 * NCH; e++)
+    if ((uint32_t)(e / NCH) < nv) o[e] = (uint8_t)(w[e >> 2] >> (8 * (e & 3)));
+}
+
+constexpr int kMapBlock = 512;  // eight waves share one copy of the step tables (24 KB): three workgroups = 24 waves per CU
+// EDGE: maps that are not whole blocks.  A three-channel map (RGB888 through jpeg_write_scanlines) repeats its last column and row, as
+// fdct_quant_rgb_kernel does -- the clamped sample's byte --, a one-channel map is zero outside; the ratio plane keeps pitch map_w, so a
+// row is read float by float; the optional 8-bit map is stored byte by byte, map_w x map_h of them.
+template <int NCH, bool EDGE = false>
 __global__ __launch_bounds__(kMapBlock) void map_blocks_kernel(const MapBlocksParams p) {
   constexpr int kBlock = kMapBlock;  // (shadows the file's 256 inside this kernel)
   __shared__ int s_ws[kBlock / 64][kWsWords];
@@ -86,13 +109,53 @@ __global__ __launch_bounds__(kMapBlock) void map_blocks_kernel(const MapBlocksPa
   const int groups_x = (p.bw + 7) >> 3, total = groups_x * p.bh;
   const int gwave = blockIdx.x * (kBlock / 64) + wv, nwaves = gridDim.x * (kBlock / 64);
   const int rr = lane >> 3, rb = lane & 7;
-  const uint32_t map_w = (uint32_t)p.bw * 8;
+  const uint32_t map_w = EDGE ? p.map_w : (uint32_t)p.bw * 8;
   for (int t = gwave; t < total; t += nwaves) {
     const int by = t / groups_x, gx = t - by * groups_x;
     const int bx = gx * 8 + rb;
     const bool active = bx < p.bw;
     int comp[3][8];
-    if (active) {
+    if (EDGE && active) {
+      const uint32_t y = by * 8 + rr, x0 = bx * 8;
+      const float* row = p.ratio + (size_t)min(y, p.map_h - 1) * map_w * NCH;
+      auto ratio_at = [&](int e) -> float { return row[(size_t)min(x0 + (uint32_t)(e / NCH), map_w - 1) * NCH + e % NCH]; };
+      uint32_t w[2 * NCH];
+      if (tabs) {
+#pragma unroll
+        for (int k = 0; k < 2 * NCH; k++) {
+          uint32_t acc = 0;
+#pragma unroll
+          for (int i = 0; i < 4; i++) acc |= step_code(ratio_at(4 * k + i), s_tab[(4 * k + i) % NCH], st[(4 * k + i) % NCH]) << (8 * i);
+          w[k] = acc;
+        }
+      } else {  // (the per-sample evaluation below, on the clamped samples)
+#pragma unroll 1
+        for (int k = 0; k < 2 * NCH; k++) {
+          uint32_t acc = 0;
+#pragma unroll 1
+          for (int i = 0; i < 4; i++) {
+            const int c = (4 * k + i) % NCH;
+            const float lg = gain_log2_of_ratio(ratio_at(4 * k + i), p.math_tab);
+            float m = div_by_rcp64(lg - p.dev->mn[c], p.dev->range_rcp[c]);
+            if (p.gamma_thr) {
+              acc |= gamma_code(m, p.gamma_thr) << (8 * i);
+              continue;
+            }
+            m *= 255.0f;
+            float t2 = m + 0.5f;
+            t2 = (t2 < 0.0f) ? 0.0f : ((t2 > 255.0f) ? 255.0f : t2);
+            acc |= (uint32_t)t2 << (8 * i);
+          }
+          ws[lane * 9 + k] = (int)acc;
+        }
+#pragma unroll
+        for (int k = 0; k < 2 * NCH; k++) w[k] = (uint32_t)ws[lane * 9 + k];
+      }
+      const uint32_t nv = map_row_valid(x0, y, map_w, p.map_h);
+      if constexpr (NCH == 1) map_row_zero_outside(w, nv);
+      if (p.map_out && nv) map_row_store_bytes<NCH>(p.map_out + ((size_t)y * p.out_stride + x0) * NCH, w, nv);
+      map_row_samples<NCH>(w, comp);
+    } else if (active) {
       const uint32_t y = by * 8 + rr, x0 = bx * 8;
       const float4* src = (const float4*)(p.ratio + ((size_t)y * map_w + x0) * NCH);
       float4 g[2 * NCH];
@@ -201,8 +264,10 @@ __device__ __forceinline__ void onepass_codes(Color3 s, Color3 h, const GenParam
   }
 }
 
-template <int SDRF, int HDRF, int NCH, bool FAST>
+// EDGE (never with FAST): maps that are not whole blocks, by map_blocks_kernel<.., EDGE>'s rules -- a lane computes the clamped map pixel.
+template <int SDRF, int HDRF, int NCH, bool FAST, bool EDGE = false>
 __global__ __launch_bounds__(kMapBlock, 4) void map_blocks_onepass_kernel(const MapOnepassParams p) {
+  static_assert(!(FAST && EDGE), "the vector fetch reads whole blocks");
   constexpr int kBlock = kMapBlock;
   __shared__ int s_ws[kBlock / 64][kWsWords];
   __shared__ OnepassLds L;
@@ -230,6 +295,7 @@ __global__ __launch_bounds__(kMapBlock, 4) void map_blocks_onepass_kernel(const 
     int comp[3][8];
     if (active) {
       const uint32_t y = by * 8 + rr, x0 = bx * 8;
+      const uint32_t ys = EDGE ? min(y, g.map_h - 1) : y, x_last = g.map_w - 1;  // (sample_box below: column min(x0 + k, x_last) for EDGE)
       uint32_t w[2 * NCH];  // the 8 * NCH map bytes of this row, packed as they come
 #pragma unroll
       for (int i = 0; i < 2 * NCH; i++) w[i] = 0;
@@ -257,7 +323,8 @@ __global__ __launch_bounds__(kMapBlock, 4) void map_blocks_onepass_kernel(const 
       } else if (HDRF >= 0 && tab) {
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-          const Color3 s = sample_box<SDRF>(g.sdr, g.scale, x0 + k, y, &L.unorm), h = sample_box<HDRF>(g.hdr, g.scale, x0 + k, y, &L.unorm);
+          const uint32_t xs = EDGE ? min(x0 + k, x_last) : x0 + k;
+          const Color3 s = sample_box<SDRF>(g.sdr, g.scale, xs, ys, &L.unorm), h = sample_box<HDRF>(g.hdr, g.scale, xs, ys, &L.unorm);
           uint32_t code[NCH];
           onepass_codes<NCH>(s, h, g, L, s_gain8, hdr_lut, hdr_lut_4096, code);
 #pragma unroll
@@ -269,7 +336,8 @@ __global__ __launch_bounds__(kMapBlock, 4) void map_blocks_onepass_kernel(const 
         uint8_t* park = (uint8_t*)(ws + lane * 9);
 #pragma unroll 1
         for (int k = 0; k < 8; k++) {
-          const Color3 s = sample_box<SDRF>(g.sdr, g.scale, x0 + k, y, &L.unorm), h = sample_box<HDRF>(g.hdr, g.scale, x0 + k, y, &L.unorm);
+          const uint32_t xs = EDGE ? min(x0 + k, x_last) : x0 + k;
+          const Color3 s = sample_box<SDRF>(g.sdr, g.scale, xs, ys, &L.unorm), h = sample_box<HDRF>(g.hdr, g.scale, xs, ys, &L.unorm);
           uint32_t code[NCH];
           onepass_codes<NCH>(s, h, g, L, tab ? s_gain8 : nullptr, hdr_lut, hdr_lut_4096, code);
 #pragma unroll
@@ -278,7 +346,11 @@ __global__ __launch_bounds__(kMapBlock, 4) void map_blocks_onepass_kernel(const 
 #pragma unroll
         for (int i = 0; i < 2 * NCH; i++) w[i] = (uint32_t)ws[lane * 9 + i];
       }
-      if (g.out) {
+      if constexpr (EDGE) {
+        const uint32_t nv = map_row_valid(x0, y, g.map_w, g.map_h);
+        if constexpr (NCH == 1) map_row_zero_outside(w, nv);
+        if (g.out && nv) map_row_store_bytes<NCH>(g.out + ((size_t)y * g.out_stride + x0) * NCH, w, nv);
+      } else if (g.out) {
         uint8_t* o = g.out + ((size_t)y * g.out_stride + x0) * NCH;
 #pragma unroll
         for (int k = 0; k < NCH; k++) *(uint2*)(o + 8 * k) = uint2{w[2 * k], w[2 * k + 1]};
@@ -300,10 +372,61 @@ struct BaseBlocksParams {
   Mat3 c;                  // convertYuv's coefficients (host_tables.cpp: yuv_encoding_matrix)
   int16_t* coef[3];
   QuantTables q;
+  // EDGE: the frame's w x h samples (even), ALIGN(w, 8), and per plane compressYCbCr's column mode (FdctEdge, uhdr_types.h);
+  // mcus_x, mcus_y are ceil(w / 16), ceil(h / 16)
+  int w, h, aw_y;
+  int cm[3];
 };
 
 __device__ __forceinline__ uint32_t st8(float v) { return (uint32_t)__builtin_amdgcn_fmed3f(v, 0.0f, 255.0f); }  // static_cast<uint8_t>(CLIP3(v, 0, 255)), convert.hip
 
+// One quad (luma columns gx, gx + 1 of rows gy, gy + 1, the chroma sample under them) of an MCU that reaches beyond the frame, as
+// JpegEncoderHelper::compressYCbCr (jpegencoderhelper.cpp:246-309) hands it to libjpeg after convertYuv ran in place on w x h only -- FdctEdge's
+// rules, per plane.  Column mode 0 (the stride covers the block-aligned width): columns past the width are the caller's bytes, unconverted;
+// rows past the height are 0 (Y) / 128 (Cb, Cr).  Column mode 1: columns past the width are 0 / 128, rows past the height still hold what the
+// MCU row above copied into the helper's scratch rows -- the converted row 16 (chroma: 8) rows up, zeros in the first MCU row.
+// w and h are even: a quad lies inside or outside as a whole, in each direction.
+__device__ __forceinline__ void base_edge_quad(const BaseBlocksParams& p, int gy, int gx, uint32_t& o0, uint32_t& o1, uint32_t& ou, uint32_t& ov) {
+  const bool in_x = gx < p.w, in_y = gy < p.h;
+  const int sgy = in_y ? gy : gy - 16;  // (a row of the MCU row above: all of its rows are inside)
+  uint32_t c0 = 0, c1 = 0, cu = 0, cv = 0;  // the converted quad at (sgy, gx)
+  if (in_x && sgy >= 0) {
+    const uint32_t r0 = *(const uint16_t*)(p.y + (size_t)sgy * p.sy + gx), r1 = *(const uint16_t*)(p.y + (size_t)(sgy + 1) * p.sy + gx);
+    const uint32_t ub = p.u[(size_t)(sgy >> 1) * p.su + (gx >> 1)], vb = p.v[(size_t)(sgy >> 1) * p.sv + (gx >> 1)];
+    c0 = r0; c1 = r1; cu = ub; cv = vb;
+    if (p.convert) {  // (base_blocks_kernel's arithmetic)
+      const float u = (float)((int)ub - 128) * (1 / 255.0f), v = (float)((int)vb - 128) * (1 / 255.0f);
+      const Color3 a = mat3_apply({(float)(r0 & 0xff) * (1 / 255.0f), u, v}, p.c);
+      const Color3 b = mat3_apply({(float)(r0 >> 8) * (1 / 255.0f), u, v}, p.c);
+      const Color3 c = mat3_apply({(float)(r1 & 0xff) * (1 / 255.0f), u, v}, p.c);
+      const Color3 d = mat3_apply({(float)(r1 >> 8) * (1 / 255.0f), u, v}, p.c);
+      const float nu = (((a.g + b.g) + c.g) + d.g) / 4.0f;
+      const float nv = (((a.b + b.b) + c.b) + d.b) / 4.0f;
+      c0 = st8(a.r * 255.0f + 0.5f) | (st8(b.r * 255.0f + 0.5f) << 8);
+      c1 = st8(c.r * 255.0f + 0.5f) | (st8(d.r * 255.0f + 0.5f) << 8);
+      cu = st8(nu * 255.0f + 128.0f + 0.5f);
+      cv = st8(nv * 255.0f + 128.0f + 0.5f);
+    }
+  }
+  o0 = o1 = 0;
+  if (in_x) {
+    if (in_y || p.cm[0] == 1) { o0 = c0; o1 = c1; }
+  } else if (in_y && p.cm[0] == 0 && gx < p.aw_y) {  // (luma blocks past aw_y only complete an MCU: never written)
+    o0 = *(const uint16_t*)(p.y + (size_t)gy * p.sy + gx);
+    o1 = *(const uint16_t*)(p.y + (size_t)(gy + 1) * p.sy + gx);
+  }
+  auto chroma = [&](const uint8_t* plane, uint32_t stride, int cm, uint32_t conv) -> uint32_t {
+    if (in_x) return (in_y || cm == 1) ? conv : 128u;
+    return (in_y && cm == 0) ? (uint32_t)plane[(size_t)(gy >> 1) * stride + (gx >> 1)] : 128u;
+  };
+  ou = chroma(p.u, p.su, p.cm[1], cu);
+  ov = chroma(p.v, p.sv, p.cm[2], cv);
+}
+
+// EDGE: frames that are not whole MCUs -- ceil(w / 16) x ceil(h / 16) MCUs, the luma blocks of libjpeg's width_in_blocks grid
+// (ceil(w / 8) x ceil(h / 8): a luma block that only completes an MCU is the entropy coder's to make up).  A pair that reaches beyond the
+// frame (wave-uniform) builds its quads with base_edge_quad; every other pair takes the loads of the whole-MCU kernel.
+template <bool EDGE>
 __global__ __launch_bounds__(kBlock) void base_blocks_kernel(const BaseBlocksParams p) {
   __shared__ int s_ws[kBlock / 64][kWsWords];
   // per wave: the converted samples of two MCUs -- luma 16 rows x 32, Cb and Cr 8 rows x 16 each
@@ -320,17 +443,28 @@ __global__ __launch_bounds__(kBlock) void base_blocks_kernel(const BaseBlocksPar
   __shared__ uint2 s_q[2][64];
   stage_quant_tables(s_q, p.q, threadIdx.x);
   __syncthreads();
-  const int bw_y = p.mcus_x * 2, bw_c = p.mcus_x;
+  const int bw_y = EDGE ? (p.w + 7) >> 3 : p.mcus_x * 2, bw_c = p.mcus_x;
+  const int bh_y = (p.h + 7) >> 3;  // (EDGE)
   for (int t = gwave; t < total; t += nwaves) {
     const int my = t / pairs_x, mp = t - my * pairs_x;
     const int mx0 = mp * 2;
     const int n_mcu = (mx0 + 1 < p.mcus_x) ? 2 : 1;
+    const bool edge_pair = EDGE && (my * 16 + 16 > p.h || (mx0 + n_mcu) * 16 > p.w);  // (wave-uniform)
     // ---- phase A: the pair's 128 quads (8 quad rows x 16 quad columns), two per lane, through convertYuv into the tile ----
 #pragma unroll
     for (int h = 0; h < 2; h++) {
       const int q = lane + 64 * h, qr = q >> 4, qc = q & 15;  // quad row / column inside the pair
       if (qc < n_mcu * 8) {
         const size_t gy = (size_t)my * 16 + qr * 2, gx = (size_t)mx0 * 16 + qc * 2;
+        if (edge_pair) {
+          uint32_t e0, e1, eu, ev;
+          base_edge_quad(p, (int)gy, (int)gx, e0, e1, eu, ev);
+          *(uint16_t*)(ty + (qr * 2) * 32 + qc * 2) = (uint16_t)e0;
+          *(uint16_t*)(ty + (qr * 2 + 1) * 32 + qc * 2) = (uint16_t)e1;
+          tcb[qr * 16 + qc] = (uint8_t)eu;
+          tcr[qr * 16 + qc] = (uint8_t)ev;
+          continue;
+        }
         const uint32_t r0 = *(const uint16_t*)(p.y + gy * p.sy + gx), r1 = *(const uint16_t*)(p.y + (gy + 1) * p.sy + gx);
         const uint32_t ub = p.u[(gy >> 1) * p.su + (gx >> 1)], vb = p.v[(gy >> 1) * p.sv + (gx >> 1)];
         uint32_t o0 = r0, o1 = r1, ou = ub, ov = vb;
@@ -358,7 +492,7 @@ __global__ __launch_bounds__(kBlock) void base_blocks_kernel(const BaseBlocksPar
     // ---- phase B: the 8 luma blocks.  Block rb = (MCU m, block row byy, block column bxx) ------------------------------------
     {
       const int m = rb >> 2, byy = (rb >> 1) & 1, bxx = rb & 1;
-      const bool active = m < n_mcu;
+      const bool active = m < n_mcu && (!EDGE || ((mx0 + m) * 2 + bxx < bw_y && my * 2 + byy < bh_y));
       int in[8], out[8], v[8];
       if (active) {
         const uint8_t* src = ty + (byy * 8 + rr) * 32 + m * 16 + bxx * 8;
@@ -495,10 +629,12 @@ int resident_grid(int total_wave_items, int per_cu) {
 // nch 3: packed RGB semantics (rgb_ycc_convert, 4:4:4, luma table for Y, chroma table for Cb / Cr); nch 1: a Y400 map.
 hipError_t launch_map_blocks(const float* ratio, const AffineDev* dev, const double* math_tab, int nch, int bw, int bh, const uint16_t* qt_luma,
                              const uint16_t* qt_chroma, int16_t* const coef[3], uint8_t* map_out, uint32_t out_stride, hipStream_t s,
-                             const float* gamma_thr) {
+                             const float* gamma_thr, uint32_t edge_w, uint32_t edge_h) {
+  // edge_w x edge_h != 0: the map's samples, bw x bh = ceil(edge_w / 8) x ceil(edge_h / 8) -- the EDGE kernel (any size, any map_out pitch)
   MapBlocksParams p;
   memset(&p, 0, sizeof p);
   p.gamma_thr = gamma_thr;
+  p.map_w = edge_w; p.map_h = edge_h;
   p.ratio = ratio; p.dev = dev; p.math_tab = math_tab; p.map_out = map_out; p.out_stride = out_stride; p.bw = bw; p.bh = bh;
   for (int i = 0; i < nch; i++) p.coef[i] = coef[i];
   fill_quant_table(qt_luma, &p.q.luma);
@@ -506,7 +642,10 @@ hipError_t launch_map_blocks(const float* ratio, const AffineDev* dev, const dou
   int grid = (((bw + 7) / 8) * bh + kMapBlock / 64 - 1) / (kMapBlock / 64);
   const int cap = resident_grid(1 << 30, 3);  // 44 KB of LDS (tables + workspaces) per 512 threads: three workgroups per CU
   if (grid > cap) grid = cap;
-  if (nch == 3) hipLaunchKernelGGL((map_blocks_kernel<3>), dim3(grid), dim3(kMapBlock), 0, s, p);
+  if (edge_w && edge_h) {
+    if (nch == 3) hipLaunchKernelGGL((map_blocks_kernel<3, true>), dim3(grid), dim3(kMapBlock), 0, s, p);
+    else hipLaunchKernelGGL((map_blocks_kernel<1, true>), dim3(grid), dim3(kMapBlock), 0, s, p);
+  } else if (nch == 3) hipLaunchKernelGGL((map_blocks_kernel<3>), dim3(grid), dim3(kMapBlock), 0, s, p);
   else hipLaunchKernelGGL((map_blocks_kernel<1>), dim3(grid), dim3(kMapBlock), 0, s, p);
   return hipGetLastError();
 }
@@ -521,21 +660,25 @@ static bool map_onepass_fast_layout(const GenParams& g) {
   return g.hdr.stride[0] % 8 == 0 && g.hdr.stride[1] % 8 == 0;  // (strides in 16-bit samples)
 }
 template <int SDRF, int HDRF>
-static void launch_onepass_n(const MapOnepassParams& p, int nch, int grid, hipStream_t s) {
-  if (nch == 3) hipLaunchKernelGGL((map_blocks_onepass_kernel<SDRF, HDRF, 3, false>), dim3(grid), dim3(kMapBlock), 0, s, p);
+static void launch_onepass_n(const MapOnepassParams& p, int nch, int grid, hipStream_t s, bool edges) {
+  if (edges) {
+    if (nch == 3) hipLaunchKernelGGL((map_blocks_onepass_kernel<SDRF, HDRF, 3, false, true>), dim3(grid), dim3(kMapBlock), 0, s, p);
+    else hipLaunchKernelGGL((map_blocks_onepass_kernel<SDRF, HDRF, 1, false, true>), dim3(grid), dim3(kMapBlock), 0, s, p);
+  } else if (nch == 3) hipLaunchKernelGGL((map_blocks_onepass_kernel<SDRF, HDRF, 3, false>), dim3(grid), dim3(kMapBlock), 0, s, p);
   else hipLaunchKernelGGL((map_blocks_onepass_kernel<SDRF, HDRF, 1, false>), dim3(grid), dim3(kMapBlock), 0, s, p);
 }
 
 // The one-pass gain map of the two intents in g (fill_gen_params + the one-pass range + gain8; g.out: the optional 8-bit map, g.out_stride
 // pixels) -> quantized coefficients of the map's JPEG.  map_w, map_h multiples of 8, gamma 1; SDR 4:2:0 or RGBA8888, every HDR format
-// fill_gen_params takes; nch as in launch_map_blocks.
+// fill_gen_params takes; nch as in launch_map_blocks.  edges: any map size and any map_out pitch (the EDGE kernel; 4:2:0 SDR intents).
 hipError_t launch_map_blocks_onepass(const GenParams& g, int nch, const uint16_t* qt_luma, const uint16_t* qt_chroma, int16_t* const coef[3],
-                                     uint8_t* map_out, uint32_t out_stride, hipStream_t s) {
+                                     uint8_t* map_out, uint32_t out_stride, hipStream_t s, bool edges) {
   MapOnepassParams p;
   memset(&p, 0, sizeof p);
   p.g = g;
   p.g.out = map_out; p.g.out_stride = out_stride;
   p.bw = (int)(g.map_w / 8); p.bh = (int)(g.map_h / 8);
+  if (edges) { p.bw = (int)((g.map_w + 7) / 8); p.bh = (int)((g.map_h + 7) / 8); }
   for (int i = 0; i < nch; i++) p.coef[i] = coef[i];
   fill_quant_table(qt_luma, &p.q.luma);
   fill_quant_table(qt_chroma, &p.q.chroma);
@@ -544,15 +687,16 @@ hipError_t launch_map_blocks_onepass(const GenParams& g, int nch, const uint16_t
   if (grid > cap) grid = cap;
   constexpr int k420 = UHDR_IMG_FMT_12bppYCbCr420, kRgba = UHDR_IMG_FMT_32bppRGBA8888, kP010 = UHDR_IMG_FMT_24bppYCbCrP010, k1010102 = UHDR_IMG_FMT_32bppRGBA1010102;
   // UHDR_HIP_ONEPASS_NO_VECTOR_FETCH=1: the per-sample fetch on every layout (tools/api1_onepass_time.py times the two against each other)
-  if (g.gain8.tab && map_onepass_fast_layout(g) && !getenv("UHDR_HIP_ONEPASS_NO_VECTOR_FETCH")) {
+  if (edges && g.sdr.fmt != k420) return hipErrorInvalidValue;
+  if (!edges && g.gain8.tab && map_onepass_fast_layout(g) && !getenv("UHDR_HIP_ONEPASS_NO_VECTOR_FETCH")) {
     if (nch == 3) hipLaunchKernelGGL((map_blocks_onepass_kernel<k420, kP010, 3, true>), dim3(grid), dim3(kMapBlock), 0, s, p);
     else hipLaunchKernelGGL((map_blocks_onepass_kernel<k420, kP010, 1, true>), dim3(grid), dim3(kMapBlock), 0, s, p);
   } else if (g.sdr.fmt == k420) {
-    if (g.hdr.fmt == kP010) launch_onepass_n<k420, kP010>(p, nch, grid, s);
-    else launch_onepass_n<k420, -1>(p, nch, grid, s);
+    if (g.hdr.fmt == kP010) launch_onepass_n<k420, kP010>(p, nch, grid, s, edges);
+    else launch_onepass_n<k420, -1>(p, nch, grid, s, edges);
   } else if (g.sdr.fmt == kRgba) {
-    if (g.hdr.fmt == k1010102) launch_onepass_n<kRgba, k1010102>(p, nch, grid, s);
-    else launch_onepass_n<kRgba, -1>(p, nch, grid, s);
+    if (g.hdr.fmt == k1010102) launch_onepass_n<kRgba, k1010102>(p, nch, grid, s, false);
+    else launch_onepass_n<kRgba, -1>(p, nch, grid, s, false);
   } else {
     return hipErrorInvalidValue;
   }
@@ -560,8 +704,10 @@ hipError_t launch_map_blocks_onepass(const GenParams& g, int nch, const uint16_t
 }
 
 // 4:2:0 planes (w, h multiples of 16) -> [convertYuv with matrix c ->] quantized coefficients of Y, Cb, Cr
+// edges: any even w, h -- ceil(w / 16) x ceil(h / 16) MCUs, luma on its ceil(w / 8) x ceil(h / 8) grid, the samples beyond the frame by
+// compressYCbCr's rules (base_edge_quad); a whole-MCU frame takes the kernel it takes without the flag
 hipError_t launch_base_blocks(const ImageView& yuv420, const Mat3* c, const uint16_t* qt_luma, const uint16_t* qt_chroma, int16_t* const coef[3],
-                              hipStream_t s) {
+                              hipStream_t s, bool edges) {
   BaseBlocksParams p;
   memset(&p, 0, sizeof p);
   p.y = (const uint8_t*)yuv420.p[0]; p.u = (const uint8_t*)yuv420.p[1]; p.v = (const uint8_t*)yuv420.p[2];
@@ -572,8 +718,18 @@ hipError_t launch_base_blocks(const ImageView& yuv420, const Mat3* c, const uint
   for (int i = 0; i < 3; i++) p.coef[i] = coef[i];
   fill_quant_table(qt_luma, &p.q.luma);
   fill_quant_table(qt_chroma, &p.q.chroma);
+  if (edges && (yuv420.w % 16 || yuv420.h % 16)) {
+    p.mcus_x = (int)((yuv420.w + 15) / 16); p.mcus_y = (int)((yuv420.h + 15) / 16);
+    p.w = (int)yuv420.w; p.h = (int)yuv420.h; p.aw_y = (p.w + 7) & ~7;
+    p.cm[0] = p.sy >= (uint32_t)p.aw_y ? 0 : 1;  // jpegencoderhelper.cpp:256: strides[i] < alignedPlaneWidth[i] copies rows into a scratch MCU row
+    p.cm[1] = p.su >= (uint32_t)p.mcus_x * 8 ? 0 : 1;
+    p.cm[2] = p.sv >= (uint32_t)p.mcus_x * 8 ? 0 : 1;
+    const int grid = resident_grid(((p.mcus_x + 1) / 2) * p.mcus_y, 8);
+    hipLaunchKernelGGL(base_blocks_kernel<true>, dim3(grid), dim3(kBlock), 0, s, p);
+    return hipGetLastError();
+  }
   const int grid = resident_grid(((p.mcus_x + 1) / 2) * p.mcus_y, 8);
-  hipLaunchKernelGGL(base_blocks_kernel, dim3(grid), dim3(kBlock), 0, s, p);
+  hipLaunchKernelGGL(base_blocks_kernel<false>, dim3(grid), dim3(kBlock), 0, s, p);
   return hipGetLastError();
 }
 

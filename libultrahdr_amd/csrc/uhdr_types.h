@@ -288,11 +288,12 @@ hipError_t launch_minmax_table(const MinmaxTableParams& p, hipStream_t s);
 // gamma_thr: the two-pass byte thresholds of a gamma != 1 (UHDR_HIP_GENERATE_GAMMA_TABLE) for channels without a step table; null: gamma is 1
 hipError_t launch_map_blocks(const float* ratio, const AffineDev* dev, const double* math_tab, int nch, int bw, int bh, const uint16_t* qt_luma,
                              const uint16_t* qt_chroma, int16_t* const coef[3], uint8_t* map_out, uint32_t out_stride, hipStream_t s,
-                             const float* gamma_thr = nullptr);
+                             const float* gamma_thr = nullptr, uint32_t edge_w = 0, uint32_t edge_h = 0);
+// edge_w x edge_h / edges: the kernels for maps and frames that are not whole blocks / MCUs (bw, bh: ceil(edge_w / 8), ceil(edge_h / 8))
 hipError_t launch_map_blocks_onepass(const GenParams& g, int nch, const uint16_t* qt_luma, const uint16_t* qt_chroma, int16_t* const coef[3],
-                                     uint8_t* map_out, uint32_t out_stride, hipStream_t s);
+                                     uint8_t* map_out, uint32_t out_stride, hipStream_t s, bool edges = false);
 hipError_t launch_base_blocks(const ImageView& yuv420, const Mat3* c, const uint16_t* qt_luma, const uint16_t* qt_chroma, int16_t* const coef[3],
-                              hipStream_t s);
+                              hipStream_t s, bool edges = false);
 hipError_t launch_base_blocks_rgba(const ImageView& rgba, const Rgb2Yuv& k, const Mat3* c, const uint16_t* qt_luma, const uint16_t* qt_chroma,
                                    int16_t* const coef[3], hipStream_t s);
 hipError_t launch_selftest(int which, unsigned long long* out, uint32_t arg0, uint32_t arg1, uint32_t seed, const double* math_tab, const AffineDev* dev,

@@ -440,6 +440,49 @@ class UltraHdr:
         return self.encodeApi1ScansAny(sdr_intent, hdr_intent, base_encoding, qt_base, qt_map, out_base, out_map, sdr_is_601, use_luminance,
                                        _fns=(lambda *a: lib.uhdr_hip_encode_api1_scans_ex_dev(*a, fl), lambda *a: lib.uhdr_hip_encode_api1_scans_ex(*a, fl)))
 
+    def encodeApi1FusedEdges(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, flags: int = 0, want_map=True,
+                             gm: Image = None, sdr_is_601=False, use_luminance=True):
+        """encodeApi1FusedOnePass with generateGainMap's flags for frames that are not whole MCUs and maps that are not whole blocks
+        (uhdr_hip_encode_api1_fused_edges_dev; jpegencoderhelper.cpp:246-309): a 4:2:0 SDR intent of any even size, a map of any size.  The
+        coefficient tensors sit on libjpeg's width_in_blocks grids -- luma (ceil(h/8), ceil(w/8), 64), chroma (ceil(h/16), ceil(w/16), 64),
+        map (ceil(mh/8), ceil(mw/8), 64).  An RGBA8888 intent is taken as encodeApi1FusedOnePass takes it: dimensions multiples of 8 and a map
+        of whole 8 x 8 blocks, else UhdrError (the edge handling is for 4:2:0 intents).  gm: a caller's device map image of any stride >= mw (a fresh 64-aligned one when None and
+        want_map).  Returns (base coefficient tensors [3], map coefficient tensors [1 or 3], metadata, gainmap Image or None)."""
+        import torch
+
+        assert _is_dev(sdr_intent, hdr_intent)
+        w, h, dev = sdr_intent.w, sdr_intent.h, sdr_intent.buf.device
+        mw, mh = self.gainmap_dims(w, h)
+        nch = 3 if self.mUseMultiChannelGainMap else 1
+        cdiv = 8 if sdr_intent.fmt == A.UHDR_IMG_FMT_32bppRGBA8888 else 16
+        grid = lambda rows, cols, d: torch.empty((-(-rows // d), -(-cols // d), 64), dtype=torch.int16, device=dev)
+        base = [grid(h, w, 8), grid(h, w, cdiv), grid(h, w, cdiv)]
+        mapc = [grid(mh, mw, 8) for _ in range(nch)]
+        blocks = A.Api1Blocks()
+        for i in range(3):
+            blocks.base_coef[i] = base[i].data_ptr()
+            blocks.map_coef[i] = mapc[i].data_ptr() if i < nch else None
+        qb, qm = self._qt_pair(qt_base), self._qt_pair(qt_map)
+        if gm is None and want_map:
+            gm = Image(A.UHDR_IMG_FMT_24bppRGB888 if nch == 3 else A.UHDR_IMG_FMT_8bppYCbCr400, mw, mh, align=64, device=sdr_intent.device)
+        md = A.GainmapMetadata()
+        cfg = self.encode_cfg(sdr_is_601, use_luminance)
+        self._call(True, self.lib.uhdr_hip_encode_api1_fused_edges_dev, self.ctx.handle, C.byref(sdr_intent.raw), C.byref(hdr_intent.raw), C.byref(cfg),
+                   base_encoding, C.c_void_p(qb.ctypes.data), C.c_void_p(qm.ctypes.data), C.byref(blocks), C.byref(md),
+                   C.byref(gm.raw) if gm is not None else None, C.c_uint(flags))
+        if gm is not None:
+            gm.sync_meta_from_raw()
+        return base, mapc, md, gm
+
+    def encodeApi1ScansEdges(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, out_base, out_map, flags: int = 0,
+                             sdr_is_601=False, use_luminance=True):
+        """encodeApi1ScansEx for frames that are not whole MCUs and maps that are not whole blocks -- 1920 x 1080, 4000 x 3000
+        (uhdr_hip_encode_api1_scans_edges_dev for device images, uhdr_hip_encode_api1_scans_edges for host images): same arguments, same
+        returns; the scans carry the real blocks of the true w x h, as uhdr_hip_jpeg_encode_image writes them."""
+        lib, fl = self.lib, C.c_uint(flags)
+        return self.encodeApi1ScansAny(sdr_intent, hdr_intent, base_encoding, qt_base, qt_map, out_base, out_map, sdr_is_601, use_luminance,
+                                       _fns=(lambda *a: lib.uhdr_hip_encode_api1_scans_edges_dev(*a, fl), lambda *a: lib.uhdr_hip_encode_api1_scans_edges(*a, fl)))
+
     def encodeApi1ScansAny(self, sdr_intent: Image, hdr_intent: Image, base_encoding: int, qt_base, qt_map, out_base, out_map,
                            sdr_is_601=False, use_luminance=True, _fns=None):
         """encodeApi1Scans for both SDR intents API-1 takes, YCbCr 4:2:0 and RGBA8888 (base scan 1x1 / 1x1 / 1x1), in ONE C call.
