@@ -3,21 +3,25 @@ effect_remap_kernel past one item per walker.  The launchers cap their grids at 
 every wave / workgroup walks `for (t = first; t < items; t += walkers)`; the shapes come from tests/tile_loop_shapes.py for
 the compute-unit count of the device the test runs on, so that some walkers take a second trip and some do not, tiles_x is
 neither 1 nor a power of two and each row ends in a ragged tile.  Every comparison is exact: against the staged operators
-(P010, RGBA), tests/resize_port.py and row stripes below the cap (resize), the remap formulas of test_gpu_effects.py."""
+(P010, RGBA), tests/resize_port.py and row stripes below the cap (resize), the remap formulas of test_gpu_effects.py.  At the end of the
+file the per-pixel routes of convertYuv, convert_raw_input_to_ycbcr, libjpeg's colour conversions and toneMap, against their vector routes."""
 import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
+import framed as FR
 import resize_cases as K
 import resize_port as P
+import route_lattice as RL
 import test_gpu_api0_p010 as P0
 import test_gpu_api1_rgba as R
 import test_gpu_effects as E
 import tile_loop_shapes as T
 from libultrahdr_amd import capi as A
 from libultrahdr_amd.images import Image
+from oracle import loader as L
 
 pytestmark = pytest.mark.gpu
 
@@ -216,3 +220,152 @@ def test_effects_past_the_grid_cap(hip_ctx, fmt):
     tiles_x, tiles, walkers = T.effect_walk(1030, 4100)
     assert tiles_x == 5 and tiles > walkers == 16384
     _check_effects(hip_ctx, _random_image(fmt, 4100, 1030, 4 + fmt), [(0, 90, 0, 1030, 4100)])
+
+
+# ---- the per-pixel routes of the oldest launchers (tests/route_lattice.py) ------------------------------------------------------------------
+# Each operator once on a view with odd strides and bases inside a 0xA5 frame (tests/framed.py), which forces its per-pixel kernel, at
+# the shape where that kernel's workgroups (waves) come round again -- and once on an aligned copy of the same samples, which its
+# vector route takes.  The two outputs are equal byte for byte; the integer operators equal the oracle as well.
+def _odd(fmt, w, sample_bytes=1):
+    """(strides, offsets) of a view no vector route takes: odd strides, bases off every alignment the sample size allows."""
+    n = len(FR.plane_samples(fmt, w, 2))
+    widths = [pw for _, pw in FR.plane_samples(fmt, w, 2)]
+    return [pw + 3 - pw % 2 for pw in widths], [sample_bytes * (1 + 2 * (i % 2)) for i in range(n)]
+
+
+def _aligned(fmt, w):
+    widths = [pw for _, pw in FR.plane_samples(fmt, w, 2)]
+    return [-(-pw // 64) * 64 for pw in widths], [0] * len(widths)
+
+
+def _random_bytes(fmt, w, h, seed, cg=A.UHDR_CG_BT_709, ct=A.UHDR_CT_SRGB):
+    img = Image(fmt, w, h, cg, ct, FULL, align=2)
+    img.buf[:] = np.random.default_rng(seed).integers(0, 256, img.buf.size, dtype=np.uint8)
+    return img
+
+
+def _planes_same(got, want, what):
+    for i, (g, w_) in enumerate(zip(got, want)):
+        if not np.array_equal(g, w_):
+            ys, xs = np.nonzero(np.asarray(g) != np.asarray(w_))
+            raise AssertionError(f"{what}: plane {i}: {ys.size} samples differ, the first at row {ys[0]}, column {xs[0]}")
+
+
+@pytest.mark.parametrize("kernel,fmt", [("yuv420", S420), ("yuv444", A.UHDR_IMG_FMT_24bppYCbCr444)])
+def test_convert_yuv_narrow_route_on_the_second_trip(hip_ctx, kernel, fmt):
+    loop = _loop(kernel)
+    w, h = loop.w, loop.h
+    src = _random_bytes(fmt, w, h, loop.items)
+    enc = (A.UHDR_CG_BT_709, A.UHDR_CG_BT_2100)
+    outs = []
+    for strides, offsets in (_odd(fmt, w), _aligned(fmt, w)):
+        case = RL.Case("transform_yuv", kernel, w, h, RL.Layout(fmt, tuple(strides), tuple(offsets)), None, None, {})
+        outs.append(RL.route(case))
+        fr = FR.framed(fmt, w, h, strides, offsets, src=src, device=DEV)
+        A.check(hip_ctx.lib.uhdr_hip_convert_yuv_dev(hip_ctx.handle, C.byref(fr.raw), *enc))
+        hip_ctx.synchronize()
+        FR.assert_frame_intact(fr, what=f"{kernel} {outs[-1]}")
+        outs.append(fr.valid())
+    assert outs[0] == (f"transform_{kernel}_kernel",) and outs[2] == (f"transform_{kernel}_wide_kernel",)
+    _planes_same(outs[1], outs[3], f"{kernel}: the per-pixel route against the vector route")
+    _planes_same(outs[1], L.convert_yuv(P0.oracle_kind(), src, *enc).planes_valid(), f"{kernel}: against the oracle")
+
+
+@pytest.mark.parametrize("kernel,src_fmt,dst_fmt", [("rgb420", R.RGBA, S420), ("rgb444", A.UHDR_IMG_FMT_32bppRGBA1010102, A.UHDR_IMG_FMT_30bppYCbCr444)])
+def test_convert_raw_input_narrow_route_on_the_second_trip(hip_ctx, kernel, src_fmt, dst_fmt):
+    loop = _loop(kernel)
+    w, h = loop.w, loop.h
+    ten = dst_fmt == A.UHDR_IMG_FMT_30bppYCbCr444
+    src = _random_bytes(src_fmt, w, h, loop.items, cg=A.UHDR_CG_DISPLAY_P3)
+    outs = []
+    for lay in (_odd, _aligned):
+        (ss, so), (ds, do) = (lay(src_fmt, w, 4), lay(dst_fmt, w, 2 if ten else 1)) if lay is _odd else (lay(src_fmt, w), lay(dst_fmt, w))
+        case = RL.Case("rgb_to_ycbcr", kernel, w, h, RL.Layout(src_fmt, tuple(ss), tuple(so)), RL.Layout(dst_fmt, tuple(ds), tuple(do)), None, {})
+        outs.append(RL.route(case))
+        sfr, dfr = FR.framed(src_fmt, w, h, ss, so, src=src, device=DEV), FR.framed(dst_fmt, w, h, ds, do, device=DEV)
+        A.check(hip_ctx.lib.uhdr_hip_convert_raw_input_to_ycbcr_dev(hip_ctx.handle, C.byref(sfr.raw), int(not ten), C.byref(dfr.raw)))
+        hip_ctx.synchronize()
+        FR.assert_frame_intact(dfr, what=f"{kernel} {outs[-1]}")
+        FR.assert_frame_intact(sfr, written=(), what=f"{kernel} source")
+        outs.append(dfr.valid())
+    t = "true" if ten else "false"
+    assert outs[0] == (f"rgb_to_ycbcr{kernel[3:]}_kernel<{t}>",) and outs[2] == (f"rgb_to_ycbcr{kernel[3:]}_wide_kernel<{t}>",)
+    _planes_same(outs[1], outs[3], f"{kernel}: the per-pixel route against the vector route")
+    _planes_same(outs[1], L.convert_raw_input_to_ycbcr(P0.oracle_kind(), src, not ten).planes_valid(), f"{kernel}: against the oracle")
+
+
+@pytest.mark.parametrize("direction,rgb_fmt", [("rgb_to_ycc", A.UHDR_IMG_FMT_24bppRGB888), ("ycc_to_rgb", R.RGBA)])
+def test_jpeg_colour_narrow_route_on_the_second_trip(hip_ctx, direction, rgb_fmt):
+    loop = _loop("jpeg_colour")
+    w, h = loop.w, loop.h
+    ycc_fmt = A.UHDR_IMG_FMT_24bppYCbCr444
+    src_fmt, dst_fmt = (rgb_fmt, ycc_fmt) if direction == "rgb_to_ycc" else (ycc_fmt, rgb_fmt)
+    src = _random_bytes(src_fmt, w, h, loop.items)
+    outs = []
+    for lay in (_odd, _aligned):
+        (ss, so), (ds, do) = lay(src_fmt, w), lay(dst_fmt, w)
+        if lay is _odd and rgb_fmt == R.RGBA:  # pixels stay on 4-byte boundaries
+            do = [4]
+        case = RL.Case("jpeg_" + direction, direction, w, h, RL.Layout(src_fmt, tuple(ss), tuple(so)), RL.Layout(dst_fmt, tuple(ds), tuple(do)), None, {})
+        outs.append(RL.route(case))
+        sfr, dfr = FR.framed(src_fmt, w, h, ss, so, src=src, device=DEV), FR.framed(dst_fmt, w, h, ds, do, device=DEV)
+        if direction == "rgb_to_ycc":
+            A.check(hip_ctx.lib.uhdr_hip_jpeg_rgb_to_ycc_dev(hip_ctx.handle, C.byref(sfr.raw), C.byref(dfr.raw)))
+        else:
+            A.check(hip_ctx.lib.uhdr_hip_jpeg_ycc_to_rgb_dev(hip_ctx.handle, C.byref(sfr.raw), 0, C.byref(dfr.raw)))
+        hip_ctx.synchronize()
+        FR.assert_frame_intact(dfr, what=f"{direction} {outs[-1]}")
+        FR.assert_frame_intact(sfr, written=(), what=f"{direction} source")
+        outs.append([p.view(np.uint8) for p in dfr.valid()])
+    bpp = 4 if rgb_fmt == R.RGBA else 3
+    assert outs[0] == (f"jpeg_{direction}_kernel<{bpp}, false>",) and outs[2] == (f"jpeg_{direction}_kernel<{bpp}, true>",)
+    _planes_same(outs[1], outs[3], f"{direction}: the per-pixel route against the vector route")
+    if direction == "rgb_to_ycc":
+        want = L.jpeg_rgb_to_ycc_port(np.ascontiguousarray(src.valid(0)), w, w, h)
+    else:
+        want = [L.jpeg_ycc_to_rgb_port(src.valid(0), src.valid(1), src.valid(2), out_bpp=4, variant=0)]
+    _planes_same(outs[1], want, f"{direction}: against the oracle")
+
+
+def _legal_p010(w, h, ct, cg, seed):
+    """Independent random codes of the limited range in every sample of a P010 image."""
+    rng = np.random.default_rng(seed)
+    img = Image(P010, w, h, cg, ct, LIMITED, 2)
+    img.valid(0)[:] = rng.integers(64, 941, (h, w), dtype=np.uint16) << 6
+    img.valid(1)[:] = rng.integers(64, 961, (h // 2, w), dtype=np.uint16) << 6
+    return img
+
+
+@pytest.mark.parametrize("kernel", ["tone_p010", "tone_pixel"])
+def test_tone_map_narrow_routes_on_the_second_trip(hip_ctx, kernel):
+    """tonemap_p010_kernel with per-pixel loads and byte luma stores against its quad loads and 16-bit stores; tonemap_pixel_kernel, which
+    has one route, on the odd view against the aligned one -- and, being the only check of its loop, against the oracle at the bar of
+    tests/test_gpu_formats.py (+-1 code on <= 1e-4 of the samples)."""
+    loop = _loop(kernel)
+    w, h = loop.w, loop.h
+    if kernel == "tone_p010":
+        src_fmt, dst_fmt, sb = P010, S420, 2
+        hdr = _legal_p010(w, h, A.UHDR_CT_HLG, A.UHDR_CG_BT_2100, loop.items)
+    else:
+        src_fmt, dst_fmt, sb = A.UHDR_IMG_FMT_32bppRGBA1010102, R.RGBA, 4
+        hdr = _random_bytes(src_fmt, w, h, loop.items, cg=A.UHDR_CG_BT_2100, ct=A.UHDR_CT_PQ)
+    outs = []
+    for lay in (_odd, _aligned):
+        (ss, so), (ds, do) = (lay(src_fmt, w, sb), lay(dst_fmt, w, 4 if dst_fmt == R.RGBA else 1)) if lay is _odd else (lay(src_fmt, w), lay(dst_fmt, w))
+        case = RL.Case("tone_map", kernel, w, h, RL.Layout(src_fmt, tuple(ss), tuple(so)), RL.Layout(dst_fmt, tuple(ds), tuple(do)), None,
+                       dict(ct=hdr.raw.ct, cg=hdr.raw.cg))
+        outs.append(RL.route(case))
+        hfr, sfr = FR.framed(src_fmt, w, h, ss, so, src=hdr, device=DEV), FR.framed(dst_fmt, w, h, ds, do, device=DEV)
+        A.check(hip_ctx.lib.uhdr_hip_tone_map_dev(hip_ctx.handle, C.byref(hfr.raw), C.byref(sfr.raw)))
+        hip_ctx.synchronize()
+        FR.assert_frame_intact(sfr, what=f"{kernel} {outs[-1]}")
+        FR.assert_frame_intact(hfr, written=(), what=f"{kernel} hdr intent")
+        outs.append([p.view(np.uint8) for p in sfr.valid()])
+    if kernel == "tone_p010":
+        assert outs[0][1:] == ("p010: pixel loads", "p010: byte luma stores") and outs[2][1:] == ("p010: quad loads", "p010: 16-bit luma store")
+    _planes_same(outs[1], outs[3], f"{kernel}: the odd view against the aligned one")
+    if kernel == "tone_pixel":
+        import test_gpu_formats as TF
+
+        want = L.tone_map(P0.oracle_kind(), hdr)
+        TF.assert_close_codes(outs[1][0], want.valid(0).view(np.uint8), 1e-4, "tone_pixel against the oracle")

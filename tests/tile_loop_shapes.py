@@ -10,6 +10,10 @@ compute units, so the grid arithmetic of each launcher is restated here, line by
   * tiles_x (groups_x) at least 3 and not a power of two (every one of these kernels divides the item index by it),
   * a ragged last tile in each row.
 
+NARROW_KERNELS are the per-pixel routes of the oldest launchers (convertYuv, convert_raw_input_to_ycbcr, libjpeg's colour conversions,
+toneMap), whose loops are `for (t = blockIdx.x; t < tiles; t += gridDim.x)` under grid_for's cap of 4096 workgroups, resident_grid(..., 8) and
+tone_grid(..., 4): the same search, with widths that the vector route of the same operator takes as well.
+
 It raises NoSuchShape where there is none: a device test that cannot reach the second trip has to fail, not pass quietly.
 MIRRORED lists the source lines restated here; the CPU test checks that they still read the same."""
 from collections import namedtuple
@@ -19,6 +23,10 @@ LOW, HIGH = 1.25, 2.5
 TARGET = 1.3  # the ratio aimed at: the smallest image that is safely past LOW
 
 KERNELS = ("p010_two_pass", "p010_one_pass", "rgba", "resize", "effects")
+# the per-pixel ("narrow") routes of the oldest launchers, which a layout off the vector alignment selects (tests/route_lattice.py): their
+# widths are whole vector tiles (8 pixels, 4 for the colour kernels) so that the same samples also run on the vector route
+NARROW_KERNELS = ("yuv420", "yuv444", "rgb420", "rgb444", "jpeg_colour", "tone_pixel", "tone_p010")
+AT_CAP = ("yuv420", "yuv444", "rgb420", "rgb444")  # kernels whose shape also has to reach grid_for's cap of 4096 workgroups
 
 # (file under libultrahdr_amd/csrc, text): what the functions below restate
 MIRRORED = [
@@ -42,6 +50,32 @@ MIRRORED = [
     ("resize_image.hip", "const int grid = (int)(tiles < 16384u ? tiles : 16384u);"),
     ("effects.hip", "const uint32_t tiles = ((p.dst_w + 255u) / 256u) * p.dst_h;"),
     ("effects.hip", "const int grid = (int)(tiles < 16384u ? tiles : 16384u);"),
+    ("convert.hip", "constexpr int kBlock = 256;"),
+    ("convert.hip", "const uint32_t tiles_x = (qw + kBlock - 1) / kBlock, tiles = tiles_x * qh;"),
+    ("convert.hip", "const uint32_t tiles_x = (w + kBlock - 1) / kBlock, tiles = tiles_x * h;"),
+    ("convert.hip", "for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {"),
+    ("convert.hip", "size_t g = (total + kBlock - 1) / kBlock;"),
+    ("convert.hip", "if (g > 4096) g = 4096;"),
+    ("convert.hip", "hipLaunchKernelGGL(transform_yuv420_kernel, dim3(grid_for((size_t)(p.img.w / 2) * (p.img.h / 2))),"),
+    ("convert.hip", "hipLaunchKernelGGL(transform_yuv444_kernel, dim3(grid_for((size_t)p.img.w * p.img.h)), dim3(kBlock), 0, s, p);"),
+    ("convert.hip", "const int g = grid_for((size_t)(p.src.w / 2) * (p.src.h / 2));"),
+    ("convert.hip", "const int g = grid_for((size_t)p.src.w * p.src.h);"),
+    ("jpeg_decode.hip", "const uint32_t per_row = VEC ? p.w / 4 : p.w;"),
+    ("jpeg_decode.hip", "const uint32_t tiles_x = (per_row + kBlock - 1) / kBlock, tiles = tiles_x * p.h;"),
+    ("jpeg_decode.hip", "for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {"),
+    ("jpeg_decode.hip", "const int grid = resident_grid(((per_row + kBlock - 1) / kBlock) * p.h, 8);"),
+    ("upsample_core.h", "const uint32_t r = (uint32_t)(device_cu_count() * per_cu);"),
+    ("upsample_core.h", "return (int)(tiles < r ? (tiles ? tiles : 1u) : r);"),
+    ("tonemap.hip", "constexpr int kQuadBlock = 512;"),
+    ("tonemap.hip", "const uint32_t tiles_x = (qw + 63) / 64, tiles = tiles_x * qh;"),
+    ("tonemap.hip", "const uint32_t nwaves = gridDim.x * (kQuadBlock / 64);"),
+    ("tonemap.hip", "for (uint32_t t = wave; t < tiles; t += nwaves) {"),
+    ("tonemap.hip", "const uint32_t tiles_x = (w + kBlock - 1) / kBlock, tiles = tiles_x * h;"),
+    ("tonemap.hip", "for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {"),
+    ("tonemap.hip", "const int resident = cus * per_cu;"),
+    ("tonemap.hip", "const uint32_t g = tiles < (uint32_t)resident ? tiles : (uint32_t)resident;"),
+    ("tonemap.hip", "const int grid = tone_grid((wave_tiles + kQuadBlock / 64 - 1) / (kQuadBlock / 64), 4);"),
+    ("tonemap.hip", "const int grid = tone_grid(((p.hdr.w + kBlock - 1) / kBlock) * p.hdr.h, 4);"),
 ]
 
 TileLoop = namedtuple("TileLoop", "kernel w h tiles_x items walkers")
@@ -105,6 +139,59 @@ def effect_walk(dst_w, dst_h):
     return tiles_x, tiles, (tiles if tiles < 16384 else 16384)
 
 
+def grid_for(total):
+    """convert.hip: grid_for (one 256-thread workgroup per 256 quads / pixels, at most 4096)."""
+    g = _ceil_div(total, 256)                        # size_t g = (total + kBlock - 1) / kBlock;
+    if g > 4096:                                     # if (g > 4096) g = 4096;
+        g = 4096
+    return 1 if g < 1 else g                         # return (int)(g < 1 ? 1 : g);
+
+
+def convert420_walk(w, h):
+    """(tiles_x, items, walkers) of transform_yuv420_kernel and rgb_to_ycbcr420_kernel on a w x h image; a walker is a workgroup.  The grid
+    counts quads, the loop counts tiles of one quad row: a ragged row makes more tiles than workgroups well below the cap."""
+    qw, qh = w // 2, h // 2
+    tiles_x = _ceil_div(qw, 256)                     # const uint32_t tiles_x = (qw + kBlock - 1) / kBlock, tiles = tiles_x * qh;
+    return tiles_x, tiles_x * qh, grid_for(qw * qh)  # grid_for((size_t)(p.img.w / 2) * (p.img.h / 2))
+
+
+def convert444_walk(w, h):
+    """(tiles_x, items, walkers) of transform_yuv444_kernel and rgb_to_ycbcr444_kernel on a w x h image; a walker is a workgroup."""
+    tiles_x = _ceil_div(w, 256)                      # const uint32_t tiles_x = (w + kBlock - 1) / kBlock, tiles = tiles_x * h;
+    return tiles_x, tiles_x * h, grid_for(w * h)     # grid_for((size_t)p.img.w * p.img.h)
+
+
+def jpeg_colour_walk(cus, w, h):
+    """(tiles_x, items, walkers) of jpeg_rgb_to_ycc_kernel<BPP, false> and jpeg_ycc_to_rgb_kernel<BPP, false>; a walker is a workgroup."""
+    tiles_x = _ceil_div(w, 256)                      # per_row = p.w; tiles_x = (per_row + kBlock - 1) / kBlock
+    tiles = tiles_x * h
+    r = cus * 8                                      # resident_grid(..., 8): const uint32_t r = (uint32_t)(device_cu_count() * per_cu);
+    return tiles_x, tiles, (tiles if tiles < r else r) or 1
+
+
+def tone_grid(cus, tiles, per_cu):
+    """tonemap.hip: tone_grid."""
+    resident = cus * per_cu                          # const int resident = cus * per_cu;
+    g = tiles if tiles < resident else resident      # const uint32_t g = tiles < (uint32_t)resident ? tiles : (uint32_t)resident;
+    return 1 if g < 1 else g                         # return (int)(g < 1 ? 1 : g);
+
+
+def tone_pixel_walk(cus, w, h):
+    """(tiles_x, items, walkers) of tonemap_pixel_kernel; a walker is a workgroup."""
+    tiles_x = _ceil_div(w, 256)
+    tiles = tiles_x * h
+    return tiles_x, tiles, tone_grid(cus, tiles, 4)  # tone_grid(((p.hdr.w + kBlock - 1) / kBlock) * p.hdr.h, 4)
+
+
+def tone_p010_walk(cus, w, h):
+    """(tiles_x, items, walkers) of tonemap_p010_kernel; a walker is a wave (kQuadBlock = 512: eight per workgroup)."""
+    qw, qh = w // 2, h // 2
+    tiles_x = (qw + 63) // 64                        # const uint32_t tiles_x = (qw + 63) / 64, tiles = tiles_x * qh;
+    wave_tiles = tiles_x * qh
+    grid = tone_grid(cus, _ceil_div(wave_tiles, 8), 4)  # tone_grid((wave_tiles + kQuadBlock / 64 - 1) / (kQuadBlock / 64), 4)
+    return tiles_x, wave_tiles, grid * 8             # nwaves = gridDim.x * (kQuadBlock / 64)
+
+
 # ---- the search -----------------------------------------------------------------------------------------------------------------------
 def _is_pow2(n):
     return n & (n - 1) == 0
@@ -121,6 +208,17 @@ def _geometry(kernel, cus):
         return resize_walk, (lambda tx: (tx - 1) * 1024 + 2), (lambda r: r), range(1, MAX_DIM + 1)
     if kernel == "effects":  # 256 elements per tile; even rows, so that a 4:2:0 image has whole chroma planes
         return effect_walk, (lambda tx: (tx - 1) * 256 + 8), (lambda r: r), range(2, MAX_DIM + 1, 2)
+    # the narrow routes: a ragged last tile of whole vector tiles (8 pixels; 4 for the colour kernels)
+    if kernel in ("yuv420", "rgb420"):  # 256 quads per tile, one item row per quad row
+        return convert420_walk, (lambda tx: 2 * ((tx - 1) * 256 + 4)), (lambda r: 2 * r), range(1, MAX_DIM // 2 + 1)
+    if kernel in ("yuv444", "rgb444"):  # 256 pixels per tile
+        return convert444_walk, (lambda tx: (tx - 1) * 256 + 8), (lambda r: r), range(1, MAX_DIM + 1)
+    if kernel == "jpeg_colour":
+        return (lambda w, h: jpeg_colour_walk(cus, w, h)), (lambda tx: (tx - 1) * 256 + 4), (lambda r: r), range(1, MAX_DIM + 1)
+    if kernel == "tone_pixel":
+        return (lambda w, h: tone_pixel_walk(cus, w, h)), (lambda tx: (tx - 1) * 256 + 4), (lambda r: r), range(1, MAX_DIM + 1)
+    if kernel == "tone_p010":  # 64 quads per tile, one item row per quad row
+        return (lambda w, h: tone_p010_walk(cus, w, h)), (lambda tx: 2 * ((tx - 1) * 64 + 1)), (lambda r: 2 * r), range(1, MAX_DIM // 2 + 1)
     raise ValueError(f"unknown kernel {kernel!r}")
 
 
@@ -145,6 +243,8 @@ def tile_loop(kernel, cus):
         cap = walk(w, height_of(rows_allowed[-1]))[2]
         want = _ceil_div(int(TARGET * cap * 1000), 1000 * tx)
         fits = [r for r in rows_allowed if satisfies(TileLoop(kernel, w, height_of(r), *walk(w, height_of(r))))]
+        if kernel in AT_CAP:  # (grid_for counts samples, the loop tiles: a ragged row alone makes a second trip -- take the grid at its cap)
+            fits = [r for r in fits if walk(w, height_of(r))[2] == cap]
         if fits:
             r = min(fits, key=lambda r: (abs(r - want), r))
             return TileLoop(kernel, w, height_of(r), *walk(w, height_of(r)))
