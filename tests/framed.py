@@ -1,5 +1,6 @@
-"""Images as views inside sentinel frames: a plain helper module (no pytest fixtures) for tests/test_route_lattice.py (CPU) and
-tests/test_gpu_route_lattice.py / tests/test_gpu_tile_loops.py (device).
+"""Images as views inside sentinel frames: a plain helper module (no pytest fixtures) for tests/test_route_lattice.py and
+tests/test_apply_lattice.py (CPU) and tests/test_gpu_route_lattice.py / tests/test_gpu_apply_lattice.py / tests/test_gpu_tile_loops.py
+(device).
 
 framed() builds an image of a given format and size whose planes each live in a buffer of their own, filled with GUARD (0xA5):
 guard rows above and below, the caller's stride per plane (in samples, as uhdr_raw_image_t counts them: pixels for the packed
@@ -135,13 +136,32 @@ def tight(fmt, w, h, src):
     return out
 
 
-def assert_frame_intact(frame, written=None, what=""):
+def stripe(frame, row0, rows):
+    """The uhdr_raw_image_t of rows [row0, row0 + rows) of a Frame: a view inside the same buffers, as a caller that shards an image
+    by rows hands it over (row0 and rows even for a format with subsampled chroma rows)."""
+    r = A.RawImage()
+    C.memmove(C.byref(r), C.byref(frame.raw), C.sizeof(A.RawImage))
+    r.h = rows
+    for i, pl in enumerate(frame.planes):
+        k = frame.h // pl.rows if pl.rows else 1  # luma rows per row of this plane
+        assert row0 % k == 0 and rows % k == 0 and row0 + rows <= frame.h, (row0, rows, k)
+        r.planes[i] = frame.raw.planes[i] + (row0 // k) * pl.pitch
+    return r
+
+
+def assert_frame_intact(frame, written=None, what="", rows=None):
     """Every byte of every buffer of `frame` still holds what it was built with, except the samples an operator may write: all
     valid samples (written=None, a destination), none (written=(), an input), or the top-left (w, h) image of the same format
     (an in-place operator that leaves the last column / row of an odd-sized subsampled image alone).  Outside the valid samples
-    that means GUARD: the guard rows, the bytes in front of the base, the padding behind each row."""
+    that means GUARD: the guard rows, the bytes in front of the base, the padding behind each row.  rows=(row0, n): the writable
+    samples are those of rows [row0, row0 + n) only (a destination handed over as a stripe()), at their full width."""
     now = frame.download()
-    if written is None:
+    first = [0] * len(frame.planes)
+    if rows is not None:
+        assert written is None
+        geom = plane_samples(frame.fmt, frame.w, rows[1])
+        first = [rows[0] // (frame.h // pl.rows) * pl.pitch for pl in frame.planes]
+    elif written is None:
         geom = plane_samples(frame.fmt, frame.w, frame.h)
     elif len(written) == 0:
         geom = [(0, 0)] * len(frame.planes)
@@ -150,7 +170,7 @@ def assert_frame_intact(frame, written=None, what=""):
     for i, (buf, was, pl, (rows, width)) in enumerate(zip(now, frame.initial, frame.planes, geom)):
         keep = np.ones(pl.nbytes, dtype=bool)
         if rows and width:
-            _rows(keep, pl, rows, width * pl.bps)[:] = False
+            _rows(keep[first[i]:], pl, rows, width * pl.bps)[:] = False
         bad = np.flatnonzero(keep & (buf != was))
         if bad.size:
             off = int(bad[0]) - pl.base
