@@ -472,9 +472,18 @@ bool encode_api0(uhdr_raw_image_t* hdr_intent, int base_quality, int map_quality
   if (*scale_factor != 1 && !sub) return false;
   const unsigned w = hdr_intent->w, h = hdr_intent->h;
   const unsigned grid = p010 ? 16 : 8;  // whole MCUs: 2x2 / 1x1 / 1x1 sampling for P010, 1x1 otherwise
-  if (w == 0 || h == 0 || w % grid || h % grid || w > 65535 || h > 65535) return false;
-  if (sub) {  // no half float, a map of whole blocks, pitches the vector loads can read
-    if (hdr_intent->fmt == UHDR_IMG_FMT_64bppRGBAHalfFloat || (w / scale) % 8 || (h / scale) % 8) return false;
+  if (w == 0 || h == 0 || w > 65535 || h > 65535) return false;
+  // a frame that is not whole MCUs (1920 x 1080 P010) or whose map is not whole blocks (480 x 270) takes the fused route only when asked
+  // to: UHDR_HIP_SEAM_FUSED_API0_EDGES hands it to uhdr_hip_encode_api0_scans_edges, which makes up the samples beyond the frame the way
+  // JpegEncoderHelper::compressYCbCr reads them from the zero-filled images of this path; without it the per-stage seams run as before.
+  // The two variables above keep gating what they gate.
+  bool edges = false;
+  if (w % grid || h % grid || (sub && ((w / scale) % 8 || (h / scale) % 8))) {
+    if (w % 2 || h % 2 || !getenv("UHDR_HIP_SEAM_FUSED_API0_EDGES")) return false;
+    edges = true;
+  }
+  if (sub) {  // no half float, a frame the scaled front end walks, pitches the vector loads can read
+    if (hdr_intent->fmt == UHDR_IMG_FMT_64bppRGBAHalfFloat || w % 4 || h % scale) return false;
     if (p010 ? (hdr_intent->stride[0] % 2 || hdr_intent->stride[1] % 2) : (hdr_intent->stride[0] % 4 != 0)) return false;
   }
   const unsigned mw = w / scale, mh = h / scale;  // the map's own dimensions
@@ -506,10 +515,10 @@ bool encode_api0(uhdr_raw_image_t* hdr_intent, int base_quality, int map_quality
   sb.h = h; sm.h = mh;
   for (int i = 0; i < 3; i++) {
     const unsigned blk = (p010 && i) ? 16 : 8;
-    sb.blocks_w[i] = (int)(w / blk); sb.blocks_h[i] = (int)(h / blk);
+    sb.blocks_w[i] = (int)((w + blk - 1) / blk); sb.blocks_h[i] = (int)((h + blk - 1) / blk);  // (libjpeg's width_in_blocks: real blocks)
     sb.h_samp[i] = sb.v_samp[i] = (p010 && !i) ? 2 : 1;
   }
-  for (int i = 0; i < nch; i++) { sm.blocks_w[i] = (int)(mw / 8); sm.blocks_h[i] = (int)(mh / 8); sm.h_samp[i] = sm.v_samp[i] = 1; }
+  for (int i = 0; i < nch; i++) { sm.blocks_w[i] = (int)((mw + 7) / 8); sm.blocks_h[i] = (int)((mh + 7) / 8); sm.h_samp[i] = sm.v_samp[i] = 1; }
   unsigned char hb[2048], hm[2048];
   const unsigned char none = 0;
   const size_t nhb = uhdr_hip_jpeg_assemble(&sb, qt_base[0], qt_base[1], &none, 0, hb, sizeof hb);
@@ -521,6 +530,10 @@ bool encode_api0(uhdr_raw_image_t* hdr_intent, int base_quality, int map_quality
   const size_t lead_m = lead_bytes(nhm, map_icc ? map_icc_size : 0, map_comment);
   const size_t lead_b_max = lead_bytes(nhb, kIccRoom, nullptr);
   size_t cap_b = (size_t)w * h * 3 + (1u << 16), cap_m = (size_t)mw * mh * nch + (1u << 16);  // one byte per coefficient: never seen exceeded
+  if (edges) {  // ... of the blocks there are, not of w * h
+    cap_b = ((size_t)sb.blocks_w[0] * sb.blocks_h[0] + 2 * (size_t)sb.blocks_w[1] * sb.blocks_h[1]) * 64 + (1u << 16);
+    cap_m = (size_t)sm.blocks_w[0] * sm.blocks_h[0] * 64 * nch + (1u << 16);
+  }
   if (const char* e = getenv("UHDR_HIP_SEAM_TEST_SMALL_CAP")) {  // (tests: the second attempt below)
     const size_t div = (size_t)(atoi(e) > 1 ? atoi(e) : 16);
     cap_b /= div;
@@ -537,9 +550,8 @@ bool encode_api0(uhdr_raw_image_t* hdr_intent, int base_quality, int map_quality
     out->gainmap_data.reset(new (std::nothrow) unsigned char[lead_m + cap_m + 2]);
     if (!out->base_data || !out->gainmap_data) return false;
     nb = nm = 0;
-    *st = (sub ? uhdr_hip_encode_api0_scans_scaled : uhdr_hip_encode_api0_scans_any)(cur(), hdr_intent, &cfg, qt_base, qt_map, &md, &gm_desc, &cg,
-                                                                                     out->base_data.get() + lead_b_max, cap_b, &nb,
-                                                                                     out->gainmap_data.get() + lead_m, cap_m, &nm);
+    *st = (edges ? uhdr_hip_encode_api0_scans_edges : sub ? uhdr_hip_encode_api0_scans_scaled : uhdr_hip_encode_api0_scans_any)(
+        cur(), hdr_intent, &cfg, qt_base, qt_map, &md, &gm_desc, &cg, out->base_data.get() + lead_b_max, cap_b, &nb, out->gainmap_data.get() + lead_m, cap_m, &nm);
     if (st->error_code == UHDR_CODEC_MEM_ERROR && attempt == 0 && (nb > cap_b || nm > cap_m)) {  // (as in encode_api1: once more with the reported sizes)
       note("encode_api0_fused", true, "scan larger than one byte per coefficient: second attempt with the reported sizes");
       if (nb > cap_b) cap_b = nb + nb / 16 + (1u << 16);

@@ -1119,6 +1119,30 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans_scaled(uhdr_hip_ctx_t* ctx, const u
                                                     size_t base_capacity, size_t* base_bytes, uint8_t* map_scan, size_t map_capacity,
                                                     size_t* map_bytes);
 
+/* uhdr_hip_encode_api0_scans_scaled for frames that are not whole MCUs and maps that are not whole blocks as well -- 1920 x 1080 P010, its
+ * 480 x 270 map at scale factor 4 (lib/src/jpegr.cpp:179-244 through JpegEncoderHelper::compressYCbCr's edge handling,
+ * lib/src/jpegencoderhelper.cpp:246-309).  P010, RGBA1010102 and half-float intents of any even w, h up to 65535; scale factor 1, and 2 / 4
+ * under the front end's rules (RGBA1010102 or P010, w % 4 == 0, h % S == 0, strides the vector loads can read).  The scans carry the real
+ * blocks of libjpeg's width_in_blocks grids -- luma ceil(w / 8) x ceil(h / 8), 4:2:0 chroma ceil(w / 16) x ceil(h / 16), the map
+ * ceil(w / S / 8) x ceil(h / S / 8) -- with the true w, h, as uhdr_hip_jpeg_encode_image writes them.  Beyond the frame the samples are what
+ * the reference reads on this path, where every image is one it allocated zero-filled with a stride of ALIGN(w, 64): columns past a
+ * plane's width are 0 (Cb and Cr too), rows past its height 0 (Y, a one-channel map) / 128 (Cb, Cr); a three-channel map repeats its last
+ * column and row (jpeg_write_scanlines).  A whole-MCU, whole-block request runs what uhdr_hip_encode_api0_scans_scaled runs.
+ * UHDR_CODEC_UNSUPPORTED_FEATURE before anything is uploaded: odd dimensions, w % 4 or h % S at scale factor 2 / 4, a half-float intent at
+ * 2 / 4, a frame too small for its scale factor, a context with a communicator.  UHDR_CODEC_MEM_ERROR with the needed sizes in *_bytes.
+ * _dev: hdr's planes, base_scan and map_scan are DEVICE pointers -- nothing is staged, both scans are Huffman-coded straight into the
+ * caller's buffers, only the two sizes come down; synchronous. */
+uhdr_error_info_t uhdr_hip_encode_api0_scans_edges(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                   const uint16_t qt_base[2][64], const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md,
+                                                   uhdr_raw_image_t* gainmap_desc, uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan,
+                                                   size_t base_capacity, size_t* base_bytes, uint8_t* map_scan, size_t map_capacity,
+                                                   size_t* map_bytes);
+uhdr_error_info_t uhdr_hip_encode_api0_scans_edges_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
+                                                       const uint16_t qt_base[2][64], const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md,
+                                                       uhdr_raw_image_t* gainmap_desc, uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan,
+                                                       size_t base_capacity, size_t* base_bytes, uint8_t* map_scan, size_t map_capacity,
+                                                       size_t* map_bytes);
+
 /* The same on DEVICE-resident intents into DEVICE buffers, and its inverse (round 6): one entry point per direction of the API-1
  * round trip, for callers whose images live in HBM (a transcoding service; bench.py's headline).
  * uhdr_hip_encode_api1_scans_dev: JpegR::encodeJPEGR API-1 (jpegr.cpp:253-316) without the container -- sdr / hdr are device images,

@@ -256,6 +256,28 @@ class UltraHdr {
                                              base_bytes, map_scan, map_capacity, map_bytes);
   }
 
+  // encodeApi0ScansScaled for frames that are not whole MCUs and maps that are not whole blocks as well -- 1920 x 1080 P010
+  // (uhdr_hip_encode_api0_scans_edges); the scans carry the real blocks of the true w x h.
+  // encodeApi0ScansEdgesDev (uhdr_hip_encode_api0_scans_edges_dev): the intent's planes and both scan buffers are device memory.
+  uhdr_error_info_t encodeApi0ScansEdges(uhdr_raw_image_t* hdr_intent, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                         uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_raw_image_t* gainmap_desc, uhdr_color_gamut_t* sdr_cg,
+                                         uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan, size_t map_capacity,
+                                         size_t* map_bytes, bool dev = false) {
+    if (!mCtx) return mCreateStatus;
+    uhdr_hip_encode_cfg_t cfg{mMapDimensionScaleFactor, mUseMultiChannelGainMap ? 1 : 0, mGamma, (int)mEncPreset,
+                              mMinContentBoost, mMaxContentBoost, mTargetDispPeakBrightness, 0, 0};
+    return (dev ? uhdr_hip_encode_api0_scans_edges_dev : uhdr_hip_encode_api0_scans_edges)(mCtx, hdr_intent, &cfg, qt_base, qt_map, gainmap_metadata, gainmap_desc,
+                                                                                          sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
+                                                                                          map_bytes);
+  }
+  uhdr_error_info_t encodeApi0ScansEdgesDev(uhdr_raw_image_t* hdr_intent, const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
+                                            uhdr_gainmap_metadata_t* gainmap_metadata, uhdr_raw_image_t* gainmap_desc, uhdr_color_gamut_t* sdr_cg,
+                                            uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan, size_t map_capacity,
+                                            size_t* map_bytes) {
+    return encodeApi0ScansEdges(hdr_intent, qt_base, qt_map, gainmap_metadata, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan,
+                                map_capacity, map_bytes, /*dev=*/true);
+  }
+
   // The sample -> coefficient part of an API-1 encode on device-resident intents (uhdr_hip_encode_api1_fused_any_dev): the SDR intent is
   // YCbCr 4:2:0 (multiples of 16) or RGBA8888 (multiples of 8; its base image is 4:4:4, three (w/8)*(h/8) coefficient arrays).
   // blocks: device buffers; gainmap_img may be null.

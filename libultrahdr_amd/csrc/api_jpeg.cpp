@@ -994,6 +994,25 @@ static uhdr_error_info_t check_scaled_scans(const uhdr_raw_image_t* hdr, const u
   return ok_status();
 }
 
+// What the _edges entry points decline before anything goes up: every frame the front end's kernels cannot walk.  Whole MCUs and whole
+// blocks are not asked for -- FdctEdge / base_edge_quad / launch_fdct_quant_rgb's vw, vh make up what lies beyond the frame.
+static uhdr_error_info_t check_api0_edges(const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg) {
+  const unsigned w = hdr->w, h = hdr->h;
+  const int s = cfg->map_dimension_scale_factor;
+  if (w == 0 || h == 0 || w % 2 || h % 2 || w > 65535 || h > 65535)
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs even dimensions up to 65535 (received %ux%u); use the operators", w, h);
+  if ((s == 2 || s == 4) && (w / (unsigned)s == 0 || h / (unsigned)s == 0))
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain keeps the scale factor it is given: a %ux%u frame is too small for scale factor %d; "
+                      "use the operators", w, h, s);
+  UHDR_TRY(check_scaled_request(hdr, cfg, true));
+  if (s == 1) return ok_status();
+  const bool p010 = hdr->fmt == UHDR_IMG_FMT_24bppYCbCrP010;
+  if (p010 ? (hdr->stride[0] % 2 || hdr->stride[1] % 2) : (hdr->stride[0] % 4 != 0))
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain at scale factor %d reads the intent with vector loads: strides that are multiples of %d; "
+                      "use the operators", s, p010 ? 2 : 4);
+  return ok_status();
+}
+
 // The driver behind uhdr_hip_encode_api0_scans (any_format == false: RGBA1010102 / RGBA half float only), uhdr_hip_encode_api0_scans_any and
 // uhdr_hip_encode_api0_scans_scaled (scaled: scale factors 2 and 4 as well, for RGBA1010102 and P010 -- the map is then a (w / S) x (h / S) image
 // of whole blocks).  A P010 intent (what camera and video frames arrive as; jpegr.cpp:179-244 compresses the tone mapper's 4:2:0 planes as they
@@ -1002,7 +1021,8 @@ static uhdr_error_info_t check_scaled_scans(const uhdr_raw_image_t* hdr, const u
 static uhdr_error_info_t encode_api0_scans_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
                                                 const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
                                                 uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
-                                                size_t map_capacity, size_t* map_bytes, bool any_format, bool scaled) {
+                                                size_t map_capacity, size_t* map_bytes, bool any_format, bool scaled, bool edges = false,
+                                                bool dev = false) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   if (!hdr || !cfg_in || !qt_base || !qt_map || !md || !base_scan || !map_scan || !base_bytes || !map_bytes)
     return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr argument");
@@ -1013,10 +1033,14 @@ static uhdr_error_info_t encode_api0_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs a full-resolution gain map (scale factor 1), received %d", cfg_in->map_dimension_scale_factor);
   // the base image's layout: cdiv = a chroma block's width in luma samples, csub = luma samples per chroma sample; the image is whole MCUs
   const unsigned w = hdr->w, h = hdr->h, cdiv = p010 ? 16 : 8, csub = cdiv / 8;
-  if (w == 0 || h == 0 || w % cdiv || h % cdiv || w > 65535 || h > 65535)
+  if (edges) UHDR_TRY(check_api0_edges(hdr, cfg_in));
+  else if (w == 0 || h == 0 || w % cdiv || h % cdiv || w > 65535 || h > 65535)
     return p010 ? err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs P010 dimensions that are multiples of 16 (received %ux%u); use the operators", w, h)
                 : err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-0 chain needs dimensions that are multiples of 8 (received %ux%u); use the operators", w, h);
-  if (scaled) UHDR_TRY(check_scaled_scans(hdr, cfg_in));
+  if (scaled && !edges) UHDR_TRY(check_scaled_scans(hdr, cfg_in));
+  if (edges && (c->comm != nullptr || c->comm_custom))
+    return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes of whole MCU rows; frames that are not whole MCUs are encoded "
+                      "whole: use the operators");
   if (c->comm != nullptr || c->comm_custom) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "a context with a communicator encodes stripes");
   UHDR_TRY(validate_image(hdr, "hdr intent"));
   UHDR_TRY(check_quant_tables(qt_base, qt_map));
@@ -1027,16 +1051,34 @@ static uhdr_error_info_t encode_api0_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   cfg.use_luminance = 0;
   const int nch = cfg.use_multi_channel_gainmap ? 3 : 1;
   uhdr_raw_image_t dh;
-  if (c->resident_on) UHDR_TRY(resident_write_back_all(c));
-  UHDR_TRY(stage_in(c, 1, hdr, &dh, true));
+  if (dev) {
+    dh = *hdr;
+  } else {
+    if (c->resident_on) UHDR_TRY(resident_write_back_all(c));
+    UHDR_TRY(stage_in(c, 1, hdr, &dh, true));
+  }
   // device images: the base image's three planes and the map (rows padded to 64 samples), then the coefficient arrays
   const unsigned scale = (unsigned)cfg.map_dimension_scale_factor, mw = w / scale, mh = h / scale;  // (1 unless scaled)
   const size_t pitch = ((size_t)w + 63) & ~(size_t)63, cpitch = ((size_t)(w / csub) + 63) & ~(size_t)63, map_pitch = ((size_t)mw + 63) & ~(size_t)63;
   const size_t plane_y = pitch * h, plane_c = cpitch * (h / csub);
   UHDR_TRY(ensure(c->enc[1], plane_y + 2 * plane_c + 256));
   UHDR_TRY(ensure(c->enc[2], map_pitch * (size_t)nch * mh + 256));
-  const size_t nby = (size_t)(w / 8) * (h / 8), nbc = (size_t)(w / cdiv) * (h / cdiv);
-  const size_t nblocks[6] = {nby, nbc, nbc, nby, nby, nby};  // (the map's arrays have room for a full-resolution map)
+  // the coefficient arrays on libjpeg's width_in_blocks grids (real blocks): what w / 8, w / cdiv are for whole MCUs
+  const int bw_y = (int)((w + 7) / 8), bh_y = (int)((h + 7) / 8), bw_m = (int)((mw + 7) / 8), bh_m = (int)((mh + 7) / 8);
+  const size_t nby = (size_t)bw_y * bh_y, nbc = (size_t)((w + cdiv - 1) / cdiv) * ((h + cdiv - 1) / cdiv);
+  const size_t nbm = edges ? (size_t)bw_m * bh_m : nby;  // (the siblings' map arrays have room for a full-resolution map)
+  const size_t nblocks[6] = {nby, nbc, nbc, nbm, nbm, nbm};
+  // edges: what lies beyond the frame and the map.  Every image on this path is one the reference allocates itself, zero-filled, with a
+  // stride of ALIGN(w, 64) (ultrahdr_api.cpp:45-117), so compressYCbCr (jpegencoderhelper.cpp:246-309) reads zeros behind every width
+  // and its constant rows below every height; the planes here are context scratch with the same pitches but whatever bytes an earlier call
+  // left, hence FdctEdge's column mode 2, which loads nothing there.  A three-channel map goes through jpeg_write_scanlines: last column / row.
+  const bool base_edges = edges && (w % cdiv || h % cdiv), map_edges = edges && (mw % 8 || mh % 8);
+  auto zero_cols = [](unsigned pw, unsigned ph, int fill) {
+    FdctEdge e;
+    memset(&e, 0, sizeof e);
+    e.on = 1; e.w = (int)pw; e.h = (int)ph; e.col_mode = 2; e.fill = fill; e.mcu_rows = 8;
+    return e;
+  };
   int16_t* coef[6];
   UHDR_TRY(carve_coef_arrays(c->enc[0], nblocks, 3 + nch, coef));
   uhdr_raw_image_t ycc, gm;
@@ -1057,16 +1099,45 @@ static uhdr_error_info_t encode_api0_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   }
   if (p010) {
     ProfScope ps(c, "fdct_quant");
-    HIP_TRY(launch_base_blocks(view_of(&ycc), nullptr, qt_base[0], qt_base[1], coef, c->stream));
+    HIP_TRY(launch_base_blocks(view_of(&ycc), nullptr, qt_base[0], qt_base[1], coef, c->stream, base_edges, base_edges ? 2 : -1));
+  } else if (base_edges) {
+    ProfScope ps(c, "fdct_quant");
+    for (int i = 0; i < 3; i++) {
+      const FdctEdge e = zero_cols(w, h, i ? 128 : 0);
+      HIP_TRY(launch_fdct_quant((const uint8_t*)ycc.planes[i], pitch, bw_y, bh_y, qt_base[i ? 1 : 0], coef[i], c->stream, &e));
+    }
   } else {
     for (int i = 0; i < 3; i++)
       UHDR_TRY(uhdr_hip_fdct_quant_dev(c, (const uint8_t*)ycc.planes[i], pitch, (int)(w / 8), (int)(h / 8), qt_base[i ? 1 : 0], coef[i]));
   }
-  if (nch == 3) UHDR_TRY(uhdr_hip_fdct_quant_rgb_dev(c, &gm, qt_map[0], qt_map[1], coef[3], coef[4], coef[5]));
-  else UHDR_TRY(uhdr_hip_fdct_quant_dev(c, (const uint8_t*)gm.planes[0], (size_t)gm.stride[0], (int)(mw / 8), (int)(mh / 8), qt_map[0], coef[3]));
+  if (map_edges) {
+    ProfScope ps(c, "fdct_quant");
+    const FdctEdge e = zero_cols(mw, mh, 0);
+    if (nch == 3) HIP_TRY(launch_fdct_quant_rgb((const uint8_t*)gm.planes[0], (size_t)gm.stride[0] * 3, 3, bw_m, bh_m, qt_map[0], qt_map[1], coef[3], coef[4], coef[5],
+                                                c->stream, (int)mw, (int)mh));
+    else HIP_TRY(launch_fdct_quant((const uint8_t*)gm.planes[0], (size_t)gm.stride[0], bw_m, bh_m, qt_map[0], coef[3], c->stream, &e));
+  } else if (nch == 3) {
+    UHDR_TRY(uhdr_hip_fdct_quant_rgb_dev(c, &gm, qt_map[0], qt_map[1], coef[3], coef[4], coef[5]));
+  } else {
+    UHDR_TRY(uhdr_hip_fdct_quant_dev(c, (const uint8_t*)gm.planes[0], (size_t)gm.stride[0], (int)(mw / 8), (int)(mh / 8), qt_map[0], coef[3]));
+  }
   uhdr_hip_jpeg_scan_t sb, sm;
   fill_scan(&sb, w, h, 3, cdiv, coef);
   fill_scan(&sm, mw, mh, nch, 8, coef + 3);
+  if (dev) {  // straight into the caller's device buffers; the one synchronisation of this route
+    if (base_capacity > 0xFFFFFFF0u) base_capacity = 0xFFFFFFF0u;
+    if (map_capacity > 0xFFFFFFF0u) map_capacity = 0xFFFFFFF0u;
+    size_t nbs = 0, nms = 0;
+    const uhdr_error_info_t e2 = uhdr_hip_huffman_encode2_dev(c, &sb, base_scan, base_capacity, &nbs, &sm, map_scan, map_capacity, &nms);
+    *base_bytes = nbs;
+    *map_bytes = nms;
+    if (e2.error_code != UHDR_CODEC_OK) {
+      (void)hipStreamSynchronize(c->stream);
+      return e2;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return ok_status();
+  }
   // the scans' device buffers: the image planes are free again once the FDCTs have run -- but those are only enqueued, so separate ones
   return scans_to_host(c, &sb, &sm, c->jpg[0], c->jpg[4], base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes);
 }
@@ -1090,6 +1161,25 @@ uhdr_error_info_t uhdr_hip_encode_api0_scans_scaled(uhdr_hip_ctx_t* c, const uhd
                                                     size_t map_capacity, size_t* map_bytes) {
   return encode_api0_scans_impl(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes,
                                 /*any_format=*/true, /*scaled=*/true);
+}
+// ... and for frames that are not whole MCUs and maps that are not whole blocks (1080p P010; a 480 x 270 map): any even w x h the front
+// end's kernels walk, the scans on libjpeg's width_in_blocks grids with the true w, h, and beyond the frame what compressYCbCr
+// (jpegencoderhelper.cpp:246-309) reads from the zero-filled images jpegr.cpp:179-244 allocates.  A whole-MCU, whole-block request runs what
+// uhdr_hip_encode_api0_scans_scaled runs.
+uhdr_error_info_t uhdr_hip_encode_api0_scans_edges(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in, const uint16_t qt_base[2][64],
+                                                   const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md, uhdr_raw_image_t* gainmap_desc,
+                                                   uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity, size_t* base_bytes, uint8_t* map_scan,
+                                                   size_t map_capacity, size_t* map_bytes) {
+  return encode_api0_scans_impl(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes,
+                                /*any_format=*/true, /*scaled=*/true, /*edges=*/true);
+}
+// ... on a DEVICE-resident intent, into DEVICE buffers: nothing is staged and nothing comes down but the two sizes
+uhdr_error_info_t uhdr_hip_encode_api0_scans_edges_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg_in,
+                                                       const uint16_t qt_base[2][64], const uint16_t qt_map[2][64], uhdr_gainmap_metadata_t* md,
+                                                       uhdr_raw_image_t* gainmap_desc, uhdr_color_gamut_t* sdr_cg, uint8_t* base_scan, size_t base_capacity,
+                                                       size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes) {
+  return encode_api0_scans_impl(c, hdr, cfg_in, qt_base, qt_map, md, gainmap_desc, sdr_cg, base_scan, base_capacity, base_bytes, map_scan, map_capacity, map_bytes,
+                                /*any_format=*/true, /*scaled=*/true, /*edges=*/true, /*dev=*/true);
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -385,6 +385,8 @@ __device__ __forceinline__ uint32_t st8(float v) { return (uint32_t)__builtin_am
 // rules, per plane.  Column mode 0 (the stride covers the block-aligned width): columns past the width are the caller's bytes, unconverted;
 // rows past the height are 0 (Y) / 128 (Cb, Cr).  Column mode 1: columns past the width are 0 / 128, rows past the height still hold what the
 // MCU row above copied into the helper's scratch rows -- the converted row 16 (chroma: 8) rows up, zeros in the first MCU row.
+// Column mode 2 (API-0: planes the library allocated zero-filled, whose device copy is not): mode 0 with columns past the width 0 in every
+// plane, and no load there.
 // w and h are even: a quad lies inside or outside as a whole, in each direction.
 __device__ __forceinline__ void base_edge_quad(const BaseBlocksParams& p, int gy, int gx, uint32_t& o0, uint32_t& o1, uint32_t& ou, uint32_t& ov) {
   const bool in_x = gx < p.w, in_y = gy < p.h;
@@ -417,6 +419,7 @@ __device__ __forceinline__ void base_edge_quad(const BaseBlocksParams& p, int gy
   }
   auto chroma = [&](const uint8_t* plane, uint32_t stride, int cm, uint32_t conv) -> uint32_t {
     if (in_x) return (in_y || cm == 1) ? conv : 128u;
+    if (in_y && cm == 2) return 0u;
     return (in_y && cm == 0) ? (uint32_t)plane[(size_t)(gy >> 1) * stride + (gx >> 1)] : 128u;
   };
   ou = chroma(p.u, p.su, p.cm[1], cu);
@@ -705,9 +708,10 @@ hipError_t launch_map_blocks_onepass(const GenParams& g, int nch, const uint16_t
 
 // 4:2:0 planes (w, h multiples of 16) -> [convertYuv with matrix c ->] quantized coefficients of Y, Cb, Cr
 // edges: any even w, h -- ceil(w / 16) x ceil(h / 16) MCUs, luma on its ceil(w / 8) x ceil(h / 8) grid, the samples beyond the frame by
-// compressYCbCr's rules (base_edge_quad); a whole-MCU frame takes the kernel it takes without the flag
+// compressYCbCr's rules (base_edge_quad); a whole-MCU frame takes the kernel it takes without the flag.  col_mode >= 0: every plane's
+// column mode is that one, whatever the strides (2: the API-0 chain's scratch planes)
 hipError_t launch_base_blocks(const ImageView& yuv420, const Mat3* c, const uint16_t* qt_luma, const uint16_t* qt_chroma, int16_t* const coef[3],
-                              hipStream_t s, bool edges) {
+                              hipStream_t s, bool edges, int col_mode) {
   BaseBlocksParams p;
   memset(&p, 0, sizeof p);
   p.y = (const uint8_t*)yuv420.p[0]; p.u = (const uint8_t*)yuv420.p[1]; p.v = (const uint8_t*)yuv420.p[2];
@@ -724,6 +728,7 @@ hipError_t launch_base_blocks(const ImageView& yuv420, const Mat3* c, const uint
     p.cm[0] = p.sy >= (uint32_t)p.aw_y ? 0 : 1;  // jpegencoderhelper.cpp:256: strides[i] < alignedPlaneWidth[i] copies rows into a scratch MCU row
     p.cm[1] = p.su >= (uint32_t)p.mcus_x * 8 ? 0 : 1;
     p.cm[2] = p.sv >= (uint32_t)p.mcus_x * 8 ? 0 : 1;
+    if (col_mode >= 0) p.cm[0] = p.cm[1] = p.cm[2] = col_mode;
     const int grid = resident_grid(((p.mcus_x + 1) / 2) * p.mcus_y, 8);
     hipLaunchKernelGGL(base_blocks_kernel<true>, dim3(grid), dim3(kBlock), 0, s, p);
     return hipGetLastError();

@@ -23,11 +23,14 @@ constexpr int kBlock = 256;  // 4 waves = 32 blocks per workgroup iteration
 //     helper hands libjpeg pointers into the caller's rows), rows >= h are a constant row of `fill` (mPlanesMCURow);
 //   it does not (col_mode 1): the helper copies every row into a scratch MCU row whose tail is `fill`; rows >= h are never
 //     written, they still hold what the PREVIOUS MCU row copied there -- row y - mcu_rows of the plane (zeros in the first).
+//   col_mode 2 is col_mode 0 for a plane the library allocated itself (API-0: uhdr_raw_image_ext_t zero-fills, stride ALIGN(w, 64)):
+//     columns >= w are 0 whatever the component, and nothing is loaded there -- the device copy's bytes behind the width are not the
+//     allocation's; rows >= h are the constant `fill` row.
 __device__ __forceinline__ void load8_edge(const uint8_t* plane, size_t stride, int x0, int y, const FdctEdge& e, int in[8]) {
   int ys = y;
   bool row_const = false;
   if (y >= e.h) {
-    if (e.col_mode == 0) row_const = true;
+    if (e.col_mode != 1) row_const = true;
     else ys = y - e.mcu_rows;
   }
 #pragma unroll
@@ -35,7 +38,7 @@ __device__ __forceinline__ void load8_edge(const uint8_t* plane, size_t stride, 
     const int x = x0 + c;
     int v;
     if (row_const) v = e.fill;
-    else if (x >= e.w) v = e.col_mode == 0 ? (int)plane[(size_t)ys * stride + x] : e.fill;
+    else if (x >= e.w) v = e.col_mode == 0 ? (int)plane[(size_t)ys * stride + x] : (e.col_mode == 2 ? 0 : e.fill);
     else v = ys < 0 ? 0 : (int)plane[(size_t)ys * stride + x];
     in[c] = v - 128;
   }

@@ -293,7 +293,7 @@ hipError_t launch_map_blocks(const float* ratio, const AffineDev* dev, const dou
 hipError_t launch_map_blocks_onepass(const GenParams& g, int nch, const uint16_t* qt_luma, const uint16_t* qt_chroma, int16_t* const coef[3],
                                      uint8_t* map_out, uint32_t out_stride, hipStream_t s, bool edges = false);
 hipError_t launch_base_blocks(const ImageView& yuv420, const Mat3* c, const uint16_t* qt_luma, const uint16_t* qt_chroma, int16_t* const coef[3],
-                              hipStream_t s, bool edges = false);
+                              hipStream_t s, bool edges = false, int col_mode = -1);
 hipError_t launch_base_blocks_rgba(const ImageView& rgba, const Rgb2Yuv& k, const Mat3* c, const uint16_t* qt_luma, const uint16_t* qt_chroma,
                                    int16_t* const coef[3], hipStream_t s);
 hipError_t launch_selftest(int which, unsigned long long* out, uint32_t arg0, uint32_t arg1, uint32_t seed, const double* math_tab, const AffineDev* dev,
@@ -312,7 +312,9 @@ hipError_t launch_rgb_to_ycbcr(const RgbToYcbcrParams& p, hipStream_t s);
 // Samples of partial edge blocks, made up on the device the way JpegEncoderHelper::compressYCbCr does on the host
 // (jpegencoderhelper.cpp:246-309): w x h valid samples; col_mode 0 = the plane's pitch covers the block-aligned width and the
 // bytes beyond w are read as they are, rows beyond h are constant `fill`; col_mode 1 = columns beyond w are `fill`, rows beyond
-// h repeat row y - mcu_rows (the helper's stale scratch row; zeros before the first).  fill: 0 for component 0, 128 else.
+// h repeat row y - mcu_rows (the helper's stale scratch row; zeros before the first); col_mode 2 = col_mode 0 for a plane the
+// library allocated zero-filled (API-0): columns beyond w are 0 and are not loaded, rows beyond h are constant `fill`.
+// fill: 0 for component 0, 128 else.
 struct FdctEdge {
   int on, w, h, col_mode, fill, mcu_rows;
 };

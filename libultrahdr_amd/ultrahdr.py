@@ -337,6 +337,31 @@ class UltraHdr:
         the gainmap descriptor carries the map's (w / S) x (h / S)."""
         return self.encodeApi0ScansAny(hdr_intent, qt_base, qt_map, base_capacity, map_capacity, _fn=self.lib.uhdr_hip_encode_api0_scans_scaled)
 
+    def encodeApi0ScansEdges(self, hdr_intent: Image, qt_base, qt_map, base_capacity: int, map_capacity: int):
+        """encodeApi0ScansScaled for frames that are not whole MCUs and maps that are not whole blocks as well -- 1920 x 1080 P010, its
+        480 x 270 map (uhdr_hip_encode_api0_scans_edges): same arguments, same returns; the scans carry the real blocks of the true
+        w x h, as uhdr_hip_jpeg_encode_image writes them from the zero-filled images the reference allocates on this path."""
+        return self.encodeApi0ScansAny(hdr_intent, qt_base, qt_map, base_capacity, map_capacity, _fn=self.lib.uhdr_hip_encode_api0_scans_edges)
+
+    def encodeApi0ScansEdgesDev(self, hdr_intent: Image, qt_base, qt_map, out_base, out_map):
+        """encodeApi0ScansEdges on a DEVICE intent into DEVICE buffers (uhdr_hip_encode_api0_scans_edges_dev): out_base / out_map are
+        uint8 CUDA tensors that receive the entropy-coded scans; nothing is staged and only the sizes come down.  Returns (the base
+        scan, the map scan -- views of out_base / out_map --, metadata, gainmap descriptor, gamut of the SDR rendition); a UhdrError
+        for a tensor that is too small carries the needed sizes in .needed."""
+        assert _is_dev(hdr_intent) and out_base.is_cuda and out_map.is_cuda
+        qb, qm = self._qt_pair(qt_base), self._qt_pair(qt_map)
+        md, desc, cg = A.GainmapMetadata(), A.RawImage(), C.c_int(0)
+        cfg = self.encode_cfg(False, False)
+        nb, nm = C.c_size_t(0), C.c_size_t(0)
+        try:
+            self._call(True, self.lib.uhdr_hip_encode_api0_scans_edges_dev, self.ctx.handle, C.byref(hdr_intent.raw), C.byref(cfg),
+                       C.c_void_p(qb.ctypes.data), C.c_void_p(qm.ctypes.data), C.byref(md), C.byref(desc), C.byref(cg), C.c_void_p(out_base.data_ptr()),
+                       int(out_base.numel()), C.byref(nb), C.c_void_p(out_map.data_ptr()), int(out_map.numel()), C.byref(nm))
+        except A.UhdrError as e:
+            e.needed = (int(nb.value), int(nm.value))
+            raise
+        return out_base[:nb.value], out_map[:nm.value], md, desc, int(cg.value)
+
     def encodeApi0ScansAny(self, hdr_intent: Image, qt_base, qt_map, base_capacity: int, map_capacity: int, any_format=True, _fn=None):
         """JpegR::encodeJPEGR API-0 (jpegr.cpp:179-244) without the container in ONE C call on a HOST intent: RGBA1010102, RGBA half
         float or P010 (uhdr_hip_encode_api0_scans_any; any_format=False: uhdr_hip_encode_api0_scans, which declines P010).
