@@ -309,9 +309,17 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
   // a 4:2:0 frame that is not whole MCUs (1920 x 1080) or whose map is not whole blocks takes the fused route only when asked to:
   // UHDR_HIP_SEAM_FUSED_EDGES hands it to uhdr_hip_encode_api1_scans_edges, which makes up the samples beyond the frame the way
   // JpegEncoderHelper::compressYCbCr does; without it the per-stage seams run as before.  The preset and gamma conditions above stay what they are.
-  bool edges = false;
+  // An RGBA8888 frame that is not whole blocks, or whose map is not (1920 x 1080 at scale factor 2 or 4, every crop), takes it only when asked
+  // to as well: UHDR_HIP_SEAM_FUSED_RGBA_EDGES (beside UHDR_HIP_SEAM_FUSED_RGBA_SDR) hands it to the same entry point with
+  // UHDR_HIP_ENCODE_RGBA_EDGES; any size, odd ones included -- the entry point answers for what the HDR intent's format needs.
+  bool edges = false, rgba_edges = false;
   if (w % grid || h % grid || mw % 8 || mh % 8) {
-    if (rgba || sdr_intent->fmt != UHDR_IMG_FMT_12bppYCbCr420 || w % 2 || h % 2 || !getenv("UHDR_HIP_SEAM_FUSED_EDGES")) return false;
+    if (rgba) {
+      if (!getenv("UHDR_HIP_SEAM_FUSED_RGBA_EDGES")) return false;
+      rgba_edges = true;
+    } else if (sdr_intent->fmt != UHDR_IMG_FMT_12bppYCbCr420 || w % 2 || h % 2 || !getenv("UHDR_HIP_SEAM_FUSED_EDGES")) {
+      return false;
+    }
     if ((preset == UHDR_USAGE_REALTIME && !realtime) || (gamma != 1.0f && !gamma_ex)) return false;  // (what the whole-MCU entry points decline)
     edges = true;
   }
@@ -379,7 +387,7 @@ bool encode_api1(uhdr_raw_image_t* hdr_intent, uhdr_raw_image_t* sdr_intent, int
     if (edges)
       *st = uhdr_hip_encode_api1_scans_edges(cur(), sdr_intent, hdr_intent, &cfg, UHDR_CG_DISPLAY_P3, qt_base, qt_map, &md, &gm_desc,
                                              out->base_data.get() + lead_b, cap_b, &nb, out->gainmap_data.get() + lead_m, cap_m, &nm,
-                                             gamma_ex ? UHDR_HIP_GENERATE_GAMMA_TABLE : 0u);
+                                             (gamma_ex ? UHDR_HIP_GENERATE_GAMMA_TABLE : 0u) | (rgba_edges ? UHDR_HIP_ENCODE_RGBA_EDGES : 0u));
     else if (gamma_ex)
       *st = uhdr_hip_encode_api1_scans_ex(cur(), sdr_intent, hdr_intent, &cfg, UHDR_CG_DISPLAY_P3, qt_base, qt_map, &md, &gm_desc,
                                           out->base_data.get() + lead_b, cap_b, &nb, out->gainmap_data.get() + lead_m, cap_m, &nm,

@@ -1047,7 +1047,7 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans_ex_dev(uhdr_hip_ctx_t* ctx, const u
  * JpegEncoderHelper::compressYCbCr's edge handling, lib/src/jpegencoderhelper.cpp:246-309) ---------------------------------------------
  * 1920 x 1080, 4000 x 3000, any frame uhdr_enc_set_raw_image admits.  Three entry points: the front end with the parameter list of
  * uhdr_hip_encode_api1_fused_onepass_dev plus flags, the two scans forms with the parameter lists of uhdr_hip_encode_api1_scans_ex /
- * _ex_dev.  flags: 0 or UHDR_HIP_GENERATE_GAMMA_TABLE; unknown bits are UHDR_CODEC_INVALID_PARAM.  A request the _ex siblings take runs
+ * _ex_dev.  flags: UHDR_HIP_GENERATE_GAMMA_TABLE, UHDR_HIP_ENCODE_RGBA_EDGES (below); unknown bits are UHDR_CODEC_INVALID_PARAM.  A request the _ex siblings take runs
  * exactly what they run.  In addition:
  *   - a UHDR_IMG_FMT_12bppYCbCr420 SDR intent of any even w, h >= 2.  Coefficient arrays sit on libjpeg's width_in_blocks grids, as for
  *     uhdr_hip_jpeg_encode_image: luma ceil(w / 8) x ceil(h / 8), chroma ceil((w / 2) / 8) x ceil((h / 2) / 8); a luma block that only
@@ -1062,10 +1062,22 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans_ex_dev(uhdr_hip_ctx_t* ctx, const u
  * Both presets, one and three channels, gamma 1 and the table gamma, every HDR format.  The scans carry the real blocks with the true w, h
  * and equal uhdr_hip_convert_yuv + uhdr_hip_jpeg_encode_image on the caller's strides, uhdr_hip_generate_gainmap(_ex) into a zero-filled
  * map of stride ALIGN(mw, 64) + uhdr_hip_jpeg_encode_image, byte for byte; scan capacities are a matter of block counts, not of w * h.
- * UHDR_CODEC_UNSUPPORTED_FEATURE before anything is uploaded or launched: an odd or empty 4:2:0 frame, an RGBA8888 SDR intent whose dimensions
- * are not multiples of 8 or whose map (w / S) x (h / S) is not whole 8 x 8 blocks (the edge handling, the map's included, is for 4:2:0
- * intents), a context with a communicator, a frame so small that generateGainMap changes the scale factor (w / S or h / S == 0).  A scale
- * factor below 1 is UHDR_CODEC_INVALID_PARAM, as for uhdr_hip_generate_gainmap. */
+ * UHDR_CODEC_UNSUPPORTED_FEATURE before anything is uploaded or launched: an odd or empty 4:2:0 frame, without UHDR_HIP_ENCODE_RGBA_EDGES an
+ * RGBA8888 SDR intent whose dimensions are not multiples of 8 or whose map (w / S) x (h / S) is not whole 8 x 8 blocks (without that flag the
+ * edge handling, the map's included, is for 4:2:0 intents), a context with a communicator, a frame so small that generateGainMap changes the scale factor (w / S or h / S == 0).  A scale
+ * factor below 1 is UHDR_CODEC_INVALID_PARAM, as for uhdr_hip_generate_gainmap.
+ * UHDR_HIP_ENCODE_RGBA_EDGES (these three entry points only; every other entry point answers UHDR_CODEC_INVALID_PARAM for it; combines with
+ * UHDR_HIP_GENERATE_GAMMA_TABLE): the edge handling for a UHDR_IMG_FMT_32bppRGBA8888 SDR intent as well -- any w, h >= 1 that
+ * uhdr_hip_generate_gainmap takes for the pair of intents (the chain adds no parity rule: an odd frame is fine unless the HDR format
+ * forbids it), any pitch >= w pixels, base address a multiple of 4, every scale factor whose map is 1 x 1 at least, and with gm given any
+ * stride and address.  The three base arrays (1x1 / 1x1 / 1x1 scan) sit on ceil(w / 8) x ceil(h / 8), the map on ceil(mw / 8) x ceil(mh / 8).
+ * Samples beyond the frame follow the reference, which converts an RGBA intent into an image it allocated itself -- zero-filled, stride
+ * ALIGN(w, 64) -- so that compressYCbCr always sees a stride that covers the aligned width: columns past the width are byte 0 in Y, Cb and
+ * Cr, rows past the height are 0 (Y) / 128 (Cb, Cr) over the whole aligned width, and NO byte of the caller's behind w pixels of a row is
+ * ever read.  The scans equal uhdr_hip_convert_raw_input_to_ycbcr (a fresh zero-filled image of stride ALIGN(w, 64)) + uhdr_hip_convert_yuv
+ * + uhdr_hip_jpeg_encode_image and the map chain above, byte for byte.  A request that is whole blocks in frame and map runs the kernels it
+ * runs without the flag; a 4:2:0 intent ignores the flag.  Still declined: a communicator, w / S or h / S == 0, a scale factor below 1. */
+#define UHDR_HIP_ENCODE_RGBA_EDGES 0x4u
 uhdr_error_info_t uhdr_hip_encode_api1_fused_edges_dev(uhdr_hip_ctx_t* ctx, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
                                                        const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
                                                        const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],

@@ -44,6 +44,8 @@ FLT_MAX = 3.4028234663852886e38
 UHDR_HIP_APPLY_RESIZED_MAP, UHDR_HIP_APPLY_GAMMA_TABLE = 0x1, 0x2
 # generateGainMap flags (uhdr_hip_generate_gainmap_ex and its siblings)
 UHDR_HIP_GENERATE_GAMMA_TABLE = 0x1
+# ... and on the three API-1 _edges entry points only: the edge handling for an RGBA8888 SDR intent too
+UHDR_HIP_ENCODE_RGBA_EDGES = 0x4
 
 
 class ErrorInfo(C.Structure):  # uhdr_error_info_t

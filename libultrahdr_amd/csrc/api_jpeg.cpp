@@ -396,6 +396,7 @@ enum Api1Route : unsigned {
   kApi1Onepass = 4,  // the real-time preset is taken too
   kApi1GammaTable = 8,  // UHDR_HIP_GENERATE_GAMMA_TABLE: a gamma != 1 is taken, through the host's byte thresholds (gamma_code.h)
   kApi1Edges = 16,   // the _edges entry points: 4:2:0 frames that are not whole MCUs and maps that are not whole blocks are taken
+  kApi1RgbaEdges = 32,  // UHDR_HIP_ENCODE_RGBA_EDGES on the _edges entry points: RGBA8888 frames and their maps that are not whole blocks too
 };
 
 // What the chain declines whatever else the request holds -- the SDR intent's format and MCU rule, the preset, gamma -- stated once: the
@@ -403,7 +404,10 @@ enum Api1Route : unsigned {
 static uhdr_error_info_t check_api1_request(const uhdr_raw_image_t* sdr, const uhdr_hip_encode_cfg_t* cfg, unsigned route, bool whole_image) {
   const bool empty = sdr->w == 0 || (whole_image && sdr->h == 0);
   if (route & kApi1Edges) {  // (whole images only)
-    if (sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888 && (sdr->w % 8 || sdr->h % 8 || sdr->w == 0 || sdr->h == 0))
+    if (sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888 && (route & kApi1RgbaEdges) && (sdr->w == 0 || sdr->h == 0))
+      return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain takes a UHDR_IMG_FMT_32bppRGBA8888 SDR intent of 1x1 at least (received %ux%u); "
+                        "use the operators", sdr->w, sdr->h);
+    if (sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888 && !(route & kApi1RgbaEdges) && (sdr->w % 8 || sdr->h % 8 || sdr->w == 0 || sdr->h == 0))
       return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain has edge handling for 4:2:0 base images only: a UHDR_IMG_FMT_32bppRGBA8888 SDR intent "
                         "needs dimensions that are multiples of 8 (received %ux%u); use the operators", sdr->w, sdr->h);
     if (sdr->fmt != UHDR_IMG_FMT_32bppRGBA8888 && sdr->fmt != UHDR_IMG_FMT_12bppYCbCr420)
@@ -440,7 +444,7 @@ static uhdr_error_info_t check_api1_request(const uhdr_raw_image_t* sdr, const u
 //
 // kApi1AnySdr (uhdr_hip_encode_api1_fused_any_dev): a packed RGBA8888 SDR intent is taken as well -- the other form API-1 accepts (jpegr.cpp:247-291),
 // whose base image is YCbCr 4:4:4: the gain-map passes read it as they are (pass 1 fetches RGBA8888), launch_base_blocks_rgba is the base
-// launch (three (w / 8) x (h / 8) coefficient arrays), dimensions are multiples of 8, whole images only.
+// launch (three (w / 8) x (h / 8) coefficient arrays), dimensions are multiples of 8 (any size on ceil grids with kApi1RgbaEdges), whole images only.
 static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
                                                 const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
                                                 const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
@@ -457,6 +461,9 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   // edges (uhdr_hip_encode_api1_fused_edges_dev): a 4:2:0 frame of any even size and a map of any size -- launch_base_blocks and the map
   // launches with their EDGE kernels where the request is not whole MCUs / blocks, the kernels of the siblings where it is
   const bool edges = (route & kApi1Edges) != 0;
+  // rgba_edges (UHDR_HIP_ENCODE_RGBA_EDGES): the same for an RGBA8888 frame of any size -- launch_base_blocks_rgba's EDGE kernel, and the EDGE
+  // map kernels on its map; without the flag an RGBA8888 request stays whole blocks in frame, map and map image
+  const bool rgba_edges = edges && rgba && (route & kApi1RgbaEdges);
   bool map_edges = false;
   const float* gamma_thr2 = nullptr;  // two pass, gamma != 1: the thresholds behind the range kernel's tables and the map kernel's per-sample tail
   float gamma_gap = 0.0f;
@@ -485,8 +492,8 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
     if (edges && p.scale != (uint32_t)cfg->map_dimension_scale_factor)
       return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain keeps the scale factor it is given: a %ux%u frame is too small for scale factor %d "
                         "(generateGainMap would take %u); use the operators", sdr->w, sdr->h, cfg->map_dimension_scale_factor, p.scale);
-    map_edges = edges && !rgba && (p.map_w % 8 || p.map_h % 8);
-    if (edges && rgba && (p.map_w % 8 || p.map_h % 8))  // (the EDGE map kernels read 4:2:0 intents: what the scans forms answer)
+    map_edges = edges && (!rgba || rgba_edges) && (p.map_w % 8 || p.map_h % 8);
+    if (edges && rgba && !rgba_edges && (p.map_w % 8 || p.map_h % 8))  // (an RGBA8888 intent's EDGE kernels are behind their flag: what the scans forms answer)
       return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs map dimensions that are multiples of 8 (scale factor %d on %ux%u)",
                         cfg->map_dimension_scale_factor, sdr->w, sdr->h);
     if (!edges && (p.scale != (uint32_t)cfg->map_dimension_scale_factor || p.map_w % 8 || p.map_h % 8))
@@ -508,7 +515,7 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
       if (!gm->planes[0]) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for the gainmap image's plane");
       if (gm->stride[0] < gm->w) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap stride (%u) cannot be less than its width (%u)", gm->stride[0], gm->w);
       if (((uintptr_t)gm->planes[0] | ((size_t)gm->stride[0] * nch)) & 7) {
-        if (!edges || rgba) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain stores the map in 8-byte pieces: aligned rows");
+        if (!edges || (rgba && !rgba_edges)) return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain stores the map in 8-byte pieces: aligned rows");
         map_edges = true;  // (the EDGE kernels store the map byte by byte)
       }
       map_out = (uint8_t*)gm->planes[0];
@@ -541,7 +548,7 @@ static uhdr_error_info_t encode_api1_fused_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   if (local.error_code != UHDR_CODEC_OK && !striped) return local;
   if (one) UHDR_TRY(fill_onepass_range(c, cfg, hdr_white_nits, use_base_cg, &p, md, gamma_table));  // the metadata is host arithmetic: complete here
   auto base_launch = [&](hipStream_t s) -> hipError_t {
-    if (rgba) return launch_base_blocks_rgba(view_of(sdr), base_k, convert ? &conv : nullptr, qt_base[0], qt_base[1], blocks->base_coef, s);
+    if (rgba) return launch_base_blocks_rgba(view_of(sdr), base_k, convert ? &conv : nullptr, qt_base[0], qt_base[1], blocks->base_coef, s, rgba_edges);
     return launch_base_blocks(view_of(sdr), convert ? &conv : nullptr, qt_base[0], qt_base[1], blocks->base_coef, s, edges);
   };
   bool run = local.error_code == UHDR_CODEC_OK && !empty;
@@ -721,9 +728,11 @@ static uhdr_error_info_t stage_in_420_edges(uhdr_hip_ctx* c, const uhdr_raw_imag
   return ok_status();
 }
 
-static uhdr_error_info_t check_api1_flags(unsigned int flags, unsigned* route);
+static uhdr_error_info_t check_api1_flags(unsigned int flags, unsigned* route, bool edges_entry = false);
 // ... and for frames that are not whole MCUs / maps that are not whole blocks (jpegr.cpp:247-291 through compressYCbCr's edge handling,
-// jpegencoderhelper.cpp:246-309), with generateGainMap's flags
+// jpegencoderhelper.cpp:246-309), with generateGainMap's flags -- and UHDR_HIP_ENCODE_RGBA_EDGES, which these three entry points alone know:
+// an RGBA8888 frame of any size.  The reference converts such an intent into a zero-filled image of stride ALIGN(w, 64) it allocated itself
+// (gainmapmath.cpp:1447-1449), so compressYCbCr never sees the caller's pitch: nothing behind the width is input, and stage_in's copy suffices
 uhdr_error_info_t uhdr_hip_encode_api1_fused_edges_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr,
                                                        const uhdr_hip_encode_cfg_t* cfg, uhdr_color_gamut_t base_encoding,
                                                        const uint16_t qt_base[2][64], const uint16_t qt_map[2][64],
@@ -731,7 +740,7 @@ uhdr_error_info_t uhdr_hip_encode_api1_fused_edges_dev(uhdr_hip_ctx_t* c, const 
                                                        unsigned int flags) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   unsigned route = kApi1Dev | kApi1AnySdr | kApi1Onepass | kApi1Edges;
-  UHDR_TRY(check_api1_flags(flags, &route));
+  UHDR_TRY(check_api1_flags(flags, &route, /*edges_entry=*/true));
   return encode_api1_fused_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, blocks, md, gm, route);
 }
 
@@ -750,12 +759,13 @@ static uhdr_error_info_t encode_api1_scans_impl(uhdr_hip_ctx_t* c, const uhdr_ra
   const bool rgba = (route & kApi1AnySdr) && sdr->fmt == UHDR_IMG_FMT_32bppRGBA8888;  // base image 4:4:4: a 1x1 / 1x1 / 1x1 scan
   const int scale = cfg->map_dimension_scale_factor;
   // edges (uhdr_hip_encode_api1_scans_edges / _edges_dev): a 4:2:0 frame that is not whole MCUs, a map that is not whole blocks
-  const bool edges = (route & kApi1Edges) != 0, edges420 = edges && !rgba;
+  // (with UHDR_HIP_ENCODE_RGBA_EDGES an RGBA8888 frame and its map as well: the grids below are ceil grids for every format)
+  const bool edges = (route & kApi1Edges) != 0, edges420 = edges && !rgba, edges_map = edges && (!rgba || (route & kApi1RgbaEdges));
   if (edges && scale < 1) return err_status(UHDR_CODEC_INVALID_PARAM, "gainmap scale factor %d is not positive", scale);  // (fill_gen_params' answer)
   if (edges && (sdr->w / (unsigned)scale == 0 || sdr->h / (unsigned)scale == 0))
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain keeps the scale factor it is given: a %ux%u frame is too small for scale factor %d; use the operators",
                       sdr->w, sdr->h, scale);
-  if (!edges420 && (scale < 1 || sdr->w / (unsigned)scale == 0 || sdr->h / (unsigned)scale == 0 || (sdr->w / (unsigned)scale) % 8 || (sdr->h / (unsigned)scale) % 8))
+  if (!edges_map && (scale < 1 || sdr->w / (unsigned)scale == 0 || sdr->h / (unsigned)scale == 0 || (sdr->w / (unsigned)scale) % 8 || (sdr->h / (unsigned)scale) % 8))
     return err_status(UHDR_CODEC_UNSUPPORTED_FEATURE, "the fused API-1 chain needs map dimensions that are multiples of 8 (scale factor %d on %ux%u)", scale, sdr->w, sdr->h);
   if (hdr->w != sdr->w || hdr->h != sdr->h)
     return err_status(UHDR_CODEC_INVALID_PARAM, "sdr intent resolution %ux%u and hdr intent resolution %ux%u do not match", sdr->w, sdr->h, hdr->w, hdr->h);
@@ -926,10 +936,12 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans_onepass(uhdr_hip_ctx_t* c, const uh
 
 // ... and with generateGainMap's flags: UHDR_HIP_GENERATE_GAMMA_TABLE lets a gain-map gamma other than 1 through (both presets), evaluated through the
 // host's byte thresholds as uhdr_hip_generate_gainmap_ex_dev evaluates it; flags 0 is the _onepass sibling
-static uhdr_error_info_t check_api1_flags(unsigned int flags, unsigned* route) {
-  if (flags & ~(unsigned int)UHDR_HIP_GENERATE_GAMMA_TABLE)
-    return err_status(UHDR_CODEC_INVALID_PARAM, "unknown generateGainMap flag bits 0x%x", flags & ~(unsigned int)UHDR_HIP_GENERATE_GAMMA_TABLE);
+// edges_entry (the three _edges entry points): UHDR_HIP_ENCODE_RGBA_EDGES is a known bit as well
+static uhdr_error_info_t check_api1_flags(unsigned int flags, unsigned* route, bool edges_entry) {
+  const unsigned int known = UHDR_HIP_GENERATE_GAMMA_TABLE | (edges_entry ? UHDR_HIP_ENCODE_RGBA_EDGES : 0u);
+  if (flags & ~known) return err_status(UHDR_CODEC_INVALID_PARAM, "unknown generateGainMap flag bits 0x%x", flags & ~known);
   if (flags & UHDR_HIP_GENERATE_GAMMA_TABLE) *route |= kApi1GammaTable;
+  if (flags & UHDR_HIP_ENCODE_RGBA_EDGES) *route |= kApi1RgbaEdges;
   return ok_status();
 }
 uhdr_error_info_t uhdr_hip_encode_api1_scans_ex_dev(uhdr_hip_ctx_t* c, const uhdr_raw_image_t* sdr, const uhdr_raw_image_t* hdr, const uhdr_hip_encode_cfg_t* cfg,
@@ -958,7 +970,7 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans_edges_dev(uhdr_hip_ctx_t* c, const 
                                                        size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned int flags) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   unsigned route = kApi1Dev | kApi1AnySdr | kApi1Onepass | kApi1Edges;
-  UHDR_TRY(check_api1_flags(flags, &route));
+  UHDR_TRY(check_api1_flags(flags, &route, /*edges_entry=*/true));
   return encode_api1_scans_impl(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
                                 map_bytes, route);
 }
@@ -968,7 +980,7 @@ uhdr_error_info_t uhdr_hip_encode_api1_scans_edges(uhdr_hip_ctx_t* c, const uhdr
                                                    size_t* base_bytes, uint8_t* map_scan, size_t map_capacity, size_t* map_bytes, unsigned int flags) {
   if (!c) return err_status(UHDR_CODEC_INVALID_PARAM, "received nullptr for uhdr_hip context");
   unsigned route = kApi1AnySdr | kApi1Onepass | kApi1Edges;
-  UHDR_TRY(check_api1_flags(flags, &route));
+  UHDR_TRY(check_api1_flags(flags, &route, /*edges_entry=*/true));
   return encode_api1_scans_timed(c, sdr, hdr, cfg, base_encoding, qt_base, qt_map, md, gainmap_desc, base_scan, base_capacity, base_bytes, map_scan, map_capacity,
                                  map_bytes, route);
 }

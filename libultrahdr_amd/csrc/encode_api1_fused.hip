@@ -541,6 +541,12 @@ __global__ __launch_bounds__(kBlock) void base_blocks_kernel(const BaseBlocksPar
 // column_pass_and_quantize use the wave's workspace, three times per strip.  4 B/px in, 6 B/px out.
 // Rows whose base address and pitch are multiples of 16 bytes are read with two 16-byte loads per lane (VEC); any other pitch takes the
 // same kernel with eight dword loads (pixels are 32-bit words: the base address is a multiple of 4, the launcher's caller checks).
+// EDGE: frames that are not whole blocks, on the ceil(w / 8) x ceil(h / 8) grid.  The reference converts an RGBA intent into an image it
+// allocated itself -- zero-filled, stride ALIGN(w, 64) (gainmapmath.cpp:1447-1449, ultrahdr_api.cpp:50-95) --, convertYuv rewrites w x h of it,
+// and compressYCbCr (jpegencoderhelper.cpp:246-309) sees a stride that covers the block-aligned width: columns past the width are the
+// allocation's zeros in all three planes (never converted), rows past the height are the helper's zero Y row and its memset(128) chroma row
+// over the whole aligned width.  A strip that touches the right or bottom edge (wave-uniform) loads pixel by pixel, predicated per lane --
+// nothing past w pixels of a row or past row h - 1 is read --, every other strip takes the loads of the whole-block kernel.
 struct BaseBlocksRgbaParams {
   const uint32_t* src;     // packed RGBA8888
   uint32_t stride;         // pixels
@@ -550,11 +556,12 @@ struct BaseBlocksRgbaParams {
   Mat3 c;                  // convertYuv's coefficients (host_tables.cpp: yuv_encoding_matrix)
   int16_t* coef[3];
   QuantTables q;
+  uint32_t w, h;           // EDGE: the frame's pixels; bw, bh are ceil(w / 8), ceil(h / 8)
 };
 
 __device__ __forceinline__ float clipf255(float v) { return (v < 0.0f) ? 0.0f : ((v > 255.0f) ? 255.0f : v); }  // convert.hip: clipf
 
-template <bool VEC>
+template <bool VEC, bool EDGE = false>
 __global__ __launch_bounds__(kBlock) void base_blocks_rgba_kernel(const BaseBlocksRgbaParams p) {
   __shared__ int s_ws[kBlock / 64][kWsWords];
   __shared__ uint2 s_q[2][64];
@@ -577,7 +584,18 @@ __global__ __launch_bounds__(kBlock) void base_blocks_rgba_kernel(const BaseBloc
     if (active) {
       const uint32_t* s0 = p.src + ((size_t)(by * 8 + rr) * p.stride + (size_t)bx * 8);
       uint32_t px[8];
-      if (VEC) {
+      bool edge_strip = false;  // (wave-uniform)
+      uint32_t nv = 8;          // EDGE: the pixels of this lane's row that lie inside the frame
+      bool row_in = true;
+      if constexpr (EDGE) {
+        edge_strip = (uint32_t)by * 8 + 8 > p.h || (uint32_t)gx * 64 + 64 > p.w;
+        row_in = (uint32_t)(by * 8 + rr) < p.h;
+        nv = row_in ? min(8u, p.w - (uint32_t)bx * 8) : 0u;
+      }
+      if (EDGE && edge_strip) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) px[j] = (uint32_t)j < nv ? s0[j] : 0u;
+      } else if (VEC) {
         const uint4 a = *(const uint4*)s0, b = *(const uint4*)(s0 + 4);
         px[0] = a.x; px[1] = a.y; px[2] = a.z; px[3] = a.w; px[4] = b.x; px[5] = b.y; px[6] = b.z; px[7] = b.w;
       } else {
@@ -600,6 +618,16 @@ __global__ __launch_bounds__(kBlock) void base_blocks_rgba_kernel(const BaseBloc
         comp[0][j] = yy - 128;
         comp[1][j] = uu - 128;
         comp[2][j] = vv - 128;
+      }
+      if (EDGE && edge_strip) {
+        const int c_out = row_in ? -128 : 0;  // byte 0 of the zero-filled allocation / byte 128 of the helper's chroma row
+#pragma unroll
+        for (int j = 0; j < 8; j++)
+          if ((uint32_t)j >= nv) {
+            comp[0][j] = -128;
+            comp[1][j] = c_out;
+            comp[2][j] = c_out;
+          }
       }
     }
     // fdct_core.h's strip_transform, spelled out: behind the helper call the compiler packs the conversion above into v_pk_* pairs
@@ -673,7 +701,7 @@ static void launch_onepass_n(const MapOnepassParams& p, int nch, int grid, hipSt
 
 // The one-pass gain map of the two intents in g (fill_gen_params + the one-pass range + gain8; g.out: the optional 8-bit map, g.out_stride
 // pixels) -> quantized coefficients of the map's JPEG.  map_w, map_h multiples of 8, gamma 1; SDR 4:2:0 or RGBA8888, every HDR format
-// fill_gen_params takes; nch as in launch_map_blocks.  edges: any map size and any map_out pitch (the EDGE kernel; 4:2:0 SDR intents).
+// fill_gen_params takes; nch as in launch_map_blocks.  edges: any map size and any map_out pitch (the EDGE kernel).
 hipError_t launch_map_blocks_onepass(const GenParams& g, int nch, const uint16_t* qt_luma, const uint16_t* qt_chroma, int16_t* const coef[3],
                                      uint8_t* map_out, uint32_t out_stride, hipStream_t s, bool edges) {
   MapOnepassParams p;
@@ -690,7 +718,6 @@ hipError_t launch_map_blocks_onepass(const GenParams& g, int nch, const uint16_t
   if (grid > cap) grid = cap;
   constexpr int k420 = UHDR_IMG_FMT_12bppYCbCr420, kRgba = UHDR_IMG_FMT_32bppRGBA8888, kP010 = UHDR_IMG_FMT_24bppYCbCrP010, k1010102 = UHDR_IMG_FMT_32bppRGBA1010102;
   // UHDR_HIP_ONEPASS_NO_VECTOR_FETCH=1: the per-sample fetch on every layout (tools/api1_onepass_time.py times the two against each other)
-  if (edges && g.sdr.fmt != k420) return hipErrorInvalidValue;
   if (!edges && g.gain8.tab && map_onepass_fast_layout(g) && !getenv("UHDR_HIP_ONEPASS_NO_VECTOR_FETCH")) {
     if (nch == 3) hipLaunchKernelGGL((map_blocks_onepass_kernel<k420, kP010, 3, true>), dim3(grid), dim3(kMapBlock), 0, s, p);
     else hipLaunchKernelGGL((map_blocks_onepass_kernel<k420, kP010, 1, true>), dim3(grid), dim3(kMapBlock), 0, s, p);
@@ -698,8 +725,8 @@ hipError_t launch_map_blocks_onepass(const GenParams& g, int nch, const uint16_t
     if (g.hdr.fmt == kP010) launch_onepass_n<k420, kP010>(p, nch, grid, s, edges);
     else launch_onepass_n<k420, -1>(p, nch, grid, s, edges);
   } else if (g.sdr.fmt == kRgba) {
-    if (g.hdr.fmt == k1010102) launch_onepass_n<kRgba, k1010102>(p, nch, grid, s, false);
-    else launch_onepass_n<kRgba, -1>(p, nch, grid, s, false);
+    if (g.hdr.fmt == k1010102) launch_onepass_n<kRgba, k1010102>(p, nch, grid, s, edges);
+    else launch_onepass_n<kRgba, -1>(p, nch, grid, s, edges);
   } else {
     return hipErrorInvalidValue;
   }
@@ -740,8 +767,10 @@ hipError_t launch_base_blocks(const ImageView& yuv420, const Mat3* c, const uint
 
 // packed RGBA8888 (w, h multiples of 8; stride in pixels; base address a multiple of 4) -> convert_raw_input_to_ycbcr with the coefficients k
 // of the image's gamut -> [convertYuv with matrix c ->] quantized coefficients of Y, Cb, Cr, each on a (w / 8) x (h / 8) grid
+// edges: any w, h >= 1 and any stride >= w -- the ceil(w / 8) x ceil(h / 8) grid, the samples beyond the frame by the rules at
+// BaseBlocksRgbaParams; a whole-block frame takes the kernel it takes without the flag
 hipError_t launch_base_blocks_rgba(const ImageView& rgba, const Rgb2Yuv& k, const Mat3* c, const uint16_t* qt_luma, const uint16_t* qt_chroma,
-                                   int16_t* const coef[3], hipStream_t s) {
+                                   int16_t* const coef[3], hipStream_t s, bool edges) {
   BaseBlocksRgbaParams p;
   memset(&p, 0, sizeof p);
   p.src = (const uint32_t*)rgba.p[0];
@@ -755,6 +784,14 @@ hipError_t launch_base_blocks_rgba(const ImageView& rgba, const Rgb2Yuv& k, cons
   fill_quant_table(qt_chroma, &p.q.chroma);
   const int grid = resident_grid(((p.bw + 7) / 8) * p.bh, 7);  // 66 VGPRs: seven waves per SIMD, i.e. seven 4-wave workgroups per CU are resident
   const bool vec = ((uintptr_t)rgba.p[0] % 16) == 0 && rgba.stride[0] % 4 == 0;
+  if (edges && (rgba.w % 8 || rgba.h % 8)) {
+    p.bw = (int)((rgba.w + 7) / 8); p.bh = (int)((rgba.h + 7) / 8);
+    p.w = rgba.w; p.h = rgba.h;
+    const int edge_grid = resident_grid(((p.bw + 7) / 8) * p.bh, 7);  // (the EDGE instantiations: 70 VGPRs, seven waves per SIMD as well)
+    if (vec) hipLaunchKernelGGL((base_blocks_rgba_kernel<true, true>), dim3(edge_grid), dim3(kBlock), 0, s, p);
+    else hipLaunchKernelGGL((base_blocks_rgba_kernel<false, true>), dim3(edge_grid), dim3(kBlock), 0, s, p);
+    return hipGetLastError();
+  }
   if (vec) hipLaunchKernelGGL((base_blocks_rgba_kernel<true>), dim3(grid), dim3(kBlock), 0, s, p);
   else hipLaunchKernelGGL((base_blocks_rgba_kernel<false>), dim3(grid), dim3(kBlock), 0, s, p);
   return hipGetLastError();

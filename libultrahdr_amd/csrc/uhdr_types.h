@@ -295,7 +295,7 @@ hipError_t launch_map_blocks_onepass(const GenParams& g, int nch, const uint16_t
 hipError_t launch_base_blocks(const ImageView& yuv420, const Mat3* c, const uint16_t* qt_luma, const uint16_t* qt_chroma, int16_t* const coef[3],
                               hipStream_t s, bool edges = false, int col_mode = -1);
 hipError_t launch_base_blocks_rgba(const ImageView& rgba, const Rgb2Yuv& k, const Mat3* c, const uint16_t* qt_luma, const uint16_t* qt_chroma,
-                                   int16_t* const coef[3], hipStream_t s);
+                                   int16_t* const coef[3], hipStream_t s, bool edges = false);
 hipError_t launch_selftest(int which, unsigned long long* out, uint32_t arg0, uint32_t arg1, uint32_t seed, const double* math_tab, const AffineDev* dev,
                            hipStream_t s, const float* thr = nullptr);  // selftest.hip
 int gen_partials_count(const GenParams& p);  // workgroups (= partials) launch_generate_gainmap(p, two_pass = true) writes

@@ -471,7 +471,9 @@ class UltraHdr:
         (uhdr_hip_encode_api1_fused_edges_dev; jpegencoderhelper.cpp:246-309): a 4:2:0 SDR intent of any even size, a map of any size.  The
         coefficient tensors sit on libjpeg's width_in_blocks grids -- luma (ceil(h/8), ceil(w/8), 64), chroma (ceil(h/16), ceil(w/16), 64),
         map (ceil(mh/8), ceil(mw/8), 64).  An RGBA8888 intent is taken as encodeApi1FusedOnePass takes it: dimensions multiples of 8 and a map
-        of whole 8 x 8 blocks, else UhdrError (the edge handling is for 4:2:0 intents).  gm: a caller's device map image of any stride >= mw (a fresh 64-aligned one when None and
+        of whole 8 x 8 blocks, else UhdrError -- unless flags carries A.UHDR_HIP_ENCODE_RGBA_EDGES: then an RGBA8888 intent of any size and pitch is
+        taken too, three base tensors of (ceil(h/8), ceil(w/8), 64), zero columns behind the width and 0 / 128 rows below the height as the
+        reference's own zero-filled 64-aligned conversion image gives them.  gm: a caller's device map image of any stride >= mw (a fresh 64-aligned one when None and
         want_map).  Returns (base coefficient tensors [3], map coefficient tensors [1 or 3], metadata, gainmap Image or None)."""
         import torch
 
@@ -503,7 +505,8 @@ class UltraHdr:
                              sdr_is_601=False, use_luminance=True):
         """encodeApi1ScansEx for frames that are not whole MCUs and maps that are not whole blocks -- 1920 x 1080, 4000 x 3000
         (uhdr_hip_encode_api1_scans_edges_dev for device images, uhdr_hip_encode_api1_scans_edges for host images): same arguments, same
-        returns; the scans carry the real blocks of the true w x h, as uhdr_hip_jpeg_encode_image writes them."""
+        returns; the scans carry the real blocks of the true w x h, as uhdr_hip_jpeg_encode_image writes them.  With
+        A.UHDR_HIP_ENCODE_RGBA_EDGES in flags an RGBA8888 intent off the block grid, in frame or map, is taken as well."""
         lib, fl = self.lib, C.c_uint(flags)
         return self.encodeApi1ScansAny(sdr_intent, hdr_intent, base_encoding, qt_base, qt_map, out_base, out_map, sdr_is_601, use_luminance,
                                        _fns=(lambda *a: lib.uhdr_hip_encode_api1_scans_edges_dev(*a, fl), lambda *a: lib.uhdr_hip_encode_api1_scans_edges(*a, fl)))
